@@ -6,12 +6,17 @@ Workload = BASELINE.json configs[1]: 19x19 board, 20-block x 256-filter network 
 weights (seeded).  A "step" is one pass of the whole network over one batch of 256 positions
 whose input planes are already resident in HBM; value = whole-job evals/s over all ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU; positions (games) shard embarrassingly, there is no data-path
 collective -- torch.distributed (RCCL) is used only for the start/stop barrier, the
 max-over-ranks timing and the stats gather.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes what the timed steps computed in the last of them -- the raw outputs sayuri_hip_download hands
+a caller -- as DIR/<name>.npy (float32): prob [n][5][361], pass [n][5], misc [n][15], own [n][361].  Inputs are seeded,
+so two builds run with the same arguments can be compared output for output.  Rank r > 0 writes DIR/<name>_rank<r>.npy.
+Above 64 MiB in all, every rank writes the same seeded sample of its positions (sorted indices).
 """
 from __future__ import annotations
 
@@ -318,6 +323,31 @@ def cpu_baseline(weights_path: str, planes, seconds: float = 15.0, pipe=None, fp
                       "Eigen / OpenBLAS are not in this image, the three CPU variants differ only in the GEMM call (blas.cc:16-166)"}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(lib, ctx, n: int, board: int, spec, out_dir: str, rank: int, world: int) -> None:
+    """The raw outputs of the last forward of the uploaded batch (sayuri_hip_download) -> out_dir/<name>[_rank<r>].npy."""
+    from sayuri_amd import _lib
+    B2 = board * board
+    prob_ch, pass_outs, misc_outs = (5, 5, 15) if spec.version >= 3 else (1, 1, 5)
+    outs = {"prob": np.zeros((n, prob_ch, B2), np.float32), "pass": np.zeros((n, pass_outs), np.float32),
+            "misc": np.zeros((n, misc_outs), np.float32), "own": np.zeros((n, B2), np.float32)}
+    fp = lambda a: a.ctypes.data_as(_lib.c_float_p)
+    if lib.sayuri_hip_download(ctx, fp(outs["prob"]), fp(outs["pass"]), fp(outs["misc"]), fp(outs["own"])):
+        raise RuntimeError(lib.sayuri_hip_last_error().decode())
+    per_sample = sum(a[0].nbytes for a in outs.values())
+    keep = min(n, (DUMP_BYTES // world) // per_sample)
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        outs = {k: a[idx] for k, a in outs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for k, a in outs.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
+    print(f"bench.py: rank {rank} wrote {', '.join(outs)} ({keep} of {n} positions) to {out_dir}", file=sys.stderr)
+
+
 def launch_ranks(n: int, port: int) -> int:
     """`python bench.py --gpus N` without a launcher: be the launcher.  Checks that the box has N devices (the HIP library's
     own count; SAYURI_BENCH_SHARE_DEVICE is the one-GPU test hook that lets ranks share), then runs this file's own command line
@@ -374,10 +404,16 @@ def main():
                          "fake device; also SAYURI_DIST_BACKEND)")
     ap.add_argument("--master-port", type=int, default=int(os.environ.get("SAYURI_BENCH_MASTER_PORT", "29571")),
                     help="rendezvous port of the ranks a plain `python bench.py --gpus N` starts itself")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the raw outputs of the last one to DIR/<name>.npy (see the head of this file)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # A plain `python bench.py --gpus N` (no launcher around it): start the N ranks here -- one process per GPU, the
         # command line the docstring names, with this process as the launcher.  The reference does the in-process form of
@@ -476,6 +512,8 @@ def main():
 
     stat = _lib.KernelStat()
     lib.sayuri_hip_timed_stat(ctx, ctypes.byref(stat))
+    if args.dump_outputs:
+        dump_outputs(lib, ctx, n, 19, spec, args.dump_outputs, rank, world)
     pump = pump_segment(lib, ctx, grid, n, max(args.steps, 40)) if args.pump else None
     pump_packed = pump_segment(lib, ctx, grid, n, max(args.steps, 40), packed=True) if args.pump else None
 

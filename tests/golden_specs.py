@@ -67,3 +67,8 @@ FIXTURES = [
     dict(name="net_40b384", spec=W.spec_40b384, seed=23, commit_weights=False, winograd=(1,), store_planes=False,
          cases=((19, 0, 601), (13, 1, 602), (9, 2, 603), (19, 3, 604))),
 ]
+
+
+# tests/golden/training_chunk.npz (generator: tests/golden/make_golden_chunks.py): one self-play game with one worker, so
+# that its training chunk is a pure function of the seed
+TRAINING_CHUNK_GAME = dict(playouts=60, parallel_games=1, num_games=1, seed=3, selfplay_query=["bkp:9:7:1"])

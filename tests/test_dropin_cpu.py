@@ -1,22 +1,13 @@
-"""CPU-side drop-in checks: the host pipe compiles against the REFERENCE's headers when
-/root/reference is mounted (dev container only), and the sharded bench path works under gloo."""
+"""CPU-side drop-in checks: the sharded bench path works under gloo.  (That the host pipe compiles against the
+REFERENCE's headers is checked by build() itself where the reference tree exists: oracle/Makefile, target ref.)"""
 import json
 import os
 import subprocess
 import sys
 
-import pytest
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference tree not mounted")
-def test_pipe_compiles_in_reference_tree():
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-DSAYURI_IN_TREE", "-I/root/reference/src",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "sayuri_amd", "csrc", "host"),
-           os.path.join(ROOT, "sayuri_amd", "csrc", "host", "hip_forward_pipe.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
 
 
 def test_sharded_stats_gather_gloo_world2(tmp_path):
@@ -209,6 +200,25 @@ def test_plain_bench_command_with_eight_ranks(tmp_path):
     assert d["n_gpus"] == 8 and d["config"]["parallelism"] == "dp8" and d["config"]["global_batch"] == 8 * 256
     assert d["selfplay"]["exchange"]["world"] == 8 and d["selfplay"]["exchange_rounds"] > 0
     assert "cpu_baseline" not in d and "config5" not in d
+
+
+def test_bench_dumps_the_outputs_of_the_timed_path(tmp_path):
+    """--dump-outputs DIR: the raw outputs of the last timed step as DIR/<name>.npy (float32, the shapes sayuri_hip_download
+    fills for the 20b256 net at batch 256 on 19x19), each rank of a multi-rank run under names of its own; --steps 0 is
+    refused, not run as some other number of steps."""
+    out = tmp_path / "dump"
+    d = _bench_on_the_fake_device(tmp_path, 2, 29559, launcher=False, seconds=0,
+                                  extra=["--no-pump", "--no-config5", "--dump-outputs", str(out)])
+    assert d["n_gpus"] == 2 and d["steps"] == 5
+    shapes = {"prob": (256, 5, 361), "pass": (256, 5), "misc": (256, 15), "own": (256, 361)}
+    want = {f"{k}{s}.npy" for k in shapes for s in ("", "_rank1")}
+    assert {f.name for f in out.iterdir()} == want
+    for f in out.iterdir():
+        a = np.load(f)
+        assert a.dtype == np.float32 and a.shape == shapes[f.name.split(".")[0].split("_")[0]], (f.name, a.dtype, a.shape)
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    r = _bench_on_the_fake_device(tmp_path, 1, 29561, extra=["--steps", "0"], check=False)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr, r.stderr[-2000:]
 
 
 def test_bench_refuses_more_ranks_than_devices(tmp_path):

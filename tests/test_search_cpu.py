@@ -124,30 +124,25 @@ def test_selfplay_pipe_dummy_backend(tmp_path):
     assert (a["moves"], a["playouts"], a["records"]) == (b["moves"], b["playouts"], b["records"]) and a["games_done"] == 2
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/train/torch"), reason="reference trainer only in the dev container")
 def test_training_chunks_parse_with_reference_reader(tmp_path):
-    """The reference's own Python chunk parser (train/torch/data.py) must accept what the writer emits."""
+    """The reference's own Python chunk parser (train/torch/data.py) must accept what the writer emits.
+    tests/golden/training_chunk.npz holds a chunk of a single-worker game (a pure function of its seed) and what that
+    parser read from it (generator: tests/golden/make_golden_chunks.py): the writer must emit that chunk byte for byte."""
     import glob
     import gzip
-    import sys
-    S.selfplay(None, dict(playouts=60, parallel_games=2, num_games=2, seed=3, selfplay_query=["bkp:9:7:1"], target_directory=str(tmp_path)))
-    sys.path.insert(0, "/root/reference/train/torch")
-    try:
-        import data as refdata
-    finally:
-        sys.path.pop(0)
-    import io
-    text = gzip.open(sorted(glob.glob(str(tmp_path / "tdata" / "*" / "*.gz")))[0]).read().decode()
-    stream, count = io.StringIO(text), 0
-    while True:
-        d = refdata.Data()
-        if not d.load_from_stream(stream):
-            break
-        d.parse()
-        count += 1
-        assert d.board_size == 9 and d.planes.shape == (37, 81) and abs(float(np.sum(d.prob)) - 1.0) < 1e-3
-        assert len(d.ownership) == 81 and d.result in (-1, 0, 1) and d.to_move in (0, 1)
-    assert count == text.count("\n") // 53 and count > 10
+
+    from golden_specs import TRAINING_CHUNK_GAME
+    g = np.load(os.path.join(ROOT, "tests", "golden", "training_chunk.npz"))
+    S.selfplay(None, dict(TRAINING_CHUNK_GAME, target_directory=str(tmp_path)))
+    text = gzip.open(sorted(glob.glob(str(tmp_path / "tdata" / "*" / "*.gz")))[0]).read()
+    want = zlib.decompress(g["text"].tobytes())
+    diff = next((k for k, (a, b) in enumerate(zip(text.split(b"\n"), want.split(b"\n"))) if a != b), None)
+    assert text == want, f"the writer's chunk is not the stored one (first different line: {diff})"
+    count = len(g["board_size"])
+    for i in range(count):
+        assert g["board_size"][i] == 9 and g["planes"][i].shape == (37, 81) and abs(float(np.sum(g["prob"][i])) - 1.0) < 1e-3
+        assert len(g["ownership"][i]) == 81 and g["result"][i] in (-1, 0, 1) and g["to_move"][i] in (0, 1)
+    assert count == text.count(b"\n") // 53 and count > 10
 
 
 def test_writer_pool_and_parallel_flush(tmp_path):
