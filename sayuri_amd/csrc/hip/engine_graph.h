@@ -72,11 +72,11 @@ public:
         // network evicting each other's L2 lines) and kept one compute stream; round 5 re-measured on the kernels of today --
         // 40b x 384 through submit / wait, two tickets in flight: a stream per ticket 26.3 k evals/s, one compute stream 23.7 k
         // (a layer is 450 workgroups, two rounds of the CUs, and the other ticket's launches fill the second; 200 batches
-        // bit-identical to the solo result, tools/gpu/c5_pump.py, concurrent_ctx_dbg.py).  Without the code object
+        // bit-identical to the solo result, profiles/r05_config5_pump_streams.json, tools/gpu/concurrent_ctx_dbg.py).  Without the code object
         // (SAYURI_TOWER=0, or a build whose seam was rejected) the older three-stream arrangement stays.
         if (describe_layers()) return -1;
-        inorder_ = flags_.io_inorder && tower_fn_[0] != nullptr;
-        if (flags_.compute_streams == 2 || inorder_) HIP_OK(hipStreamCreateWithFlags(&compute_[1], hipStreamNonBlocking));
+        inorder_ = tower_fn_[0] != nullptr;
+        if (inorder_) HIP_OK(hipStreamCreateWithFlags(&compute_[1], hipStreamNonBlocking));
         return 0;
     }
     // every 3x3 convolution of the residual tower has 128 or 256 (padded) output channels and there is at least one
@@ -176,7 +176,7 @@ public:
         HIP_OK(hipSetDevice(device_));
         if (finalize()) return -1;
         select_slot(t);
-        // Default (SAYURI_IO_INORDER=0 is the older arrangement below): everything of a ticket on the ticket's own stream, in
+        // With the tower code object loaded (init()): everything of a ticket on the ticket's own stream, in
         // order -- no event between streams at all.  Each record / wait is a marker the runtime's signal thread handles; the
         // seven per batch of the three-stream arrangement kept that thread at a full host core during self-play (one of
         // eight busy; profiles/r04_host_profile.txt), for the same evals/s.  The other ticket's stream overlaps its copies
@@ -198,10 +198,9 @@ public:
             if (!inorder && tick_ev_[t]) HIP_OK(hipStreamWaitEvent(stream_, tick_ev_[t], 0));  // the download that last read this slot's outputs
         }
         have_batch_ = true;
-        if (fwdstat_) {  // SAYURI_HIP_FWDSTAT (measuring aid): device time of every submitted forward
+        if (flags_.fwdstat) {  // SAYURI_HIP_FWDSTAT (measuring aid): device time of every submitted forward
             for (int k = 0; k < 2; ++k)
                 if (!fs_ev_[t][k]) HIP_OK(hipEventCreate(&fs_ev_[t][k]));
-
             HIP_OK(hipEventRecord(fs_ev_[t][0], stream_));
         }
         const int uploads_before = table_uploads_;
@@ -213,14 +212,14 @@ public:
         // So nothing small is copied any more: the heads kernel stores pass / misc straight into the caller's pinned
         // buffers (20 KB of posted PCIe writes), a uniform batch uses geometry arrays that are resident (enqueue_inputs),
         // and the tower table does not depend on the batch size (tower_append).  The two large outputs keep their DMA copies.
-        zc_pass_ = flags_.io_zc ? zc_device_pointer(pass) : nullptr;
+        zc_pass_ = zc_device_pointer(pass);
         zc_misc_ = zc_pass_ ? zc_device_pointer(misc) : nullptr;
         if (!zc_misc_) zc_pass_ = nullptr;  // both or neither: the heads kernel takes one path
         const int frc = forward();
         const bool small_direct = zc_pass_ != nullptr;
         zc_pass_ = zc_misc_ = nullptr;
         if (frc) return -1;
-        if (fwdstat_) {
+        if (flags_.fwdstat) {
             HIP_OK(hipEventRecord(fs_ev_[t][1], stream_));
             fs_pending_[t] = true;
             fs_n_[t] = n;
@@ -239,7 +238,7 @@ public:
         HIP_OK(hipMemcpyAsync(own, d_own_, sizeof(float) * n * B2, hipMemcpyDeviceToHost, down));
         if (!tick_ev_[t]) HIP_OK(hipEventCreateWithFlags(&tick_ev_[t], hipEventDisableTiming));
         HIP_OK(hipEventRecord(tick_ev_[t], down));
-        if (fwdstat_) {
+        if (flags_.fwdstat) {
             if (!fs_ev_[t][2]) HIP_OK(hipEventCreate(&fs_ev_[t][2]));
             HIP_OK(hipEventRecord(fs_ev_[t][2], down));
         }
@@ -251,7 +250,7 @@ public:
         HIP_OK(hipSetDevice(device_));
         HIP_OK(hipEventSynchronize(tick_ev_[ticket]));
         if (sx_check()) return -1;
-        if (fwdstat_ && fs_pending_[ticket]) {
+        if (flags_.fwdstat && fs_pending_[ticket]) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, fs_ev_[ticket][0], fs_ev_[ticket][1]) == hipSuccess) {
                 const int b = fs_n_[ticket] >= max_batch_ ? 2 : (fs_n_[ticket] * 2 > max_batch_ ? 1 : 0);
@@ -263,7 +262,6 @@ public:
                 fs_d2h_max_ = std::max(fs_d2h_max_, (double)ms);
                 fs_d2h_slow_ += ms > 1.0f;
             }
-
             fs_pending_[ticket] = false;
         }
         return 0;
@@ -330,8 +328,8 @@ public:
     }
     std::map<int, IdentGeom> ident_;
 
-    // geometry + planes H2D on the stream (no sync).  The geometry arrays are staged in a
-    // 2-deep pinned ring so a second batch can be enqueued while the first is still copying.
+    // geometry + planes to the device (no sync): the planes or packed records H2D on `copy_stream`, the geometry arrays of a
+    // mixed batch from a 2-deep pinned ring (a second batch can be enqueued while the first is still in flight) on stream_.
     int enqueue_inputs(int n, const float* planes, const int* board_sizes, hipStream_t copy_stream, const unsigned* packed = nullptr,
                        int binary = 0, bool in_place = false) {
         HIP_OK(hipSetDevice(device_));
@@ -372,7 +370,7 @@ public:
         // One sample per tile and one board size: the tables of a LONGER batch of the same size serve a shorter one (tile i
         // depends on sample i alone), so a queue that alternates between 256 and 250 positions keeps its tables.
         const bool one_per_tile = uniform && 2 * geom_.bsz[0] * geom_.bsz[0] > kBoardPT;
-        const bool prefix = flags_.io_prefix && one_per_tile && slot.tabs_single && slot.tabs_bsz.size() >= (size_t)n &&
+        const bool prefix = one_per_tile && slot.tabs_single && slot.tabs_bsz.size() >= (size_t)n &&
                             slot.tabs_bsz[0] == geom_.bsz[0];
         if (!prefix && slot.tabs_bsz != geom_.bsz) {  // this slot's tables were built for another geometry
             for (auto& kv : slot.tabs) kv.second.fresh = false;
@@ -391,30 +389,19 @@ public:
         // batch stages its arrays in a pinned ring and a one-workgroup kernel ON THE FORWARD'S OWN STREAM moves them: a
         // copy of a few KB is a blit kernel to the runtime, and on the copy stream it would wait for the other ticket's
         // persistent tower launch to give up a CU (see submit()).
-        if (flags_.io_geom) {
-            if (uniform) {
-                const IdentGeom* id = ident_geom(geom_.bsz[0]);
-                if (!id) return -1;
-                d_off_ = id->off; d_bsz_ = id->bsz; d_perm_ = id->perm;
-            } else {
-                d_off_ = slot.off; d_bsz_ = slot.bsz; d_perm_ = slot.perm;
-                int* hg = h_geom_ + (size_t)geom_slot_ * (3 * max_batch_ + 1);
-                geom_slot_ ^= 1;
-                std::memcpy(hg, geom_.off.data(), sizeof(int) * (n + 1));
-                std::memcpy(hg + max_batch_ + 1, geom_.bsz.data(), sizeof(int) * n);
-                std::memcpy(hg + 2 * max_batch_ + 1, perm_.data(), sizeof(int) * n);
-                hipLaunchKernelGGL(geom_stage_kernel, dim3(1), dim3(256), 0, stream_, (const int*)hg, max_batch_, n, d_off_, d_bsz_, d_perm_);
-                HIP_OK(hipGetLastError());
-            }
+        if (uniform) {
+            const IdentGeom* id = ident_geom(geom_.bsz[0]);
+            if (!id) return -1;
+            d_off_ = id->off; d_bsz_ = id->bsz; d_perm_ = id->perm;
         } else {
+            d_off_ = slot.off; d_bsz_ = slot.bsz; d_perm_ = slot.perm;
             int* hg = h_geom_ + (size_t)geom_slot_ * (3 * max_batch_ + 1);
             geom_slot_ ^= 1;
             std::memcpy(hg, geom_.off.data(), sizeof(int) * (n + 1));
             std::memcpy(hg + max_batch_ + 1, geom_.bsz.data(), sizeof(int) * n);
             std::memcpy(hg + 2 * max_batch_ + 1, perm_.data(), sizeof(int) * n);
-            HIP_OK(hipMemcpyAsync(d_off_, hg, sizeof(int) * (n + 1), hipMemcpyHostToDevice, copy_stream));
-            HIP_OK(hipMemcpyAsync(d_bsz_, hg + max_batch_ + 1, sizeof(int) * n, hipMemcpyHostToDevice, copy_stream));
-            HIP_OK(hipMemcpyAsync(d_perm_, hg + 2 * max_batch_ + 1, sizeof(int) * n, hipMemcpyHostToDevice, copy_stream));
+            hipLaunchKernelGGL(geom_stage_kernel, dim3(1), dim3(256), 0, stream_, (const int*)hg, max_batch_, n, d_off_, d_bsz_, d_perm_);
+            HIP_OK(hipGetLastError());
         }
         IoSlot& io = io_[cur_slot_];
         io.packed_binary = packed ? binary : 0;
@@ -428,7 +415,7 @@ public:
             // one forward after another on one stream; tools/pump_gaps.py, profiles/r05_pump_gaps.txt).  The caller keeps the
             // records untouched until wait(), as it must for the asynchronous copy.
             io.packed_src = nullptr;
-            if (in_place && flags_.io_zc_in) io.packed_src = (const unsigned*)zc_device_pointer((float*)const_cast<unsigned*>(packed));
+            if (in_place) io.packed_src = (const unsigned*)zc_device_pointer((float*)const_cast<unsigned*>(packed));
             if (io.packed_src) return 0;
             if (!io.packed && dev_alloc(&io.packed, (size_t)max_batch_ * (40 * 12 + 8))) return -1;
             HIP_OK(hipMemcpyAsync(io.packed, packed, sizeof(unsigned) * n * words, hipMemcpyHostToDevice, copy_stream));
@@ -875,7 +862,7 @@ private:
         for (hipEvent_t& e : chain_join_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
         if (chain_fork_) (void)hipEventDestroy(chain_fork_);
         chain_fork_ = nullptr;
-        if (fwdstat_ && fs_cnt_[0] + fs_cnt_[1] + fs_cnt_[2] > 0) {
+        if (flags_.fwdstat && fs_cnt_[0] + fs_cnt_[1] + fs_cnt_[2] > 0) {
             const long all = fs_cnt_[0] + fs_cnt_[1] + fs_cnt_[2];
             std::fprintf(stderr, "[hip fwdstat] forwards by batch size (<= half | partial | full): %ld / %ld / %ld, mean device ms %.4f / %.4f / %.4f, tower table uploads %ld; "
                          "forward end -> downloads done: mean %.3f ms, max %.3f, > 1 ms: %ld\n",
@@ -1032,11 +1019,12 @@ private:
         *out = &t;
         return 0;
     }
-    // the one-workgroup-per-board kernel applies to fp16 3x3 layers whose boards fit a tile and fill it reasonably
+    // The one-workgroup-per-board kernel applies to fp16 3x3 layers whenever the batch's boards fit its tiles, however empty
+    // the tiles are: which convolution kernel a sample meets must not depend on its batch mates (a lone 9x9 board fills a fifth
+    // of its tile; with the across-sample kernel it came out ~1e-4 away from the same position inside a larger batch).
     const BoardEntry* choose_board(const ConvLayerDev& L, int* kot_tiles) {
         if (sizeof(T) != 2 || L.k != 3) return nullptr;
         if (!board_plan_valid_) { board_plan_ = board_plan(geom_, flags_.conv); board_plan_valid_ = true; }
-        if (!board_plan_.ok || board_plan_.fill < flags_.conv.board_min_fill) return nullptr;
         return pick_board(board_plan_, L.ko_pad, kot_tiles, flags_.board_kot);
     }
 
@@ -1073,7 +1061,6 @@ private:
         // one each -- lead the batch: tiles [0, nbig) fused, tiles [nbig, ntiles) = samples [nbig, n) plain convolution + SE unit.
         int nbig = 0;
         while (nbig < geom_.n && 2 * geom_.bsz[nbig] * geom_.bsz[nbig] > kBoardPT) ++nbig;
-        if (!flags_.se_by_geometry) nbig = board_plan_.single ? geom_.n : 0;  // SAYURI_SE_BY_GEOMETRY=0: round 4's rule (A/B, tests)
         if (nbig == 0) return 1;
         const bool split = nbig < geom_.n;
         const BoardTabs* tabs = nullptr;
@@ -1081,14 +1068,10 @@ private:
         BoardSeParams sp;
         std::memset(&sp, 0, sizeof(sp));  // padding too: the tower table is compared bytewise with its cached copy
         BoardParams& bp = sp.b;
-        bp.tab_src = tabs->src; bp.tab_pix = tabs->pix; bp.tab_cols = tabs->cols; bp.npos = board_plan_.npos; bp.dbg = nullptr;
-        bp.uniform_info = board_plan_.uniform_info;
-        bp.arith = (board_plan_.single && board_plan_.uniform_info >= 0 && flags_.arith) ? 1 : 0;
+        board_params(bp, board_plan_, tabs->src, tabs->pix, tabs->cols, flags_.arith);
         ConvParams& p = bp.c;
-        p.in = in; p.w = L.w; p.bias = L.bias; p.res = res; p.out = out;
-        p.g = dgeom();
-        p.cin_s = L.cin_s; p.cout_s = L.cout_s; p.ko_pad = L.ko_pad;
-        p.taps = 9; p.act = act; p.npos = 0; p.num_pix_tiles = board_plan_.ntiles;
+        conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+        p.npos = 0; p.num_pix_tiles = board_plan_.ntiles;
         sp.squeeze = sq.dev(); sp.excite = ex.dev(); sp.C = C;
         sp.w1h = staged ? sq.img16 : nullptr; sp.w2h = staged ? ex.img16 : nullptr;
         sp.w1_bytes = sq.img_bytes; sp.w2_bytes = ex.img_bytes;
@@ -1098,9 +1081,8 @@ private:
             if (++dbg_se_call_ == -flags_.board_dbg) { bp.dbg = d_dbg_; dbg_is_se_ = true; }
         }
 #endif
-        const double px = geom_.total;
-        const double flops = 2.0 * px * L.cin * L.cout * 9 + 2.0 * geom_.n * ((double)sq.in * sq.out + (double)ex.in * ex.out);
-        const double bytes = sizeof(T) * (px * L.cin + px * L.cout * (res ? 2 : 1) + (double)L.cin * L.cout * 9);
+        const ConvCost cost = conv_cost(geom_.total, L.cin, L.cout, 9, res, sizeof(T));
+        const double flops = cost.flops + 2.0 * geom_.n * ((double)sq.in * sq.out + (double)ex.in * ex.out), bytes = cost.bytes;
         if (board_row_order_ok(L, be, bp, act)) { p.w = L.w_board; p.bias = L.bias_board; bp.row_order = 1; }
         const bool to_run = !split && tower_ok(be->kot) && !bp.dbg;
         if (!run_.empty() && !(to_run && run_kot_ == be->kot) && tower_flush()) return -1;
@@ -1162,17 +1144,11 @@ private:
         BoardSxParams sp;
         std::memset(&sp, 0, sizeof(sp));
         BoardParams& bp = sp.b;
-        bp.tab_src = tabs->src; bp.tab_pix = tabs->pix; bp.tab_cols = tabs->cols; bp.npos = board_plan_.npos; bp.dbg = nullptr;
-        bp.uniform_info = board_plan_.uniform_info;
-        bp.arith = (board_plan_.single && board_plan_.uniform_info >= 0 && flags_.arith) ? 1 : 0;
+        board_params(bp, board_plan_, tabs->src, tabs->pix, tabs->cols, flags_.arith);
         ConvParams& p = bp.c;
-        p.in = in; p.w = L.w; p.bias = L.bias; p.res = res; p.out = out;
-        p.g = dgeom();
-        p.cin_s = L.cin_s; p.cout_s = L.cout_s; p.ko_pad = L.ko_pad;
-        p.taps = 9; p.act = act;
+        conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
         const size_t lds = be->lds(board_plan_.npos);
         const int kts = sx_kts_;
-        const double px_all = range_px();
         if (f1 > f0) {
             p.npos = f0; p.num_pix_tiles = f1 - f0;
             sp.w1t = sq.sx_img; sp.w2t = ex.sx_img; sp.w1_bytes = sq.sx_bytes; sp.w2_bytes = ex.sx_bytes;
@@ -1184,11 +1160,10 @@ private:
                 sp.b.dbg = d_sxdbg_;
             }
             const int s0 = board_plan_.tile_first[f0], s1 = board_plan_.tile_first[f1];
-            const double px = (double)(geom_.off[s1] - geom_.off[s0]);
-            const double flops = 2.0 * px * L.cin * L.cout * 9 + 2.0 * (s1 - s0) * ((double)sq.in * sq.out + (double)ex.in * ex.out);
-            const double bytes = sizeof(T) * (px * L.cin + px * L.cout * (res ? 2 : 1) + (double)L.cin * L.cout * 9);
+            const ConvCost cost = conv_cost(geom_.off[s1] - geom_.off[s0], L.cin, L.cout, 9, res, sizeof(T));
+            const double flops = cost.flops + 2.0 * (s1 - s0) * ((double)sq.in * sq.out + (double)ex.in * ex.out);
             const int grid = (f1 - f0 + 7) / 8 * 8 * kts;
-            if (timed("conv3x3_tower_sx", flops, bytes, [&] { hipLaunchKernelGGL(conv_board_sx_kernel<2>, dim3(grid), dim3(512), lds, stream_, sp); }))
+            if (timed("conv3x3_tower_sx", flops, cost.bytes, [&] { hipLaunchKernelGGL(conv_board_sx_kernel<2>, dim3(grid), dim3(512), lds, stream_, sp); }))
                 return -1;
         }
         if (r1 > r0) {
@@ -1197,15 +1172,12 @@ private:
             rest.c.res = nullptr; rest.c.act = kIdentity;
             rest.c.npos = r0; rest.c.num_pix_tiles = r1 - r0;
             const int s0 = board_plan_.tile_first[r0], s1 = board_plan_.tile_first[r1];
-            const double px = (double)(geom_.off[s1] - geom_.off[s0]);
-            const double flops = 2.0 * px * L.cin * L.cout * 9;
-            const double bytes = sizeof(T) * (px * L.cin + px * L.cout + (double)L.cin * L.cout * 9);
+            const ConvCost cost = conv_cost(geom_.off[s1] - geom_.off[s0], L.cin, L.cout, 9, false, sizeof(T));
             const auto fn2 = be->fn;
             const int grid2 = (r1 - r0) * kts;
-            if (timed("conv3x3_tower", flops, bytes, [&] { hipLaunchKernelGGL(fn2, dim3(grid2), dim3(512), lds, stream_, rest); })) return -1;
+            if (timed("conv3x3_tower", cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn2, dim3(grid2), dim3(512), lds, stream_, rest); })) return -1;
             if (se_unit(sq, ex, out, res, C, round_up(C, 32), act, s0, s1 - s0)) return -1;
         }
-        (void)px_all;
         return 0;
     }
 
@@ -1215,11 +1187,7 @@ private:
             const BoardTabs* tabs = nullptr;
             if (board_tabs(&tabs)) return -1;
             BoardParams bp;
-            std::memset(&bp, 0, sizeof(bp));
-            bp.tab_src = tabs->src; bp.tab_pix = tabs->pix; bp.tab_cols = tabs->cols; bp.npos = board_plan_.npos;
-            bp.dbg = nullptr;
-            bp.uniform_info = board_plan_.uniform_info;
-        bp.arith = (board_plan_.single && board_plan_.uniform_info >= 0 && flags_.arith) ? 1 : 0;
+            board_params(bp, board_plan_, tabs->src, tabs->pix, tabs->cols, flags_.arith);
             auto fn = be->fn;
 #ifdef SAYURI_EXPERIMENTS
             if (be->kot == 256 && flags_.board_dbg > 0 && !strcmp(name, "conv3x3_tower")) {
@@ -1232,16 +1200,12 @@ private:
             }
 #endif
             ConvParams& p = bp.c;
-            p.in = in; p.w = L.w; p.bias = L.bias; p.res = res; p.out = out;
-            p.g = dgeom();
-            p.cin_s = L.cin_s; p.cout_s = L.cout_s; p.ko_pad = L.ko_pad;
-            p.taps = 9; p.act = act; p.npos = rg_tile0_; p.num_pix_tiles = range_ntiles();  // (npos: the launch's first tile, conv_board_kernel)
+            conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+            p.npos = rg_tile0_; p.num_pix_tiles = range_ntiles();  // (npos: the launch's first tile, conv_board_kernel)
 #ifdef SAYURI_EXPERIMENTS
             if (flags_.act_override >= 0) p.act = flags_.act_override;  // timing experiments only
 #endif
-            const double px = range_px();
-            const double flops = 2.0 * px * L.cin * L.cout * 9;
-            const double bytes = sizeof(T) * (px * L.cin + px * L.cout * (res ? 2 : 1) + (double)L.cin * L.cout * 9);
+            const ConvCost cost = conv_cost(range_px(), L.cin, L.cout, 9, res, sizeof(T));
             const bool to_run = bkt == 1 && tower_ok(be->kot) && !bp.dbg && rg_ntiles_ < 0;
             // a pending run this layer does not join ends here (a launch = an ordered point: the table starts afresh)
             if (!run_.empty() && !(to_run && run_kot_ == be->kot) && tower_flush()) return -1;
@@ -1251,11 +1215,11 @@ private:
                 BoardSeParams sp;
                 std::memset(&sp, 0, sizeof(sp));
                 sp.b = bp;
-                return tower_append(be->kot, sp, false, flops, bytes);
+                return tower_append(be->kot, sp, false, cost.flops, cost.bytes);
             }
             const size_t lds = be->lds(board_plan_.npos);
             const int grid = range_ntiles() * bkt;
-            return timed(name, flops, bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, bp); });
+            return timed(name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, bp); });
         }
         if (rg_ntiles_ >= 0) return fail(std::string("chained forward: layer ") + name + " has no board kernel");
         if (const GldsChoice* gc = choose_glds(L)) {
@@ -1265,34 +1229,26 @@ private:
             gp.tab_src = tabs->src;
             gp.tab_pix = tabs->pix;
             ConvParams& p = gp.c;
-            p.in = in; p.w = L.w; p.bias = L.bias; p.res = res; p.out = out;
-            p.g = dgeom();
-            p.cin_s = L.cin_s; p.cout_s = L.cout_s; p.ko_pad = L.ko_pad;
-            p.taps = 9; p.act = act; p.npos = 0; p.num_pix_tiles = gc->ntiles;
+            conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+            p.npos = 0; p.num_pix_tiles = gc->ntiles;
             gp.zeros = d_zeros_;
-            const double px = geom_.total;
-            const double flops = 2.0 * px * L.cin * L.cout * 9;
-            const double bytes = sizeof(T) * (px * L.cin + px * L.cout * (res ? 2 : 1) + (double)L.cin * L.cout * 9);
+            const ConvCost cost = conv_cost(geom_.total, L.cin, L.cout, 9, res, sizeof(T));
             const auto fn = gc->e->fn;
             const size_t lds = gc->e->lds;
             const int grid = gc->ntiles * (L.ko_pad / (gc->e->wmt * 32));
-            return timed(name, flops, bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, gp); });
+            return timed(name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, gp); });
         }
         const int kot = L.wmt * 32, kot_tiles = L.ko_pad / kot;
         TileChoice tc;
         if (choose_tile(L.wmt, kot_tiles, &tc)) return -1;
         ConvParams p;
-        p.in = in; p.w = L.w; p.bias = L.bias; p.res = res; p.out = out;
-        p.g = dgeom();
-        p.cin_s = L.cin_s; p.cout_s = L.cout_s; p.ko_pad = L.ko_pad;
-        p.taps = L.k * L.k; p.act = act; p.npos = tc.npos; p.num_pix_tiles = tc.ntiles;
-        const double px = geom_.total;
-        const double flops = 2.0 * px * L.cin * L.cout * p.taps;
-        const double bytes = sizeof(T) * (px * L.cin + px * L.cout * (res ? 2 : 1) + (double)L.cin * L.cout * p.taps);
+        conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, L.k * L.k, act);
+        p.npos = tc.npos; p.num_pix_tiles = tc.ntiles;
+        const ConvCost cost = conv_cost(geom_.total, L.cin, L.cout, p.taps, res, sizeof(T));
         const auto fn = tc.e->fn;
         const size_t lds = tc.e->lds(tc.npos);
         const int grid = tc.ntiles * kot_tiles;
-        return timed(name, flops, bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, p); });
+        return timed(name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, p); });
     }
 
     int depthwise(const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
@@ -1418,8 +1374,7 @@ private:
             rg_ns_ = board_plan_.tile_first[rg_tile0_ + rg_ntiles_] - rg_n0_;
             stream_ = chain_stream_[g];
             hipError_t e = hipStreamWaitEvent(stream_, chain_fork_, 0);
-            static const bool serial = std::getenv("SAYURI_CHAINS_SERIAL") != nullptr;  // debugging aid: the chains one after another
-            if (serial && g > 0 && e == hipSuccess) e = hipStreamWaitEvent(stream_, chain_join_[g - 1], 0);
+            if (flags_.chains_serial && g > 0 && e == hipSuccess) e = hipStreamWaitEvent(stream_, chain_join_[g - 1], 0);
             if (e == hipSuccess) rc = forward_graph();
             if (e == hipSuccess && rc == 0) e = hipEventRecord(chain_join_[g], stream_);
             if (e != hipSuccess) rc = fail(std::string("chained forward: ") + hipGetErrorString(e));
@@ -1628,14 +1583,12 @@ private:
         std::memset(&t, 0, sizeof(t));
         t.sp = sp;
         t.has_se = has_se ? 1 : 0;
-        if (flags_.io_v2) {
-            // what the bodies never read (tile = workgroup id, the launch's grid is the batch): left out of the table, so that
-            // a batch of 250 positions finds the table of a batch of 256 in place and nothing is uploaded
-            ConvParams& c = t.sp.b.c;
-            c.num_pix_tiles = 0;
-            c.g.n_samples = 0;
-            c.g.total_pix = 0;
-        }
+        // what the bodies never read (tile = workgroup id, the launch's grid is the batch): left out of the table, so that
+        // a batch of 250 positions finds the table of a batch of 256 in place and nothing is uploaded
+        ConvParams& c = t.sp.b.c;
+        c.num_pix_tiles = 0;
+        c.g.n_samples = 0;
+        c.g.total_pix = 0;
         run_.push_back(t);
         run_flops_ += flops;
         run_bytes_ += bytes;
@@ -1687,13 +1640,12 @@ private:
         const TowerLayer* arg = ts.dev + first;
         const int grid = board_plan_.ntiles;
         hipError_t lrc = hipSuccess;
-        static const bool sync_dbg = std::getenv("SAYURI_TOWER_SYNC") != nullptr;  // debugging aid: nothing overlaps the tower launch
-        if (sync_dbg) HIP_OK(hipStreamSynchronize(stream_));
+        if (flags_.tower_sync) HIP_OK(hipStreamSynchronize(stream_));
         const int rc = timed("tower_run", run_flops_, run_bytes_, [&] {
             void* params[] = {(void*)&arg};
             lrc = hipModuleLaunchKernel(fn, grid, 1, 1, 512, 1, 1, 0, stream_, params, nullptr);
         });
-        if (sync_dbg && lrc == hipSuccess) HIP_OK(hipStreamSynchronize(stream_));
+        if (flags_.tower_sync && lrc == hipSuccess) HIP_OK(hipStreamSynchronize(stream_));
         if (lrc != hipSuccess) return fail(std::string("hipModuleLaunchKernel(conv_tower_kernel): ") + hipGetErrorString(lrc));
         return rc;
     }
@@ -1723,7 +1675,6 @@ private:
     long tower_launches_ = 0;
     int table_uploads_ = 0;
     // SAYURI_HIP_FWDSTAT: device time of the forwards sent through submit(), by batch-size class
-    bool fwdstat_ = std::getenv("SAYURI_HIP_FWDSTAT") != nullptr;
     hipEvent_t fs_ev_[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     double fs_d2h_ms_ = 0, fs_d2h_max_ = 0;
     long fs_d2h_slow_ = 0;

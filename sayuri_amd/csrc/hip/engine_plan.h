@@ -118,30 +118,24 @@ static void enable_big_lds_glds() {
 }
 // Switches of one engine, read from the environment ONCE, in sayuri_hip_create (and per call in the layer-level test
 // taps): nothing on the launch path calls getenv.  They select between product paths that give the same results (A/B
-// measurements, tests that check one path against the other).  The measuring-only switches (in-kernel timelines, forced
-// activation / channel tile) exist only in builds with -DSAYURI_EXPERIMENTS.
+// measurements, tests that check one path against the other), or turn on a debugging / measuring aid.  The measuring-only
+// switches (in-kernel timelines, forced activation / channel tile) exist only in builds with -DSAYURI_EXPERIMENTS.
 //   SAYURI_CONV=v0 | glds[:wnt]   3x3 layers on the generic / the LDS-DMA-tiles-across-samples kernel instead of one workgroup per board
 //   SAYURI_TOWER=0                one launch per convolution instead of one persistent launch per run of board convolutions
 //   SAYURI_SE_FUSED=0             SE unit as se_pool / se_fc / se_scale instead of inside the convolution
 //   SAYURI_HEADS_FUSED=0          conv1x1 x2 + head_tail instead of head_board_kernel
 //   SAYURI_NO_ARITH=1             board kernels read their index tables instead of computing the entries
-//   SAYURI_COMPUTE_STREAMS=2      the two tickets' forwards on two streams
+//   SAYURI_CHAINS_SERIAL=1        debugging aid: the chains of a chained forward one after another (forward())
+//   SAYURI_TOWER_SYNC=1           debugging aid: nothing overlaps a persistent tower launch (tower_flush())
+//   SAYURI_HIP_FWDSTAT=1          measuring aid: device time of every forward sent through submit(), printed when the engine goes
+// The other switches are described at their fields below.
 struct ConvOverride {
     bool v0 = false, no_board = false;
     int wnt = 0;
-    // The board kernel runs whenever the batch's boards fit its tiles, however empty the tiles are: which convolution kernel
-    // a sample meets must not depend on its batch mates (a lone 9x9 board fills a fifth of its tile; with the across-sample
-    // kernel it came out ~1e-4 away from the same position inside a larger batch).  SAYURI_BOARD_MIN_FILL=0.55 brings back the
-    // rule of rounds 2-4 (tiles less than 55 % full go to the across-sample kernel: half the latency of a lone small board).
-    double board_min_fill = 0.0;
 };
 struct EngineFlags {
     ConvOverride conv;
     bool tower = true, se_fused = true, heads_fused = true, arith = true;
-    bool se_by_geometry = true;        // which samples take the fused SE form depends on their board size alone (conv_se); SAYURI_SE_BY_GEOMETRY=0: on the tiles' occupancy
-    bool io_v2 = true;                 // SAYURI_IO_V2=0: geometry / small outputs by copies again (A/B; see submit())
-    bool io_zc = true, io_geom = true, io_prefix = true;  // its three parts, one at a time (SAYURI_IO_ZC / _GEOM / _PREFIX = 0)
-    bool io_zc_in = true;  // packed records read where the caller has them (SAYURI_IO_ZC_IN=0: copied first, rounds 2-4)
     bool tower_chain = true;           // a layer of the persistent run fetches the next layer's first weight group (SAYURI_TOWER_CHAIN=0: off)
     bool tower_gen_epi = true;         // Mish layers of the run take the generated epilogue (SAYURI_TOWER_GEN_EPI=0: the compiled one)
     bool se_split = true;              // SAYURI_SE_SPLIT=0: SE units of layers split over several channel tiles (384 channels) as
@@ -154,9 +148,10 @@ struct EngineFlags {
     int dbg_recycle_input = 0;         // SAYURI_DEBUG_RECYCLE_INPUT=1: hand the packed input's buffer back to the pool after the input
                                        // convolution, as rounds 3-4 did (the row-stride table below then REFUSES the forward); =2: and
                                        // switch the table off -- the race of rounds 3-4 is back (tests/test_gpu_fuzz.py shows that it sees it)
-    int compute_streams = 1;
     int chains = 0;                    // SAYURI_CHAINS: 0 = the engine decides, 1 = never, N = N chains whenever a batch qualifies (Engine::forward)
-    bool io_inorder = true;            // each ticket's upload, forward and download on the ticket's own stream (submit()); SAYURI_IO_INORDER=0: three streams and events
+    bool chains_serial = false;        // SAYURI_CHAINS_SERIAL
+    bool tower_sync = false;           // SAYURI_TOWER_SYNC
+    bool fwdstat = false;              // SAYURI_HIP_FWDSTAT
     int board_kot = 0;                 // experiments: only this channel tile
     int act_override = -1;             // experiments: activation of every board convolution
     int board_dbg = 0, heads_dbg = 0;  // experiments: in-kernel timelines
@@ -167,7 +162,6 @@ struct EngineFlags {
             if (!strncmp(e, "v0", 2)) { f.conv.v0 = true; f.conv.no_board = true; }
             else if (!strncmp(e, "glds", 4)) { f.conv.no_board = true; (void)sscanf(e, "glds:%d", &f.conv.wnt); }
         }
-        if (const char* e = getenv("SAYURI_BOARD_MIN_FILL")) f.conv.board_min_fill = atof(e);
         f.tower = !off("SAYURI_TOWER");
         f.tower_chain = !off("SAYURI_TOWER_CHAIN");
         f.tower_gen_epi = !off("SAYURI_TOWER_GEN_EPI");
@@ -177,18 +171,13 @@ struct EngineFlags {
         f.dbg_sx_stall = getenv("SAYURI_DEBUG_SX_STALL") != nullptr;
         if (const char* e = getenv("SAYURI_DEBUG_SX_EPOCH0")) f.dbg_sx_epoch0 = (unsigned)strtoul(e, nullptr, 0);
         if (const char* e = getenv("SAYURI_TOWER_NOEPI_AFTER")) f.tower_noepi_after = atoi(e);
-        f.io_v2 = !off("SAYURI_IO_V2");
-        f.io_zc = f.io_v2 && !off("SAYURI_IO_ZC");
-        f.io_zc_in = f.io_zc && !off("SAYURI_IO_ZC_IN");
-        f.io_geom = f.io_v2 && !off("SAYURI_IO_GEOM");
-        f.io_prefix = f.io_v2 && !off("SAYURI_IO_PREFIX");
         f.se_fused = !off("SAYURI_SE_FUSED");
-        f.se_by_geometry = !off("SAYURI_SE_BY_GEOMETRY");
         f.heads_fused = !off("SAYURI_HEADS_FUSED");
         f.arith = !getenv("SAYURI_NO_ARITH");
-        if (const char* e = getenv("SAYURI_COMPUTE_STREAMS")) f.compute_streams = atoi(e) == 2 ? 2 : 1;
         if (const char* e = getenv("SAYURI_CHAINS")) f.chains = std::max(0, std::min(atoi(e), 4));
-        if (const char* e = getenv("SAYURI_IO_INORDER")) f.io_inorder = atoi(e) != 0;
+        f.chains_serial = getenv("SAYURI_CHAINS_SERIAL") != nullptr;
+        f.tower_sync = getenv("SAYURI_TOWER_SYNC") != nullptr;
+        f.fwdstat = getenv("SAYURI_HIP_FWDSTAT") != nullptr;
 #ifdef SAYURI_EXPERIMENTS
         if (const char* e = getenv("SAYURI_BOARD_KOT")) f.board_kot = atoi(e);
         if (const char* e = getenv("SAYURI_ACT_OVERRIDE")) f.act_override = atoi(e);
@@ -286,7 +275,6 @@ struct BoardPlan {
     int ntiles = 0, npos = 0;
     bool ok = false, single = false;  // single: one sample per tile
     int uniform_info = -1;            // every tile has this (column tiles | board size << 8), or -1
-    double fill = 0;
     std::vector<int> tile_first;      // first sample of every tile, then the number of samples (ntiles + 1 entries)
 };
 static BoardPlan board_plan(const HostGeom& geom, const ConvOverride& ov) {
@@ -316,7 +304,6 @@ static BoardPlan board_plan(const HostGeom& geom, const ConvOverride& ov) {
     bp.tile_first.push_back(geom.n);
     bp.uniform_info = info0;
     bp.npos = round_up(max_pos, 64);
-    bp.fill = (double)geom.total / ((double)bp.ntiles * kBoardPT);
     bp.single = bp.ntiles == geom.n;
     bp.ok = true;
     return bp;
@@ -334,6 +321,33 @@ static const BoardEntry* pick_board(const BoardPlan& bp, int ko_pad, int* kot_ti
         if (!best || cost < best_cost) { best = &e; best_cost = cost; *kot_tiles = (int)kts; }
     }
     return best;
+}
+
+// ------------------------------------------------------------------ the parameters of one 3x3 / 1x1 convolution launch
+// Shared by Engine<T> and the layer-level test taps.  conv_params fills every field but npos and num_pix_tiles (the kernel
+// family decides them) member by member, so a struct the caller zeroed keeps zero padding.
+static void conv_params(ConvParams& p, const void* in, const void* w, const float* bias, const void* res, void* out, const BatchGeom& g,
+                        int cin_s, int cout_s, int ko_pad, int taps, int act) {
+    p.in = in; p.w = w; p.bias = bias; p.res = res; p.out = out;
+    p.g = g;
+    p.cin_s = cin_s; p.cout_s = cout_s; p.ko_pad = ko_pad;
+    p.taps = taps; p.act = act;
+}
+// The board kernels' part of a launch over the tiles of `plan` (conv_params fills bp.c afterwards).  Zeroed first: the tower
+// table is compared bytewise with its cached copy (Engine::tower_flush).  The kernels compute their table entries (arith) when
+// every tile is one sample of one size and the caller allows it (SAYURI_NO_ARITH).
+static void board_params(BoardParams& bp, const BoardPlan& plan, const int* tab_src, const int2* tab_pix, const int* tab_cols, bool arith) {
+    std::memset(&bp, 0, sizeof(bp));
+    bp.tab_src = tab_src; bp.tab_pix = tab_pix; bp.tab_cols = tab_cols;
+    bp.npos = plan.npos;
+    bp.uniform_info = plan.uniform_info;
+    bp.arith = plan.single && plan.uniform_info >= 0 && arith ? 1 : 0;
+}
+// What a convolution over `px` pixels computes and moves (the flops / bytes of the profile rows and of bench.py's
+// tower_conv_mfma_frac): the activations in, out (and the residual), the weights once.
+struct ConvCost { double flops, bytes; };
+static ConvCost conv_cost(double px, int cin, int cout, int taps, bool res, size_t elem_bytes) {
+    return ConvCost{2.0 * px * cin * cout * taps, elem_bytes * (px * cin + px * cout * (res ? 2 : 1) + (double)cin * cout * taps)};
 }
 
 struct Stat {

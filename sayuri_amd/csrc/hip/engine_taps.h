@@ -110,10 +110,9 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
         bool board_done = false;
         if (sizeof(T) == 2 && k == 3) {
             enable_big_lds_glds();
-            const ConvOverride cov = EngineFlags::from_env().conv;
-            const BoardPlan plan = board_plan(hg, cov);
+            const BoardPlan plan = board_plan(hg, EngineFlags::from_env().conv);
             int kot_tiles = 0;
-            const BoardEntry* be = plan.fill >= cov.board_min_fill ? pick_board(plan, ko_pad, &kot_tiles) : nullptr;
+            const BoardEntry* be = pick_board(plan, ko_pad, &kot_tiles);
             if (be) {
                 int* tsrc = (int*)dalloc(sizeof(int) * (size_t)plan.ntiles * plan.npos);
                 int2* tpix = (int2*)dalloc(sizeof(int2) * (size_t)plan.ntiles * kBoardPT);
@@ -121,14 +120,10 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
                 if (!tsrc || !tpix || !tcols) { cleanup(); return fail("test_conv: hipMalloc failed"); }
                 hipLaunchKernelGGL(board_setup_kernel, dim3(plan.ntiles), dim3(256), 0, 0, g, plan.npos, tsrc, tpix, tcols);
                 BoardParams bp;
-                std::memset(&bp, 0, sizeof(bp));
-                bp.tab_src = tsrc; bp.tab_pix = tpix; bp.tab_cols = tcols; bp.npos = plan.npos; bp.dbg = nullptr;
-                bp.uniform_info = plan.uniform_info;
-                bp.arith = (plan.single && plan.uniform_info >= 0) ? 1 : 0;
+                board_params(bp, plan, tsrc, tpix, tcols, true);
                 ConvParams& p = bp.c;
-                p.in = dx; p.w = dw; p.bias = db; p.res = dres; p.out = dy; p.g = g;
-                p.cin_s = cin_s; p.cout_s = cout_s; p.ko_pad = ko_pad; p.taps = 9; p.act = act; p.npos = 0;
-                p.num_pix_tiles = plan.ntiles;
+                conv_params(p, dx, dw, db, dres, dy, g, cin_s, cout_s, ko_pad, 9, act);
+                p.npos = 0; p.num_pix_tiles = plan.ntiles;
                 hipLaunchKernelGGL(be->fn, dim3(plan.ntiles * kot_tiles), dim3(512), be->lds(plan.npos), 0, bp);
                 HIP_OK(hipGetLastError());
                 HIP_OK(hipDeviceSynchronize());
@@ -150,9 +145,8 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
             gp.tab_src = tsrc;
             gp.tab_pix = tpix;
             ConvParams& p = gp.c;
-            p.in = dx; p.w = dw; p.bias = db; p.res = dres; p.out = dy; p.g = g;
-            p.cin_s = cin_s; p.cout_s = cout_s; p.ko_pad = ko_pad; p.taps = 9; p.act = act; p.npos = 0;
-            p.num_pix_tiles = g_ntiles;
+            conv_params(p, dx, dw, db, dres, dy, g, cin_s, cout_s, ko_pad, 9, act);
+            p.npos = 0; p.num_pix_tiles = g_ntiles;
             gp.zeros = dz;
             hipLaunchKernelGGL(ge->fn, dim3(g_ntiles * (ko_pad / (ge->wmt * 32))), dim3(512), ge->lds, 0, gp);
             g_test_conv_kind = 1;
@@ -173,8 +167,7 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
         if (best) {
         g_test_conv_kind = 0;
         ConvParams p;
-        p.in = dx; p.w = dw; p.bias = db; p.res = dres; p.out = dy; p.g = g;
-        p.cin_s = cin_s; p.cout_s = cout_s; p.ko_pad = ko_pad; p.taps = taps; p.act = act;
+        conv_params(p, dx, dw, db, dres, dy, g, cin_s, cout_s, ko_pad, taps, act);
         p.npos = best_npos;
         const int PT = 64 * best->wnt;
         p.num_pix_tiles = (hg.total + PT - 1) / PT;
@@ -430,13 +423,11 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     BoardSeParams sp;
     std::memset(&sp, 0, sizeof(sp));
     BoardParams& bp = sp.b;
-    bp.tab_src = tsrc; bp.tab_pix = tpix; bp.tab_cols = tcols; bp.npos = plan.npos;
-    bp.uniform_info = plan.uniform_info;
-    bp.arith = (plan.single && plan.uniform_info >= 0) ? 1 : 0;
+    board_params(bp, plan, tsrc, tpix, tcols, true);
     bp.row_order = row_order ? 1 : 0;
     ConvParams& p = bp.c;
-    p.in = dx; p.w = dw; p.bias = db; p.res = dres; p.out = dy; p.g = tg.g;
-    p.cin_s = cs; p.cout_s = cs; p.ko_pad = ko_pad; p.taps = 9; p.act = act; p.num_pix_tiles = plan.ntiles;
+    conv_params(p, dx, dw, db, dres, dy, tg.g, cs, cs, ko_pad, 9, act);
+    p.num_pix_tiles = plan.ntiles;
     sp.squeeze = FcDev{dw1, db1, 3 * C, se};
     sp.excite = FcDev{dw2, db2, se, 2 * C};
     sp.C = C;
