@@ -42,10 +42,9 @@ public:
 
     int init() {
         HIP_OK(hipSetDevice(device_));
-        HIP_OK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
         // The tickets' compute streams: one shared stream to begin with; the rule below gives ticket 1 a stream of its own.
-        compute_[0] = stream_;
-        compute_[1] = stream_;
+        HIP_OK(hipStreamCreateWithFlags(&compute_[0], hipStreamNonBlocking));
+        compute_[1] = compute_[0];
         HIP_OK(hipStreamCreateWithFlags(&h2d_stream_, hipStreamNonBlocking));
         HIP_OK(hipStreamCreateWithFlags(&d2h_stream_, hipStreamNonBlocking));
         for (int t = 0; t < 2; ++t) {
@@ -97,11 +96,7 @@ public:
     static constexpr int kMaxChains = 4;
     hipStream_t chain_stream_[kMaxChains] = {};
     hipEvent_t chain_fork_ = nullptr, chain_join_[kMaxChains] = {};
-    int rg_tile0_ = 0, rg_ntiles_ = -1, rg_n0_ = 0, rg_ns_ = -1;  // the tiles / samples the launches of forward_graph() cover (-1: all)
     int last_chains_ = 1;
-    int range_ntiles() const { return rg_ntiles_ >= 0 ? rg_ntiles_ : board_plan_.ntiles; }
-    int range_ns() const { return rg_ns_ >= 0 ? rg_ns_ : geom_.n; }
-    double range_px() const { return rg_ns_ >= 0 ? (double)(geom_.off[rg_n0_ + rg_ns_] - geom_.off[rg_n0_]) : (double)geom_.total; }
     int chain_setup(int G) {
         if (!chain_fork_) HIP_OK(hipEventCreateWithFlags(&chain_fork_, hipEventDisableTiming));
         for (int g = 0; g < G; ++g) {
@@ -175,7 +170,8 @@ public:
         next_ticket_ ^= 1;
         HIP_OK(hipSetDevice(device_));
         if (finalize()) return -1;
-        select_slot(t);
+        IoSlot& io = io_[t];
+        const hipStream_t cs = compute_[t];
         // With the tower code object loaded (init()): everything of a ticket on the ticket's own stream, in
         // order -- no event between streams at all.  Each record / wait is a marker the runtime's signal thread handles; the
         // seven per batch of the three-stream arrangement kept that thread at a full host core during self-play (one of
@@ -188,20 +184,20 @@ public:
         // upload stream and one event; the slot is free for them when the ticket's last completion event has fired, which the
         // caller has normally seen already.
         const bool big_upload = inorder && packed == nullptr;
-        hipStream_t up = inorder && !big_upload ? stream_ : h2d_stream_, down = inorder ? stream_ : d2h_stream_;
+        hipStream_t up = inorder && !big_upload ? cs : h2d_stream_, down = inorder ? cs : d2h_stream_;
         if (!inorder) HIP_OK(hipStreamWaitEvent(h2d_stream_, fwd_done_[t], 0));  // the forward that last read this slot's inputs
         else if (big_upload && tick_ev_[t]) HIP_OK(hipStreamWaitEvent(h2d_stream_, tick_ev_[t], 0));
-        if (enqueue_inputs(n, planes, board_sizes, up, packed, binary, /*in_place=*/true)) return -1;
+        if (enqueue_inputs(t, n, planes, board_sizes, up, packed, binary, /*in_place=*/true)) return -1;
         if (!inorder || big_upload) {
             HIP_OK(hipEventRecord(h2d_done_[t], h2d_stream_));
-            HIP_OK(hipStreamWaitEvent(stream_, h2d_done_[t], 0));
-            if (!inorder && tick_ev_[t]) HIP_OK(hipStreamWaitEvent(stream_, tick_ev_[t], 0));  // the download that last read this slot's outputs
+            HIP_OK(hipStreamWaitEvent(cs, h2d_done_[t], 0));
+            if (!inorder && tick_ev_[t]) HIP_OK(hipStreamWaitEvent(cs, tick_ev_[t], 0));  // the download that last read this slot's outputs
         }
         have_batch_ = true;
         if (flags_.fwdstat) {  // SAYURI_HIP_FWDSTAT (measuring aid): device time of every submitted forward
             for (int k = 0; k < 2; ++k)
                 if (!fs_ev_[t][k]) HIP_OK(hipEventCreate(&fs_ev_[t][k]));
-            HIP_OK(hipEventRecord(fs_ev_[t][0], stream_));
+            HIP_OK(hipEventRecord(fs_ev_[t][0], cs));
         }
         const int uploads_before = table_uploads_;
         // The persistent tower launch holds every CU (all registers, all LDS) for the whole forward.  A copy the runtime
@@ -212,30 +208,28 @@ public:
         // So nothing small is copied any more: the heads kernel stores pass / misc straight into the caller's pinned
         // buffers (20 KB of posted PCIe writes), a uniform batch uses geometry arrays that are resident (enqueue_inputs),
         // and the tower table does not depend on the batch size (tower_append).  The two large outputs keep their DMA copies.
-        zc_pass_ = zc_device_pointer(pass);
-        zc_misc_ = zc_pass_ ? zc_device_pointer(misc) : nullptr;
-        if (!zc_misc_) zc_pass_ = nullptr;  // both or neither: the heads kernel takes one path
-        const int frc = forward();
-        const bool small_direct = zc_pass_ != nullptr;
-        zc_pass_ = zc_misc_ = nullptr;
-        if (frc) return -1;
+        float* zc_pass = zc_device_pointer(pass);
+        float* zc_misc = zc_pass ? zc_device_pointer(misc) : nullptr;
+        if (!zc_misc) zc_pass = nullptr;  // both or neither: the heads kernel takes one path
+        const bool small_direct = zc_pass != nullptr;
+        if (forward(t, zc_pass, zc_misc)) return -1;
         if (flags_.fwdstat) {
-            HIP_OK(hipEventRecord(fs_ev_[t][1], stream_));
+            HIP_OK(hipEventRecord(fs_ev_[t][1], cs));
             fs_pending_[t] = true;
             fs_n_[t] = n;
             fs_uploads_ += table_uploads_ - uploads_before;
         }
         if (!inorder) {
-            HIP_OK(hipEventRecord(fwd_done_[t], stream_));
+            HIP_OK(hipEventRecord(fwd_done_[t], cs));
             HIP_OK(hipStreamWaitEvent(d2h_stream_, fwd_done_[t], 0));
         }
         const size_t B2 = (size_t)board_ * board_;
-        HIP_OK(hipMemcpyAsync(prob, d_prob_, sizeof(float) * n * desc_.probabilities_channels * B2, hipMemcpyDeviceToHost, down));
+        HIP_OK(hipMemcpyAsync(prob, io.prob, sizeof(float) * n * desc_.probabilities_channels * B2, hipMemcpyDeviceToHost, down));
         if (!small_direct) {
-            HIP_OK(hipMemcpyAsync(pass, d_pass_, sizeof(float) * n * desc_.pass_probability_outputs, hipMemcpyDeviceToHost, down));
-            HIP_OK(hipMemcpyAsync(misc, d_misc_, sizeof(float) * n * desc_.value_misc_outputs, hipMemcpyDeviceToHost, down));
+            HIP_OK(hipMemcpyAsync(pass, io.pass, sizeof(float) * n * desc_.pass_probability_outputs, hipMemcpyDeviceToHost, down));
+            HIP_OK(hipMemcpyAsync(misc, io.misc, sizeof(float) * n * desc_.value_misc_outputs, hipMemcpyDeviceToHost, down));
         }
-        HIP_OK(hipMemcpyAsync(own, d_own_, sizeof(float) * n * B2, hipMemcpyDeviceToHost, down));
+        HIP_OK(hipMemcpyAsync(own, io.own, sizeof(float) * n * B2, hipMemcpyDeviceToHost, down));
         if (!tick_ev_[t]) HIP_OK(hipEventCreateWithFlags(&tick_ev_[t], hipEventDisableTiming));
         HIP_OK(hipEventRecord(tick_ev_[t], down));
         if (flags_.fwdstat) {
@@ -249,7 +243,7 @@ public:
         if (ticket < 0 || ticket > 1 || !tick_ev_[ticket]) return fail("wait: bad ticket");
         HIP_OK(hipSetDevice(device_));
         HIP_OK(hipEventSynchronize(tick_ev_[ticket]));
-        if (sx_check()) return -1;
+        if (sx_check(ticket)) return -1;
         if (flags_.fwdstat && fs_pending_[ticket]) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, fs_ev_[ticket][0], fs_ev_[ticket][1]) == hipSuccess) {
@@ -281,9 +275,8 @@ public:
         HIP_OK(hipStreamSynchronize(d2h_stream_));
         for (hipStream_t cs : compute_)
             if (cs) HIP_OK(hipStreamSynchronize(cs));
-        select_slot(0);
-        if (enqueue_inputs(n, planes, board_sizes, stream_, packed, binary)) return -1;
-        HIP_OK(hipStreamSynchronize(stream_));
+        if (enqueue_inputs(0, n, planes, board_sizes, compute_[0], packed, binary)) return -1;
+        HIP_OK(hipStreamSynchronize(compute_[0]));
         have_batch_ = true;
         return 0;
     }
@@ -328,9 +321,10 @@ public:
     }
     std::map<int, IdentGeom> ident_;
 
-    // geometry + planes to the device (no sync): the planes or packed records H2D on `copy_stream`, the geometry arrays of a
-    // mixed batch from a 2-deep pinned ring (a second batch can be enqueued while the first is still in flight) on stream_.
-    int enqueue_inputs(int n, const float* planes, const int* board_sizes, hipStream_t copy_stream, const unsigned* packed = nullptr,
+    // geometry + planes of ticket t to the device (no sync): the planes or packed records H2D on `copy_stream`, the geometry
+    // arrays of a mixed batch from a 2-deep pinned ring (a second batch can be enqueued while the first is still in flight) on
+    // the ticket's compute stream.
+    int enqueue_inputs(int t, int n, const float* planes, const int* board_sizes, hipStream_t copy_stream, const unsigned* packed = nullptr,
                        int binary = 0, bool in_place = false) {
         HIP_OK(hipSetDevice(device_));
         if (n <= 0 || n > max_batch_) return fail("batch size out of range");
@@ -365,24 +359,24 @@ public:
             glds_cache_.clear();
             board_plan_valid_ = false;
         }
-        IoSlot& slot = io_[cur_slot_];
+        IoSlot& io = io_[t];
         const bool uniform = !mixed;
         // One sample per tile and one board size: the tables of a LONGER batch of the same size serve a shorter one (tile i
         // depends on sample i alone), so a queue that alternates between 256 and 250 positions keeps its tables.
         const bool one_per_tile = uniform && 2 * geom_.bsz[0] * geom_.bsz[0] > kBoardPT;
-        const bool prefix = one_per_tile && slot.tabs_single && slot.tabs_bsz.size() >= (size_t)n &&
-                            slot.tabs_bsz[0] == geom_.bsz[0];
-        if (!prefix && slot.tabs_bsz != geom_.bsz) {  // this slot's tables were built for another geometry
-            for (auto& kv : slot.tabs) kv.second.fresh = false;
-            slot.board.fresh = false;
-            slot.tabs_bsz = geom_.bsz;
-            slot.tabs_single = one_per_tile;
+        const bool prefix = one_per_tile && io.tabs_single && io.tabs_bsz.size() >= (size_t)n &&
+                            io.tabs_bsz[0] == geom_.bsz[0];
+        if (!prefix && io.tabs_bsz != geom_.bsz) {  // this slot's tables were built for another geometry
+            for (auto& kv : io.tabs) kv.second.fresh = false;
+            io.board.fresh = false;
+            io.tabs_bsz = geom_.bsz;
+            io.tabs_single = one_per_tile;
         }
         // the tables of the across-sample tiles (conv_glds.h) know the pixel total: they serve exactly the batch size they were
         // built for (the board tables above serve every prefix)
-        if (slot.tabs_n != n) {
-            for (auto& kv : slot.tabs) kv.second.fresh = false;
-            slot.tabs_n = n;
+        if (io.tabs_n != n) {
+            for (auto& kv : io.tabs) kv.second.fresh = false;
+            io.tabs_n = n;
         }
         // Geometry arrays on the device.  A uniform batch (the self-play queue: every position on the NN board) uses arrays
         // that are resident -- off[i] = i * bs^2, bsz[i] = bs, perm[i] = i hold for every n -- so nothing is copied.  A mixed
@@ -392,18 +386,17 @@ public:
         if (uniform) {
             const IdentGeom* id = ident_geom(geom_.bsz[0]);
             if (!id) return -1;
-            d_off_ = id->off; d_bsz_ = id->bsz; d_perm_ = id->perm;
+            io.g_off = id->off; io.g_bsz = id->bsz; io.g_perm = id->perm;
         } else {
-            d_off_ = slot.off; d_bsz_ = slot.bsz; d_perm_ = slot.perm;
+            io.g_off = io.off; io.g_bsz = io.bsz; io.g_perm = io.perm;
             int* hg = h_geom_ + (size_t)geom_slot_ * (3 * max_batch_ + 1);
             geom_slot_ ^= 1;
             std::memcpy(hg, geom_.off.data(), sizeof(int) * (n + 1));
             std::memcpy(hg + max_batch_ + 1, geom_.bsz.data(), sizeof(int) * n);
             std::memcpy(hg + 2 * max_batch_ + 1, perm_.data(), sizeof(int) * n);
-            hipLaunchKernelGGL(geom_stage_kernel, dim3(1), dim3(256), 0, stream_, (const int*)hg, max_batch_, n, d_off_, d_bsz_, d_perm_);
+            hipLaunchKernelGGL(geom_stage_kernel, dim3(1), dim3(256), 0, compute_[t], (const int*)hg, max_batch_, n, io.off, io.bsz, io.perm);
             HIP_OK(hipGetLastError());
         }
-        IoSlot& io = io_[cur_slot_];
         io.packed_binary = packed ? binary : 0;
         if (packed) {
             const size_t words = (size_t)binary * 12 + 8;
@@ -421,7 +414,7 @@ public:
             HIP_OK(hipMemcpyAsync(io.packed, packed, sizeof(unsigned) * n * words, hipMemcpyHostToDevice, copy_stream));
             return 0;
         }
-        HIP_OK(hipMemcpyAsync(d_planes_, planes, sizeof(float) * (size_t)n * desc_.input_channels * board_ * board_,
+        HIP_OK(hipMemcpyAsync(io.planes, planes, sizeof(float) * (size_t)n * desc_.input_channels * board_ * board_,
                               hipMemcpyHostToDevice, copy_stream));
         return 0;
     }
@@ -429,24 +422,27 @@ public:
     int run() override {
         if (!have_batch_) return fail("run before upload");
         HIP_OK(hipSetDevice(device_));
-        return forward();
+        return forward(0);
     }
 
+    // run() / sync() / download(), time_runs() and profile_run() work on ticket 0, the slot upload() fills
     int sync() override {
         HIP_OK(hipSetDevice(device_));
-        HIP_OK(hipStreamSynchronize(stream_));
-        return sx_check();
+        HIP_OK(hipStreamSynchronize(compute_[0]));
+        return sx_check(0);
     }
 
     int download(float* prob, float* pass, float* misc, float* own) override {
         HIP_OK(hipSetDevice(device_));
         const size_t n = geom_.n, B2 = (size_t)board_ * board_;
-        if (prob) HIP_OK(hipMemcpyAsync(prob, d_prob_, sizeof(float) * n * desc_.probabilities_channels * B2, hipMemcpyDeviceToHost, stream_));
-        if (pass) HIP_OK(hipMemcpyAsync(pass, d_pass_, sizeof(float) * n * desc_.pass_probability_outputs, hipMemcpyDeviceToHost, stream_));
-        if (misc) HIP_OK(hipMemcpyAsync(misc, d_misc_, sizeof(float) * n * desc_.value_misc_outputs, hipMemcpyDeviceToHost, stream_));
-        if (own) HIP_OK(hipMemcpyAsync(own, d_own_, sizeof(float) * n * B2, hipMemcpyDeviceToHost, stream_));
-        HIP_OK(hipStreamSynchronize(stream_));
-        return sx_check();
+        const IoSlot& io = io_[0];
+        const hipStream_t s = compute_[0];
+        if (prob) HIP_OK(hipMemcpyAsync(prob, io.prob, sizeof(float) * n * desc_.probabilities_channels * B2, hipMemcpyDeviceToHost, s));
+        if (pass) HIP_OK(hipMemcpyAsync(pass, io.pass, sizeof(float) * n * desc_.pass_probability_outputs, hipMemcpyDeviceToHost, s));
+        if (misc) HIP_OK(hipMemcpyAsync(misc, io.misc, sizeof(float) * n * desc_.value_misc_outputs, hipMemcpyDeviceToHost, s));
+        if (own) HIP_OK(hipMemcpyAsync(own, io.own, sizeof(float) * n * B2, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        return sx_check(0);
     }
 
     int time_runs(int iters, float* ms) override {
@@ -456,11 +452,11 @@ public:
         group_counts_.clear();
         group_open_ = false;
         light_ = !light_name_.empty();
-        HIP_OK(hipEventRecord(ev0_, stream_));
+        HIP_OK(hipEventRecord(ev0_, compute_[0]));
         for (int i = 0; i < iters; ++i)
-            if (forward()) { light_ = false; return -1; }
-        if (group_open_ && close_group()) { light_ = false; return -1; }
-        HIP_OK(hipEventRecord(ev1_, stream_));
+            if (forward(0)) { light_ = false; return -1; }
+        if (group_open_ && close_group(compute_[0])) { light_ = false; return -1; }
+        HIP_OK(hipEventRecord(ev1_, compute_[0]));
         light_ = false;
         HIP_OK(hipEventSynchronize(ev1_));
         HIP_OK(hipEventElapsedTime(ms, ev0_, ev1_));
@@ -506,7 +502,7 @@ public:
         HIP_OK(hipSetDevice(device_));
         stats_.clear();
         profiling_ = true;
-        const int rc = forward();
+        const int rc = forward(0);
         profiling_ = false;
         if (rc) return -1;
         if (d_hdbg_) {
@@ -787,14 +783,13 @@ private:
             // conv_board_sx.h: the granules the sibling channel tiles of a board tile exchange, [tile][kt][sample][slot]
             if (sx_kts_ && dev_alloc(&io.sx_xchg, (size_t)max_batch_ * sx_kts_ * kSxMaxSub * kSxSlots)) return -1;
             io.sx_epoch = flags_.dbg_sx_epoch0;
-        }
-        if (sx_kts_) {
-            HIP_OK(hipHostMalloc((void**)&sx_err_host_, 64, hipHostMallocMapped));
-            std::memset(sx_err_host_, 0, 64);
-            HIP_OK(hipHostGetDevicePointer((void**)&sx_err_dev_, sx_err_host_, 0));
+            if (sx_kts_) {
+                HIP_OK(hipHostMalloc((void**)&io.sx_err_host, 64, hipHostMallocMapped));
+                std::memset(io.sx_err_host, 0, 64);
+                HIP_OK(hipHostGetDevicePointer((void**)&io.sx_err_dev, io.sx_err_host, 0));
+            }
         }
         finalized_ = true;
-        select_slot(0);
         return 0;
     }
 
@@ -847,9 +842,11 @@ private:
         ident_.clear();
         if (h_geom_) (void)hipHostFree(h_geom_);
         h_geom_ = nullptr;
-        if (sx_err_host_) (void)hipHostFree(sx_err_host_);
-        sx_err_host_ = nullptr;
-        sx_err_dev_ = nullptr;
+        for (IoSlot& io : io_) {
+            if (io.sx_err_host) (void)hipHostFree(io.sx_err_host);
+            io.sx_err_host = nullptr;
+            io.sx_err_dev = nullptr;
+        }
         for (TowerSlot& ts : tower_)
             for (int i = 0; i < 2; ++i) {
                 if (ts.stage[i]) (void)hipHostFree(ts.stage[i]);
@@ -878,32 +875,72 @@ private:
         if (ev1_) (void)hipEventDestroy(ev1_);
         for (hipEvent_t& e : h2d_done_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
         for (hipEvent_t& e : fwd_done_) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-        stream_ = compute_[0];
         if (compute_[1] && compute_[1] != compute_[0]) (void)hipStreamDestroy(compute_[1]);
-        compute_[1] = nullptr;
-        if (stream_) (void)hipStreamDestroy(stream_);
+        if (compute_[0]) (void)hipStreamDestroy(compute_[0]);
         if (h2d_stream_) (void)hipStreamDestroy(h2d_stream_);
         if (d2h_stream_) (void)hipStreamDestroy(d2h_stream_);
         ev0_ = ev1_ = nullptr;
-        stream_ = h2d_stream_ = d2h_stream_ = nullptr;
+        compute_[0] = compute_[1] = h2d_stream_ = d2h_stream_ = nullptr;
     }
 
-    // -------------------------------------------------------------- launch plumbing
-    BatchGeom dgeom() const { return BatchGeom{d_off_, d_bsz_, geom_.n, geom_.total, slot_pix_}; }
+    // -------------------------------------------------------------- what one forward works on
+    static constexpr int kNumBufs = 6;  // small pool of activation buffers
+    // device-side batch i/o, one set per ticket
+    struct IoSlot {
+        float *planes = nullptr, *prob = nullptr, *pass = nullptr, *misc = nullptr, *own = nullptr;
+        unsigned* packed = nullptr;  // packed records of the batch (allocated on first use)
+        const unsigned* packed_src = nullptr;  // non-null: the batch's records are read where the caller has them (pinned host memory)
+        int packed_binary = 0;       // > 0: the slot's current batch came as packed records with this many bit planes
+        int *off = nullptr, *bsz = nullptr, *perm = nullptr;  // a mixed batch's geometry arrays (enqueue_inputs)
+        const int *g_off = nullptr, *g_bsz = nullptr, *g_perm = nullptr;  // the current batch's: off / bsz / perm, or resident ones
+        T* bufs[kNumBufs] = {};
+        float *gate = nullptr, *separt = nullptr;
+        unsigned long long* sx_xchg = nullptr;
+        unsigned sx_epoch = 0;  // the last tag used in sx_xchg
+        unsigned *sx_err_host = nullptr, *sx_err_dev = nullptr;  // set by a split SE workgroup whose wait for its siblings ran out
+        std::map<int, TileTabs> tabs;   // index tables of the geometry this slot last ran (keyed by tile variant)
+        BoardTabs board;
+        std::vector<int> tabs_bsz;
+        bool tabs_single = false;  // tabs_bsz is one board size with one sample per tile
+        int tabs_n = -1;           // batch size the across-sample tables (tabs) were last built for
+    };
+    // One forward of a ticket's batch, or one chain of it (forward()).  Every launch helper is handed the Fwd it works for:
+    // the slot, the stream, the tiles and samples it covers and where the heads write are never read from engine members.
+    struct Fwd {
+        int t;                       // the ticket: i/o slot io_[t], tower table tower_[t]
+        IoSlot& io;
+        hipStream_t stream;
+        bool chained = false;        // one of several chains: not ordered against the other chains' launches
+        int tile0 = 0, ntiles = 0;   // the board tiles [tile0, tile0 + ntiles) ...
+        int n0 = 0, ns = 0;          // ... = the samples [n0, n0 + ns)
+        double px = 0;               // their pixels
+        float *pass = nullptr, *misc = nullptr;  // where the heads put pass / misc: the slot's buffers or the caller's (submit())
+        unsigned sx_epoch0 = 0;      // tags of the split SE launches: sx_epoch0 + 1 + index of the SE layer
+        // what lives from one layer to the next
+        bool busy[kNumBufs] = {};
+        int sx_idx = 0, dbg_call = 0, dbg_se_call = 0;
+        std::vector<TowerLayer> run;  // board convolutions waiting for the persistent launch (tower_append)
+        int run_kot = 0, table_used = 0;
+        double run_flops = 0, run_bytes = 0;
+        int take() { for (int i = 0; i < kNumBufs; ++i) if (!busy[i]) { busy[i] = true; return i; } return -1; }
+        void give(int i) { busy[i] = false; }
+    };
+    BatchGeom dgeom(const IoSlot& io) const { return BatchGeom{io.g_off, io.g_bsz, geom_.n, geom_.total, slot_pix_}; }
 
-    int close_group() {
-        HIP_OK(hipEventRecord(pool_[pool_used_ + 1], stream_));
+    // -------------------------------------------------------------- launch plumbing
+    int close_group(hipStream_t s) {
+        HIP_OK(hipEventRecord(pool_[pool_used_ + 1], s));
         pool_used_ += 2;
         group_open_ = false;
         return 0;
     }
-    template <typename F> int timed(const char* name, double flops, double bytes, F&& launch) {
-        if (!run_.empty() && tower_flush()) return -1;  // the pending run of board convolutions goes first (stream order)
+    template <typename F> int timed(Fwd& f, const char* name, double flops, double bytes, F&& launch) {
+        if (!f.run.empty() && tower_flush(f)) return -1;  // the pending run of board convolutions goes first (stream order)
         if (!profiling_) {
             // light mode: un-synchronised event pairs around runs of the dominant kernel class only
             const bool match = light_ && light_name_ == name;
             if (group_open_ && (!match || group_counts_.back() >= light_group_)) {
-                if (close_group()) return -1;
+                if (close_group(f.stream)) return -1;
             }
             if (match && !group_open_) {
                 if (pool_used_ + 2 > pool_.size()) {
@@ -913,13 +950,13 @@ private:
                         pool_.push_back(e);
                     }
                 }
-                HIP_OK(hipEventRecord(pool_[pool_used_], stream_));
+                HIP_OK(hipEventRecord(pool_[pool_used_], f.stream));
                 group_counts_.push_back(0);
                 group_open_ = true;
             }
             launch();
             HIP_OK(hipGetLastError());
-            if (rg_ntiles_ < 0) rows_reset();  // a launch on the forward's one stream: ordered against everything behind it
+            if (!f.chained) rows_reset();  // a launch on the forward's one stream: ordered against everything behind it
             if (match) {
                 group_counts_.back() += 1;
                 light_flops_ = flops;
@@ -927,11 +964,11 @@ private:
             }
             return 0;
         }
-        HIP_OK(hipEventRecord(ev0_, stream_));
+        HIP_OK(hipEventRecord(ev0_, f.stream));
         launch();
         HIP_OK(hipGetLastError());
         rows_reset();
-        HIP_OK(hipEventRecord(ev1_, stream_));
+        HIP_OK(hipEventRecord(ev1_, f.stream));
         HIP_OK(hipEventSynchronize(ev1_));
         float ms = 0.f;
         HIP_OK(hipEventElapsedTime(&ms, ev0_, ev1_));
@@ -970,15 +1007,15 @@ private:
 
     struct GldsChoice { const GldsEntry* e; int ntiles; };
     // index tables of the current batch geometry for pixel-tile size 64*wnt (built on first use)
-    int tile_tabs(const GldsEntry& e, const TileTabs** out) {
-        TileTabs& t = io_[cur_slot_].tabs[e.wnt];
+    int tile_tabs(Fwd& f, const GldsEntry& e, const TileTabs** out) {
+        TileTabs& t = f.io.tabs[e.wnt];
         if (!t.src) {
             const size_t max_tiles = ((size_t)max_batch_ * slot_pix_ + e.pt - 1) / e.pt;
             if (dev_alloc(&t.src, max_tiles * e.npos) || dev_alloc(&t.pix, max_tiles * e.pt)) return -1;
         }
         if (!t.fresh) {
             const int ntiles = (geom_.total + e.pt - 1) / e.pt;
-            hipLaunchKernelGGL(e.setup, dim3(ntiles), dim3(256), 0, stream_, dgeom(), t.src, t.pix);
+            hipLaunchKernelGGL(e.setup, dim3(ntiles), dim3(256), 0, f.stream, dgeom(f.io), t.src, t.pix);
             HIP_OK(hipGetLastError());
             t.fresh = true;
         }
@@ -998,8 +1035,8 @@ private:
     }
 
     // index tables of the current batch geometry for conv_board_kernel (built on first use)
-    int board_tabs(const BoardTabs** out) {
-        BoardTabs& t = io_[cur_slot_].board;
+    int board_tabs(Fwd& f, const BoardTabs** out) {
+        BoardTabs& t = f.io.board;
         if (!t.src) {
             // a tile holds at least one sample
             if (dev_alloc(&t.src, (size_t)max_batch_ * kBoardMaxPos) || dev_alloc(&t.pix, (size_t)max_batch_ * kBoardPT) ||
@@ -1009,7 +1046,7 @@ private:
         // (a slot's tables may be kept for a shorter batch of the same geometry -- enqueue_inputs' prefix rule trusts the
         // sizes recorded at enqueue time; what counts here is how many tiles the tables were BUILT for)
         if (!t.fresh || t.npos_built != board_plan_.npos || board_plan_.ntiles > t.ntiles_built) {
-            hipLaunchKernelGGL(board_setup_kernel, dim3(board_plan_.ntiles), dim3(256), 0, stream_, dgeom(), board_plan_.npos, t.src,
+            hipLaunchKernelGGL(board_setup_kernel, dim3(board_plan_.ntiles), dim3(256), 0, f.stream, dgeom(f.io), board_plan_.npos, t.src,
                                t.pix, t.cols);
             HIP_OK(hipGetLastError());
             t.fresh = true;
@@ -1019,13 +1056,17 @@ private:
         *out = &t;
         return 0;
     }
+    // the board tiles of the current batch geometry (computed on first use)
+    const BoardPlan& plan() {
+        if (!board_plan_valid_) { board_plan_ = board_plan(geom_, flags_.conv); board_plan_valid_ = true; }
+        return board_plan_;
+    }
     // The one-workgroup-per-board kernel applies to fp16 3x3 layers whenever the batch's boards fit its tiles, however empty
     // the tiles are: which convolution kernel a sample meets must not depend on its batch mates (a lone 9x9 board fills a fifth
     // of its tile; with the across-sample kernel it came out ~1e-4 away from the same position inside a larger batch).
     const BoardEntry* choose_board(const ConvLayerDev& L, int* kot_tiles) {
         if (sizeof(T) != 2 || L.k != 3) return nullptr;
-        if (!board_plan_valid_) { board_plan_ = board_plan(geom_, flags_.conv); board_plan_valid_ = true; }
-        return pick_board(board_plan_, L.ko_pad, kot_tiles, flags_.board_kot);
+        return pick_board(plan(), L.ko_pad, kot_tiles, flags_.board_kot);
     }
 
     // Does this layer of the persistent launch get the generated epilogue (tower_seam.py epi_hook)?  Then its weights and bias go
@@ -1037,9 +1078,59 @@ private:
                L.cout_s == be->kot && L.ko_pad == be->kot && L.w_board && L.bias_board;
     }
 
+    // The last step of a board convolution (conv, conv_se) once its parameters are built: it joins the pending persistent run
+    // (to_run), or ends that run and is launched now -- `fn` with sp.b, or be->fn_se with sp when has_se.  Outside a chained
+    // forward the layer takes the row-order weights wherever the generated epilogue covers it.
+    int board_launch(Fwd& f, const char* name, const ConvLayerDev& L, const BoardEntry* be, BoardFn fn, BoardSeParams& sp, bool has_se,
+                     bool to_run, int grid, double flops, double bytes) {
+        BoardParams& bp = sp.b;
+        ConvParams& p = bp.c;
+        if (!f.chained && board_row_order_ok(L, be, bp, p.act)) { p.w = L.w_board; p.bias = L.bias_board; bp.row_order = 1; }
+        // a pending run this layer does not join ends here (a launch = an ordered point: the table starts afresh)
+        if (!f.run.empty() && !(to_run && f.run_kot == be->kot) && tower_flush(f)) return -1;
+        if (rows_use(f, p, name)) return -1;
+        if (to_run) return tower_append(f, be->kot, sp, has_se, flops, bytes);
+        const size_t lds = be->lds(board_plan_.npos);
+        return timed(f, name, flops, bytes, [&] {
+            if (has_se) hipLaunchKernelGGL(be->fn_se, dim3(grid), dim3(512), lds, f.stream, sp);
+            else hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, f.stream, bp);
+        });
+    }
+
+    // An SE layer of a mixed batch (conv_se, conv_sx): WHICH samples take the fused form is a property of the sample alone, never
+    // of its batch mates (a position's result must not depend on what else the queue collected: the fused forms pool the fp32
+    // accumulators, the separate kernels pool x rounded to fp16).  `fused(bs)` holds for the larger boards, and the device order
+    // is largest first, so the fused samples -- and their tiles -- lead the batch: of the forward's tiles, [f0, f1) are fused
+    // and [r0, r1) are the plain tail.
+    struct SeSplit { int f0, f1, r0, r1; };
+    template <typename Rule> SeSplit se_split(const Fwd& f, Rule fused) const {
+        int s = 0, tile = 0;
+        while (s < geom_.n && fused(geom_.bsz[s])) ++s;
+        while (tile < board_plan_.ntiles && board_plan_.tile_first[tile] < s) ++tile;  // the first tile that is not fused
+        const int t1 = f.tile0 + f.ntiles;
+        return SeSplit{f.tile0, std::min(t1, tile), std::max(f.tile0, tile), t1};
+    }
+    // ... and its plain tail, the tiles [r0, r1) behind: the board convolution of `bp` over kts channel tiles without activation,
+    // residual or row order, then the SE unit's three kernels on those tiles' samples.
+    int se_tail(Fwd& f, const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const BoardEntry* be, const BoardParams& bp,
+                int kts, int r0, int r1, T* out, const T* res, int C, int act) {
+        BoardParams rest = bp;
+        rest.row_order = 0;
+        rest.c.w = L.w; rest.c.bias = L.bias; rest.c.res = nullptr; rest.c.act = kIdentity;
+        rest.c.npos = r0; rest.c.num_pix_tiles = r1 - r0;  // (npos: the launch's first tile, conv_board_kernel)
+        const int s0 = board_plan_.tile_first[r0], s1 = board_plan_.tile_first[r1];
+        const ConvCost cost = conv_cost(geom_.off[s1] - geom_.off[s0], L.cin, L.cout, 9, false, sizeof(T));
+        const auto fn = be->fn;
+        const size_t lds = be->lds(board_plan_.npos);
+        const int grid = (r1 - r0) * kts;
+        if (timed(f, "conv3x3_tower", cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, f.stream, rest); }))
+            return -1;
+        return se_unit(f, sq, ex, out, res, C, round_up(C, 32), act, s0, s1 - s0);
+    }
+
     // A block's last 3x3 convolution with the squeeze-and-excitation unit that follows it inside the kernel
     // (conv_board.h).  Returns 1 when the fused kernel does not apply (the caller then runs conv + se_unit), 0 / -1.
-    int conv_se(const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const T* in, T* out, const T* res, int C, int act) {
+    int conv_se(Fwd& f, const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const T* in, T* out, const T* res, int C, int act) {
         const bool off = !flags_.se_fused;
         int bkt = 0;
         const BoardEntry* be = nullptr;
@@ -1053,68 +1144,44 @@ private:
         const bool staged = sq.img16 && ex.img16;
         if (!staged && (sq.out % 4 || sq.out > 512 || ex.out % 4 || ex.out > 2048 || 512 % (sq.out / 4) || 512 % (ex.out / 4))) return 1;
         if constexpr (sizeof(T) != 2) return 1;
-        // WHICH samples take the fused form is a property of the sample alone, never of its batch mates (a position's result
-        // must not depend on what else the queue collected: the fused form pools the fp32 accumulators, the separate kernels
-        // pool x rounded to fp16): a board too large to share a tile with another of its size (2 bs^2 > 384 pixel slots, i.e.
-        // bs >= 14) is ALWAYS alone in its tile and ALWAYS fused; a smaller board ALWAYS goes through the separate kernels, also
-        // when it happens to sit alone in a tile.  The device order is largest first, so the fused samples -- and their tiles,
-        // one each -- lead the batch: tiles [0, nbig) fused, tiles [nbig, ntiles) = samples [nbig, n) plain convolution + SE unit.
-        int nbig = 0;
-        while (nbig < geom_.n && 2 * geom_.bsz[nbig] * geom_.bsz[nbig] > kBoardPT) ++nbig;
-        if (nbig == 0) return 1;
-        const bool split = nbig < geom_.n;
+        // fused: a board too large to share a tile with another of its size (2 bs^2 > 384 pixel slots, i.e. bs >= 14), alone in
+        // its tile; a smaller board ALWAYS goes through the separate kernels, also when it happens to sit alone in a tile
+        const auto [f0, f1, r0, r1] = se_split(f, [](int bs) { return 2 * bs * bs > kBoardPT; });
+        if (f1 <= f0) return 1;
+        // (conv_board_se_kernel's tile is its workgroup id: chains_for_batch() keeps a network with this form to one chain)
+        if (f0 > 0) return fail("chained forward: conv_board_se_kernel starts at tile 0");
         const BoardTabs* tabs = nullptr;
-        if (board_tabs(&tabs)) return -1;
+        if (board_tabs(f, &tabs)) return -1;
         BoardSeParams sp;
         std::memset(&sp, 0, sizeof(sp));  // padding too: the tower table is compared bytewise with its cached copy
         BoardParams& bp = sp.b;
         board_params(bp, board_plan_, tabs->src, tabs->pix, tabs->cols, flags_.arith);
         ConvParams& p = bp.c;
-        conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
-        p.npos = 0; p.num_pix_tiles = board_plan_.ntiles;
+        conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+        p.npos = 0; p.num_pix_tiles = f.ntiles;
         sp.squeeze = sq.dev(); sp.excite = ex.dev(); sp.C = C;
         sp.w1h = staged ? sq.img16 : nullptr; sp.w2h = staged ? ex.img16 : nullptr;
         sp.w1_bytes = sq.img_bytes; sp.w2_bytes = ex.img_bytes;
 #ifdef SAYURI_EXPERIMENTS
         if (flags_.board_dbg < 0) {  // negative n: timeline of the n-th SE convolution of the forward
             if (!d_dbg_ && dev_alloc(&d_dbg_, 4 * 8 * 8)) return -1;
-            if (++dbg_se_call_ == -flags_.board_dbg) { bp.dbg = d_dbg_; dbg_is_se_ = true; }
+            if (++f.dbg_se_call == -flags_.board_dbg) { bp.dbg = d_dbg_; dbg_is_se_ = true; }
         }
 #endif
-        const ConvCost cost = conv_cost(geom_.total, L.cin, L.cout, 9, res, sizeof(T));
-        const double flops = cost.flops + 2.0 * geom_.n * ((double)sq.in * sq.out + (double)ex.in * ex.out), bytes = cost.bytes;
-        if (board_row_order_ok(L, be, bp, act)) { p.w = L.w_board; p.bias = L.bias_board; bp.row_order = 1; }
-        const bool to_run = !split && tower_ok(be->kot) && !bp.dbg;
-        if (!run_.empty() && !(to_run && run_kot_ == be->kot) && tower_flush()) return -1;
-        if (rows_use(in, L.cin_s, "conv3x3_tower_se") || rows_use(out, L.cout_s, "conv3x3_tower_se") || rows_use(res, L.cout_s, "conv3x3_tower_se"))
-            return -1;
-        if (to_run) return tower_append(be->kot, sp, true, flops, bytes);
-        const auto fn = be->fn_se;
-        const size_t lds = be->lds(board_plan_.npos);
-        const int grid = split ? nbig : board_plan_.ntiles;
-        if (timed("conv3x3_tower_se", flops, bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, sp); })) return -1;
-        if (!split) return 0;
-        // the small boards of the batch: the same convolution without epilogue extras on the tiles behind, then the unit's
-        // three kernels on the samples behind
-        BoardParams rest = bp;
-        rest.row_order = 0;
-        rest.c.w = L.w; rest.c.bias = L.bias; rest.c.res = nullptr; rest.c.act = kIdentity;
-        rest.c.npos = nbig;  // first tile of the launch (conv_board_kernel)
-        rest.c.num_pix_tiles = board_plan_.ntiles - nbig;
-        const auto fn2 = be->fn;
-        const int grid2 = rest.c.num_pix_tiles;  // be->kot covers the layer: one channel tile
-        if (timed("conv3x3_tower", flops, bytes, [&] { hipLaunchKernelGGL(fn2, dim3(grid2), dim3(512), lds, stream_, rest); })) return -1;
-        return se_unit(sq, ex, out, res, C, round_up(C, 32), act, nbig);
+        const ConvCost cost = conv_cost(f.px, L.cin, L.cout, 9, res, sizeof(T));
+        const double flops = cost.flops + 2.0 * f.ns * ((double)sq.in * sq.out + (double)ex.in * ex.out);
+        const bool to_run = r1 <= r0 && !f.chained && tower_ok(be->kot) && !bp.dbg;
+        if (board_launch(f, "conv3x3_tower_se", L, be, be->fn, sp, true, to_run, f1 - f0, flops, cost.bytes)) return -1;
+        // the small boards behind: be->kot covers the layer, one channel tile
+        if (r1 > r0 && se_tail(f, L, sq, ex, be, bp, 1, r0, r1, out, res, C, act)) return -1;
+        return 0;
     }
-
 
     // A block's last 3x3 convolution with its SE unit when the layer's channels are split over kts = 2..4 workgroups of 128
     // (conv_board_sx.h: the siblings exchange their partial squeeze sums inside the launch).  Returns 1 when the form does not apply
-    // (the caller runs conv + se_unit), 0 / -1.  WHICH samples take it is a property of the sample alone: a board of which at
-    // most kSxMaxSub fit a tile (9x9 and larger) ALWAYS does, a smaller one NEVER -- the device order is largest first, so the
-    // tiles [0, T) of the batch are fused and [T, ntiles) = the samples behind take the plain convolution + the unit's three
-    // kernels, exactly as conv_se splits a mixed batch.  Honours the tile range of a chained forward.
-    int conv_sx(const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const T* in, T* out, const T* res, int C, int act) {
+    // (the caller runs conv + se_unit), 0 / -1.  Fused: a board of which at most kSxMaxSub fit a tile (9x9 and larger), never a
+    // smaller one.  Honours the tile range of a chained forward.
+    int conv_sx(Fwd& f, const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const T* in, T* out, const T* res, int C, int act) {
         if constexpr (sizeof(T) != 2) return 1;
         if (!flags_.se_split || sx_disabled_ || !sq.sx_img || !ex.sx_img || !sx_kts_ || L.ko_pad != sx_kts_ * 128 || L.cout_s != L.ko_pad) return 1;
         int bkt = 0;
@@ -1123,39 +1190,32 @@ private:
         for (const auto& e : kBoardEntries)
             if (e.kot == 128 && e.lds(board_plan_.npos) <= kMaxLds) be = &e;
         if (!be) return 1;
-        auto per_tile = [](int bs) {
+        const auto [f0, f1, r0, r1] = se_split(f, [](int bs) {
             BoardPack pk;
             int k = 0;
             while (pk.fits(bs)) { pk.add(bs); ++k; }
-            return k;
-        };
-        int nf = 0;
-        while (nf < geom_.n && per_tile(geom_.bsz[nf]) <= kSxMaxSub) ++nf;
-        int T0 = 0;  // first tile that is not fused
-        while (T0 < board_plan_.ntiles && board_plan_.tile_first[T0] < nf) ++T0;
-        const int t0 = rg_tile0_, t1 = rg_tile0_ + range_ntiles();
-        const int f0 = t0, f1 = std::min(t1, T0), r0 = std::max(t0, T0), r1 = t1;
-        if (!run_.empty() && tower_flush()) return -1;
+            return k <= kSxMaxSub;
+        });
+        if (!f.run.empty() && tower_flush(f)) return -1;
         const BoardTabs* tabs = nullptr;
-        if (board_tabs(&tabs)) return -1;
-        if (rows_use(in, L.cin_s, "conv3x3_tower_sx") || rows_use(out, L.cout_s, "conv3x3_tower_sx") || rows_use(res, L.cout_s, "conv3x3_tower_sx"))
-            return -1;
-        const unsigned epoch = sx_epoch0_ + 1u + (unsigned)sx_idx_++;
+        if (board_tabs(f, &tabs)) return -1;
+        const unsigned epoch = f.sx_epoch0 + 1u + (unsigned)f.sx_idx++;
         BoardSxParams sp;
         std::memset(&sp, 0, sizeof(sp));
         BoardParams& bp = sp.b;
         board_params(bp, board_plan_, tabs->src, tabs->pix, tabs->cols, flags_.arith);
         ConvParams& p = bp.c;
-        conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+        conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+        if (rows_use(f, p, "conv3x3_tower_sx")) return -1;
         const size_t lds = be->lds(board_plan_.npos);
         const int kts = sx_kts_;
         if (f1 > f0) {
             p.npos = f0; p.num_pix_tiles = f1 - f0;
             sp.w1t = sq.sx_img; sp.w2t = ex.sx_img; sp.w1_bytes = sq.sx_bytes; sp.w2_bytes = ex.sx_bytes;
             sp.nsizes = board_ - 1; sp.se = sq.out; sp.kts = kts;
-            sp.xchg = io_[cur_slot_].sx_xchg; sp.epoch = epoch; sp.err = sx_err_dev_;
+            sp.xchg = f.io.sx_xchg; sp.epoch = epoch; sp.err = f.io.sx_err_dev;
             sp.dbg_stall = flags_.dbg_sx_stall ? 1 : 0;
-            if (flags_.sx_dbg > 0 && profiling_ && sx_idx_ == flags_.sx_dbg) {
+            if (flags_.sx_dbg > 0 && profiling_ && f.sx_idx == flags_.sx_dbg) {
                 if (!d_sxdbg_ && dev_alloc(&d_sxdbg_, 4 * 64)) return -1;
                 sp.b.dbg = d_sxdbg_;
             }
@@ -1163,135 +1223,112 @@ private:
             const ConvCost cost = conv_cost(geom_.off[s1] - geom_.off[s0], L.cin, L.cout, 9, res, sizeof(T));
             const double flops = cost.flops + 2.0 * (s1 - s0) * ((double)sq.in * sq.out + (double)ex.in * ex.out);
             const int grid = (f1 - f0 + 7) / 8 * 8 * kts;
-            if (timed("conv3x3_tower_sx", flops, cost.bytes, [&] { hipLaunchKernelGGL(conv_board_sx_kernel<2>, dim3(grid), dim3(512), lds, stream_, sp); }))
+            if (timed(f, "conv3x3_tower_sx", flops, cost.bytes, [&] { hipLaunchKernelGGL(conv_board_sx_kernel<2>, dim3(grid), dim3(512), lds, f.stream, sp); }))
                 return -1;
         }
-        if (r1 > r0) {
-            // the small boards behind: the plain convolution (no activation, no residual) on their tiles, then the unit's kernels
-            BoardParams rest = bp;
-            rest.c.res = nullptr; rest.c.act = kIdentity;
-            rest.c.npos = r0; rest.c.num_pix_tiles = r1 - r0;
-            const int s0 = board_plan_.tile_first[r0], s1 = board_plan_.tile_first[r1];
-            const ConvCost cost = conv_cost(geom_.off[s1] - geom_.off[s0], L.cin, L.cout, 9, false, sizeof(T));
-            const auto fn2 = be->fn;
-            const int grid2 = (r1 - r0) * kts;
-            if (timed("conv3x3_tower", cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn2, dim3(grid2), dim3(512), lds, stream_, rest); })) return -1;
-            if (se_unit(sq, ex, out, res, C, round_up(C, 32), act, s0, s1 - s0)) return -1;
-        }
+        if (r1 > r0 && se_tail(f, L, sq, ex, be, bp, kts, r0, r1, out, res, C, act)) return -1;
         return 0;
     }
 
-    int conv(const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
+    int conv(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
         int bkt = 0;
         if (const BoardEntry* be = choose_board(L, &bkt)) {
             const BoardTabs* tabs = nullptr;
-            if (board_tabs(&tabs)) return -1;
-            BoardParams bp;
+            if (board_tabs(f, &tabs)) return -1;
+            BoardSeParams sp;
+            std::memset(&sp, 0, sizeof(sp));  // (what the tower table holds of a layer without SE unit)
+            BoardParams& bp = sp.b;
             board_params(bp, board_plan_, tabs->src, tabs->pix, tabs->cols, flags_.arith);
             auto fn = be->fn;
 #ifdef SAYURI_EXPERIMENTS
             if (be->kot == 256 && flags_.board_dbg > 0 && !strcmp(name, "conv3x3_tower")) {
                 // in-kernel timeline of the SAYURI_BOARD_DBG-th tower convolution of the forward (1 = first)
                 if (!d_dbg_ && dev_alloc(&d_dbg_, 4 * 8 * 8)) return -1;
-                if (++dbg_call_ == flags_.board_dbg) {
+                if (++f.dbg_call == flags_.board_dbg) {
                     bp.dbg = d_dbg_;
                     fn = &conv_board_kernel<4, true>;
                 }
             }
 #endif
             ConvParams& p = bp.c;
-            conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
-            p.npos = rg_tile0_; p.num_pix_tiles = range_ntiles();  // (npos: the launch's first tile, conv_board_kernel)
+            conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+            p.npos = f.tile0; p.num_pix_tiles = f.ntiles;  // (npos: the launch's first tile, conv_board_kernel)
 #ifdef SAYURI_EXPERIMENTS
             if (flags_.act_override >= 0) p.act = flags_.act_override;  // timing experiments only
 #endif
-            const ConvCost cost = conv_cost(range_px(), L.cin, L.cout, 9, res, sizeof(T));
-            const bool to_run = bkt == 1 && tower_ok(be->kot) && !bp.dbg && rg_ntiles_ < 0;
-            // a pending run this layer does not join ends here (a launch = an ordered point: the table starts afresh)
-            if (!run_.empty() && !(to_run && run_kot_ == be->kot) && tower_flush()) return -1;
-            if (rows_use(in, L.cin_s, name) || rows_use(out, L.cout_s, name) || rows_use(res, L.cout_s, name)) return -1;
-            if (to_run) {
-                if (board_row_order_ok(L, be, bp, p.act)) { p.w = L.w_board; p.bias = L.bias_board; bp.row_order = 1; }
-                BoardSeParams sp;
-                std::memset(&sp, 0, sizeof(sp));
-                sp.b = bp;
-                return tower_append(be->kot, sp, false, cost.flops, cost.bytes);
-            }
-            const size_t lds = be->lds(board_plan_.npos);
-            const int grid = range_ntiles() * bkt;
-            return timed(name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, bp); });
+            const ConvCost cost = conv_cost(f.px, L.cin, L.cout, 9, res, sizeof(T));
+            const bool to_run = bkt == 1 && !f.chained && tower_ok(be->kot) && !bp.dbg;
+            return board_launch(f, name, L, be, fn, sp, false, to_run, f.ntiles * bkt, cost.flops, cost.bytes);
         }
-        if (rg_ntiles_ >= 0) return fail(std::string("chained forward: layer ") + name + " has no board kernel");
+        if (f.chained) return fail(std::string("chained forward: layer ") + name + " has no board kernel");
         if (const GldsChoice* gc = choose_glds(L)) {
             const TileTabs* tabs = nullptr;
-            if (tile_tabs(*gc->e, &tabs)) return -1;
+            if (tile_tabs(f, *gc->e, &tabs)) return -1;
             GldsParams gp;
             gp.tab_src = tabs->src;
             gp.tab_pix = tabs->pix;
             ConvParams& p = gp.c;
-            conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+            conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
             p.npos = 0; p.num_pix_tiles = gc->ntiles;
             gp.zeros = d_zeros_;
             const ConvCost cost = conv_cost(geom_.total, L.cin, L.cout, 9, res, sizeof(T));
             const auto fn = gc->e->fn;
             const size_t lds = gc->e->lds;
             const int grid = gc->ntiles * (L.ko_pad / (gc->e->wmt * 32));
-            return timed(name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, gp); });
+            return timed(f, name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, f.stream, gp); });
         }
         const int kot = L.wmt * 32, kot_tiles = L.ko_pad / kot;
         TileChoice tc;
         if (choose_tile(L.wmt, kot_tiles, &tc)) return -1;
         ConvParams p;
-        conv_params(p, in, L.w, L.bias, res, out, dgeom(), L.cin_s, L.cout_s, L.ko_pad, L.k * L.k, act);
+        conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, L.k * L.k, act);
         p.npos = tc.npos; p.num_pix_tiles = tc.ntiles;
         const ConvCost cost = conv_cost(geom_.total, L.cin, L.cout, p.taps, res, sizeof(T));
         const auto fn = tc.e->fn;
         const size_t lds = tc.e->lds(tc.npos);
         const int grid = tc.ntiles * kot_tiles;
-        return timed(name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, stream_, p); });
+        return timed(f, name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, f.stream, p); });
     }
 
-    int depthwise(const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
+    int depthwise(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
         const int EPP = ElemTraits<T>::kPieceElems;
         const size_t total = (size_t)geom_.total * (L.cout_s / EPP);
         const int grid = (int)((total + 255) / 256);
         const double px = geom_.total;
-        const BatchGeom g = dgeom();
-        return timed(name, 2.0 * px * L.cout * L.k * L.k, sizeof(T) * px * L.cout * (res ? 3 : 2), [&] {
-            hipLaunchKernelGGL(depthwise_kernel<T>, dim3(grid), dim3(256), 0, stream_, in, res, out,
+        const BatchGeom g = dgeom(f.io);
+        return timed(f, name, 2.0 * px * L.cout * L.k * L.k, sizeof(T) * px * L.cout * (res ? 3 : 2), [&] {
+            hipLaunchKernelGGL(depthwise_kernel<T>, dim3(grid), dim3(256), 0, f.stream, in, res, out,
                                (const float*)L.w, (const float*)L.bias, g, L.cout, L.cout_s, L.k, act);
         });
     }
 
-    // n0: the unit runs on the samples [n0, n) of the batch (conv_se's split of a mixed batch)
-    int se_unit(const FcLayerDev& sq, const FcLayerDev& ex, T* x, const T* res, int C, int cs, int act, int n0 = 0, int count = -1) {
-        const BatchGeom g = dgeom();
-        const int ns = count >= 0 ? count : geom_.n - n0;
+    // the unit on the samples [n0, n0 + ns) of the batch
+    int se_unit(Fwd& f, const FcLayerDev& sq, const FcLayerDev& ex, T* x, const T* res, int C, int cs, int act, int n0, int ns) {
+        const BatchGeom g = dgeom(f.io);
         const double px = geom_.off[n0 + ns] - geom_.off[n0];
         constexpr int EPP = ElemTraits<T>::kPieceElems;
         if (cs / EPP > 256) return fail("SE unit: more than 256*8 channels is not supported");
-        if (timed("se_pool", 2.0 * px * C, sizeof(T) * px * C, [&] {
-                hipLaunchKernelGGL(se_pool_kernel<T>, dim3(ns * kSeSplit), dim3(256), 0, stream_, (const T*)x,
-                                   d_separt_, g, cs, n0);
+        float *separt = f.io.separt, *gate = f.io.gate;
+        if (timed(f, "se_pool", 2.0 * px * C, sizeof(T) * px * C, [&] {
+                hipLaunchKernelGGL(se_pool_kernel<T>, dim3(ns * kSeSplit), dim3(256), 0, f.stream, (const T*)x,
+                                   separt, g, cs, n0);
             }))
             return -1;
         const size_t smem = sizeof(float) * (3 * C + sq.out + kSeFcThreads);
-        if (timed("se_fc", 2.0 * ns * ((double)sq.in * sq.out + (double)ex.in * ex.out),
+        if (timed(f, "se_fc", 2.0 * ns * ((double)sq.in * sq.out + (double)ex.in * ex.out),
                   4.0 * ns * ((double)sq.in * sq.out + (double)ex.in * ex.out), [&] {
-                      hipLaunchKernelGGL(se_fc_kernel, dim3(ns), dim3(kSeFcThreads), smem, stream_,
-                                         (const float*)d_separt_, d_gate_, g, C, cs, sq.dev(), ex.dev(), act, n0);
+                      hipLaunchKernelGGL(se_fc_kernel, dim3(ns), dim3(kSeFcThreads), smem, f.stream,
+                                         (const float*)separt, gate, g, C, cs, sq.dev(), ex.dev(), act, n0);
                   }))
             return -1;
         const int ppr = cs / EPP;
         const dim3 grid((slot_pix_ * ppr + 256 * kScaleUnroll - 1) / (256 * kScaleUnroll), ns);
-        return timed("se_scale", 3.0 * px * C, sizeof(T) * px * C * 3, [&] {
-            hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, stream_, (const T*)x, res, x,
-                               (const float*)d_gate_, g, C, cs, act, n0);
+        return timed(f, "se_scale", 3.0 * px * C, sizeof(T) * px * C * 3, [&] {
+            hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, f.stream, (const T*)x, res, x,
+                               (const float*)gate, g, C, cs, act, n0);
         });
     }
 
-    // small pool of activation buffers
-    static constexpr int kNumBufs = 6;
     // -------------------------------------------------------------- who may write which bytes when (the buffer table)
     // Launches on one stream are ordered grid-wide; the layers INSIDE a persistent tower run are not (a workgroup walks the
     // whole run on its own clock), and neither are the chains of a chained forward (streams of their own).  In such an
@@ -1305,208 +1342,210 @@ private:
     //   `in` (packed input)       pack_bits / pack_input         input conv's cin_s (64) never inside the forward (kept to its end)
     //   pool buffers x, y, t0...  the convolution they are `out` the tower's cout_s      as soon as the layer that reads them is
     //                             of (epilogue, own tile's rows)  (256 / 384 / 128)        appended: give() -> take(), SAME stride only
-    //   d_separt_, d_gate_        se_pool / se_fc, per sample     per-sample records      per sample, inside its chain
+    //   io.separt, io.gate        se_pool / se_fc, per sample     per-sample records      per sample, inside its chain
     //   se_xchg (384-ch SE)       the sibling channel tiles       per (tile, channel tile) next SE layer (tagged with the layer's epoch)
-    //   d_prob_ ... d_own_        the heads kernel                per sample              by the ticket's next submit
+    //   io.prob ... io.own        the heads kernel                per sample              by the ticket's next submit
     //
     // rounds 3-4 broke the first line (the input's buffer went back to the pool and came out again as a block's output with
     // stride 256: a late workgroup's input lay under an early workgroup's third layer).  The table below is that rule as a
     // run-time check: every use of a pool buffer inside an unordered scope names its stride, and a second stride is refused.
+    // It spans every chain of a chained forward (forward() resets it once).
     int rows_stride_[kNumBufs] = {};          // 0: not used yet in the current scope
     const char* rows_first_[kNumBufs] = {};   // the layer that fixed it
     void rows_reset() {
         for (int i = 0; i < kNumBufs; ++i) rows_stride_[i] = 0;
     }
-    int rows_use(const T* p, int stride, const char* layer) {
-        if (!p || flags_.dbg_recycle_input >= 2) return 0;
-        for (int i = 0; i < kNumBufs; ++i) {
-            if (bufs_[i] != p) continue;
-            if (rows_stride_[i] && rows_stride_[i] != stride)
-                return fail(std::string("activation buffer ") + std::to_string(i) + " is used with row stride " + std::to_string(stride) + " by " +
-                            layer + " and with " + std::to_string(rows_stride_[i]) + " by " + (rows_first_[i] ? rows_first_[i] : "?") +
-                            " inside one persistent run / chained forward: the rows of different tiles would overlap");
-            rows_stride_[i] = stride;
-            rows_first_[i] = layer;
-        }
+    // the buffers of one layer: `in` with its cin_s, `out` and `res` with its cout_s
+    int rows_use(const Fwd& f, const ConvParams& p, const char* layer) {
+        const void* use[3] = {p.in, p.out, p.res};
+        for (int u = 0; u < 3 && flags_.dbg_recycle_input < 2; ++u)
+            for (int i = 0; i < kNumBufs; ++i) {
+                if (!use[u] || f.io.bufs[i] != use[u]) continue;
+                const int stride = u ? p.cout_s : p.cin_s;
+                if (rows_stride_[i] && rows_stride_[i] != stride)
+                    return fail(std::string("activation buffer ") + std::to_string(i) + " is used with row stride " + std::to_string(stride) + " by " +
+                                layer + " and with " + std::to_string(rows_stride_[i]) + " by " + (rows_first_[i] ? rows_first_[i] : "?") +
+                                " inside one persistent run / chained forward: the rows of different tiles would overlap");
+                rows_stride_[i] = stride;
+                rows_first_[i] = layer;
+            }
         return 0;
     }
-    int take() {
-        for (int i = 0; i < kNumBufs; ++i)
-            if (!busy_[i]) { busy_[i] = true; return i; }
-        return -1;
-    }
-    void give(int i) { busy_[i] = false; }
 
     const ConvLayerDev& cv(int id) const { return convs_.at(id); }
     const FcLayerDev& fc(int id) const { return fcs_.at(id); }
 
     // -------------------------------------------------------------- the graph
-    // One forward of the current batch: as ONE chain of launches on stream_, or -- chains_for_batch() -- as G chains over G
-    // ranges of tiles on G streams, forked from and joined to stream_ by events (the activations, tables and outputs of the
-    // ranges are disjoint: a tile is whole samples).
-    int forward() {
+    // One forward of ticket t's batch: as ONE chain of launches on the ticket's compute stream, or -- chains_for_batch() -- as
+    // G chains over G ranges of tiles on G streams, forked from and joined to that stream by events (the activations, tables
+    // and outputs of the ranges are disjoint: a tile is whole samples).  zc_pass / zc_misc: see submit().
+    int forward(int t, float* zc_pass = nullptr, float* zc_misc = nullptr) {
         const int G = chains_for_batch();
         last_chains_ = G;
         rows_reset();
+        IoSlot& io = io_[t];
+        Fwd f{t, io, compute_[t]};
+        f.ntiles = plan().ntiles;
+        f.ns = geom_.n;
+        f.px = geom_.total;
+        f.pass = zc_pass ? zc_pass : io.pass;
+        f.misc = zc_misc ? zc_misc : io.misc;
         if (sx_kts_) {
-            IoSlot& io = io_[cur_slot_];
             int nse = 0;
             for (const auto& b : blocks_) nse += b.apply_se ? 1 : 0;
             if (io.sx_epoch > 0xfff00000u) {  // tags about to wrap: start over on a clean buffer (stream order: behind the last readers)
-                HIP_OK(hipMemsetAsync(io.sx_xchg, 0, sizeof(unsigned long long) * (size_t)max_batch_ * sx_kts_ * kSxMaxSub * kSxSlots, stream_));
+                HIP_OK(hipMemsetAsync(io.sx_xchg, 0, sizeof(unsigned long long) * (size_t)max_batch_ * sx_kts_ * kSxMaxSub * kSxSlots, f.stream));
                 io.sx_epoch = 0;
             }
-            sx_epoch0_ = io.sx_epoch;
+            f.sx_epoch0 = io.sx_epoch;
             io.sx_epoch += (unsigned)nse;
         }
-        if (G <= 1) return forward_graph();
+        if (G <= 1) return forward_graph(f);
         if (chain_setup(G)) return -1;
         const BoardTabs* tabs = nullptr;
-        if (board_tabs(&tabs)) return -1;  // built on stream_, in front of the fork
-        hipStream_t main = stream_;
-        HIP_OK(hipEventRecord(chain_fork_, main));
-        int rc = 0;
+        if (board_tabs(f, &tabs)) return -1;  // built on the ticket's stream, in front of the fork
+        HIP_OK(hipEventRecord(chain_fork_, f.stream));
         const int nt = board_plan_.ntiles;
-        for (int g = 0; g < G && rc == 0; ++g) {
-            rg_tile0_ = (int)((long)nt * g / G);
-            rg_ntiles_ = (int)((long)nt * (g + 1) / G) - rg_tile0_;
-            rg_n0_ = board_plan_.tile_first[rg_tile0_];
-            rg_ns_ = board_plan_.tile_first[rg_tile0_ + rg_ntiles_] - rg_n0_;
-            stream_ = chain_stream_[g];
-            hipError_t e = hipStreamWaitEvent(stream_, chain_fork_, 0);
-            if (flags_.chains_serial && g > 0 && e == hipSuccess) e = hipStreamWaitEvent(stream_, chain_join_[g - 1], 0);
-            if (e == hipSuccess) rc = forward_graph();
-            if (e == hipSuccess && rc == 0) e = hipEventRecord(chain_join_[g], stream_);
-            if (e != hipSuccess) rc = fail(std::string("chained forward: ") + hipGetErrorString(e));
+        for (int g = 0; g < G; ++g) {
+            Fwd c = f;  // (nothing of f's layer-to-layer state is used yet)
+            c.stream = chain_stream_[g];
+            c.chained = true;
+            c.tile0 = (int)((long)nt * g / G);
+            c.ntiles = (int)((long)nt * (g + 1) / G) - c.tile0;
+            c.n0 = board_plan_.tile_first[c.tile0];
+            c.ns = board_plan_.tile_first[c.tile0 + c.ntiles] - c.n0;
+            c.px = geom_.off[c.n0 + c.ns] - geom_.off[c.n0];
+            hipError_t e = hipStreamWaitEvent(c.stream, chain_fork_, 0);
+            if (flags_.chains_serial && g > 0 && e == hipSuccess) e = hipStreamWaitEvent(c.stream, chain_join_[g - 1], 0);
+            if (e == hipSuccess && forward_graph(c)) return -1;
+            if (e == hipSuccess) e = hipEventRecord(chain_join_[g], c.stream);
+            if (e != hipSuccess) return fail(std::string("chained forward: ") + hipGetErrorString(e));
         }
-        stream_ = main;
-        rg_tile0_ = 0; rg_ntiles_ = -1; rg_n0_ = 0; rg_ns_ = -1;
-        if (rc) return rc;
-        for (int g = 0; g < G; ++g) HIP_OK(hipStreamWaitEvent(main, chain_join_[g], 0));
+        for (int g = 0; g < G; ++g) HIP_OK(hipStreamWaitEvent(f.stream, chain_join_[g], 0));
         return 0;
     }
 
-    int forward_graph() {
+    // The batch's planes or packed records -> the input convolution's layout in buffer `in`, for the samples of f.
+    int pack_input(Fwd& f, T* dst) {
+        const int cin = desc_.input_channels, cs = cv(SAYURI_L_INPUT_CONV).cin_s, board = board_;
+        const int n0 = f.n0, ns = f.ns;
+        const double px = f.px;
+        const BatchGeom g = dgeom(f.io);
+        const IoSlot& io = f.io;
+        if (io.packed_binary > 0) {
+            // (records read across PCIe: one workgroup per sample, so that a record crosses once)
+            const unsigned* rec = io.packed_src ? io.packed_src : io.packed;
+            const int split = io.packed_src ? 1 : kPackSplit;
+            const int nbin = io.packed_binary, words = nbin * 12 + 8;
+            return timed(f, "pack_input", 0, (double)ns * words * 4 + px * cs * sizeof(T), [&] {
+                hipLaunchKernelGGL(pack_bits_kernel<T>, dim3(ns * split), dim3(256), 0, f.stream, rec, words, nbin, dst, g, cin, cs,
+                                   io.g_perm, n0, split);
+            });
+        }
+        const int grid = ns * kPackSplit;  // kPackSplit workgroups per sample
+        const int chunk = pack_input_chunk(slot_pix_, cs, (int)sizeof(T));
+        const size_t lds = (size_t)chunk * (cs * sizeof(T) + 16);
+        const size_t flat_lds = pack_input_flat_lds(slot_pix_, cs, (int)sizeof(T));
+        // a sample that fits 64 KiB of LDS whole and whose planes are below 2^16 floats: one workgroup per sample
+        const bool flat = flat_lds <= 64 * 1024 && (size_t)cin * board * board < 65536;
+        return timed(f, "pack_input", 0, px * cin * 4 + px * cs * sizeof(T), [&] {
+            if (flat)
+                hipLaunchKernelGGL(pack_input_flat_kernel<T>, dim3(ns), dim3(kPackFlatThreads), flat_lds, f.stream,
+                                   (const float*)io.planes, dst, g, cin, cs, board, io.g_perm, n0);
+            else
+                hipLaunchKernelGGL(pack_input_kernel<T>, dim3(grid), dim3(kPackThreads), lds, f.stream,
+                                   (const float*)io.planes, dst, g, cin, cs, board, io.g_perm, chunk, n0);
+        });
+    }
+
+    int forward_graph(Fwd& f) {
         const auto& d = desc_;
         const int C = d.residual_channels, csC = round_up(C, 32), act = d.default_act;
-        const BatchGeom g = dgeom();
-        for (int i = 0; i < kNumBufs; ++i) busy_[i] = false;
-        dbg_call_ = 0;
-        dbg_se_call_ = 0;
-        sx_idx_ = 0;
-        run_.clear();
-        table_used_ = 0;
+        T* const* buf = f.io.bufs;
 
-        int x = take();
-        {
-            const ConvLayerDev& L = cv(SAYURI_L_INPUT_CONV);
-            const int in = take();
-            const int n0 = rg_n0_, ns = range_ns();
-            const int grid = ns * kPackSplit;  // kPackSplit workgroups per sample
-            const double px = range_px();
-            T* dst = bufs_[in];
-            const int cin = d.input_channels, cs = L.cin_s, board = board_;
-            const IoSlot& io = io_[cur_slot_];
-            if (io.packed_binary > 0) {
-                // (records read across PCIe: one workgroup per sample, so that a record crosses once)
-                const unsigned* rec = io.packed_src ? io.packed_src : io.packed;
-                const int split = io.packed_src ? 1 : kPackSplit;
-                const int nbin = io.packed_binary, words = nbin * 12 + 8;
-                if (timed("pack_input", 0, (double)ns * words * 4 + px * cs * sizeof(T), [&] {
-                        hipLaunchKernelGGL(pack_bits_kernel<T>, dim3(ns * split), dim3(256), 0, stream_, rec, words, nbin, dst, g, cin, cs,
-                                           (const int*)d_perm_, n0, split);
-                    }))
-                    return -1;
-            } else {
-                const int chunk = pack_input_chunk(slot_pix_, cs, (int)sizeof(T));
-                const size_t lds = (size_t)chunk * (cs * sizeof(T) + 16);
-                const size_t flat_lds = pack_input_flat_lds(slot_pix_, cs, (int)sizeof(T));
-                // a sample that fits 64 KiB of LDS whole and whose planes are below 2^16 floats: one workgroup per sample
-                const bool flat = flat_lds <= 64 * 1024 && (size_t)cin * board * board < 65536;
-                if (timed("pack_input", 0, px * cin * 4 + px * cs * sizeof(T), [&] {
-                        if (flat)
-                            hipLaunchKernelGGL(pack_input_flat_kernel<T>, dim3(ns), dim3(kPackFlatThreads), flat_lds, stream_,
-                                               (const float*)d_planes_, dst, g, cin, cs, board, (const int*)d_perm_, n0);
-                        else
-                            hipLaunchKernelGGL(pack_input_kernel<T>, dim3(grid), dim3(kPackThreads), lds, stream_,
-                                               (const float*)d_planes_, dst, g, cin, cs, board, (const int*)d_perm_, chunk, n0);
-                    }))
-                    return -1;
-            }
-            if (conv("conv3x3_input", L, bufs_[in], bufs_[x], nullptr, act)) return -1;
-            if (flags_.dbg_recycle_input) give(in);  // SAYURI_DEBUG_RECYCLE_INPUT: rounds 3-4's hand-back, to show what catches it
-            // `in` is NOT handed back: it stays the packed input's buffer for the whole forward.  Its rows have the input
-            // convolution's channel stride (64), every later buffer the tower's (256 / 384): recycled as a block's output, sample
-            // m's rows would lie on top of sample n's packed input.  With a kernel boundary between every two layers and one
-            // stream that is harmless.  Inside the persistent launch it is not -- a workgroup's layers follow one another with no
-            // grid-wide order, and a workgroup that STARTS LATE (more tiles than CUs, or the chip shared with another ticket's
-            // kernels) found its packed input overwritten by an early workgroup's third layer -- and across the chains of one
-            // forward neither.  Rounds 3-4 recycled it: every full-chip launch won that race by a wide margin (all 256 workgroups
-            // start together, the input is read within the first ~80 us and overwritten after ~170), which is why it took round
-            // 5's bit-level harness to see it (tools/gpu/concurrent_ctx_dbg.py, chains_layers_dbg.py).
-        }
+        int x = f.take();
+        const int in = f.take();
+        if (pack_input(f, buf[in])) return -1;
+        if (conv(f, "conv3x3_input", cv(SAYURI_L_INPUT_CONV), buf[in], buf[x], nullptr, act)) return -1;
+        if (flags_.dbg_recycle_input) f.give(in);  // SAYURI_DEBUG_RECYCLE_INPUT: rounds 3-4's hand-back, to show what catches it
+        // `in` is NOT handed back: it stays the packed input's buffer for the whole forward.  Its rows have the input
+        // convolution's channel stride (64), every later buffer the tower's (256 / 384): recycled as a block's output, sample
+        // m's rows would lie on top of sample n's packed input.  With a kernel boundary between every two layers and one
+        // stream that is harmless.  Inside the persistent launch it is not -- a workgroup's layers follow one another with no
+        // grid-wide order, and a workgroup that STARTS LATE (more tiles than CUs, or the chip shared with another ticket's
+        // kernels) found its packed input overwritten by an early workgroup's third layer -- and across the chains of one
+        // forward neither.  Rounds 3-4 recycled it: every full-chip launch won that race by a wide margin (all 256 workgroups
+        // start together, the input is read within the first ~80 us and overwritten after ~170), which is why it took round
+        // 5's bit-level harness to see it (tools/gpu/concurrent_ctx_dbg.py, chains_layers_dbg.py).
 
         for (int b = 0; b < d.residual_blocks; ++b) {
             const auto& bd = blocks_[b];
             const bool se = bd.apply_se != 0;
             const int last_act = se ? (int)kIdentity : act;
-            const int y = take();
+            const int y = f.take();
             int skip = x;  // buffer added back at the end of the block
             bool se_done = false;  // the SE unit already ran inside the block's last convolution
             if (bd.type == SAYURI_BLOCK_RESIDUAL) {
-                const int t0 = take();
-                if (conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), bufs_[x], bufs_[t0], nullptr, act)) return -1;
+                const int t0 = f.take();
+                if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[x], buf[t0], nullptr, act)) return -1;
                 int fused = 1;
                 if (se) {
-                    fused = conv_se(cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), fc(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE)),
-                                    fc(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE)), bufs_[t0], bufs_[y], bufs_[x], C, act);
+                    fused = conv_se(f, cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), fc(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE)),
+                                    fc(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE)), buf[t0], buf[y], buf[x], C, act);
                     if (fused == 1)
-                        fused = conv_sx(cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), fc(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE)),
-                                        fc(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE)), bufs_[t0], bufs_[y], bufs_[x], C, act);
+                        fused = conv_sx(f, cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), fc(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE)),
+                                        fc(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE)), buf[t0], buf[y], buf[x], C, act);
                     if (fused < 0) return -1;
                     se_done = fused == 0;
                 }
                 if (fused == 1 &&
-                    conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), bufs_[t0], bufs_[y], se ? nullptr : bufs_[x], last_act))
+                    conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t0], buf[y], se ? nullptr : buf[x], last_act))
                     return -1;
-                give(t0);
+                f.give(t0);
             } else if (bd.type == SAYURI_BLOCK_BOTTLENECK) {
-                const int t0 = take(), t1 = take();
-                if (conv("conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), bufs_[x], bufs_[t0], nullptr, act)) return -1;
-                if (conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), bufs_[t0], bufs_[t1], nullptr, act)) return -1;
-                if (conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), bufs_[t1], bufs_[t0], nullptr, act)) return -1;
-                if (conv("conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), bufs_[t0], bufs_[y], se ? nullptr : bufs_[x], last_act)) return -1;
-                give(t0); give(t1);
+                const int t0 = f.take(), t1 = f.take();
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), buf[x], buf[t0], nullptr, act)) return -1;
+                if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[t0], buf[t1], nullptr, act)) return -1;
+                if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t1], buf[t0], nullptr, act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), buf[t0], buf[y], se ? nullptr : buf[x], last_act)) return -1;
+                f.give(t0); f.give(t1);
             } else if (bd.type == SAYURI_BLOCK_NESTED_BOTTLENECK) {
-                const int r1 = take(), t0 = take(), t1 = take();
-                if (conv("conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), bufs_[x], bufs_[r1], nullptr, act)) return -1;
-                if (conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), bufs_[r1], bufs_[t0], nullptr, act)) return -1;
-                if (conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), bufs_[t0], bufs_[t1], bufs_[r1], act)) return -1;
-                if (conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV3)), bufs_[t1], bufs_[t0], nullptr, act)) return -1;
-                if (conv("conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV4)), bufs_[t0], bufs_[r1], bufs_[t1], act)) return -1;
-                if (conv("conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), bufs_[r1], bufs_[y], se ? nullptr : bufs_[x], last_act)) return -1;
-                give(r1); give(t0); give(t1);
+                const int r1 = f.take(), t0 = f.take(), t1 = f.take();
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), buf[x], buf[r1], nullptr, act)) return -1;
+                if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[r1], buf[t0], nullptr, act)) return -1;
+                if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t0], buf[t1], buf[r1], act)) return -1;
+                if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV3)), buf[t1], buf[t0], nullptr, act)) return -1;
+                if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV4)), buf[t0], buf[r1], buf[t1], act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), buf[r1], buf[y], se ? nullptr : buf[x], last_act)) return -1;
+                f.give(r1); f.give(t0); f.give(t1);
             } else {  // mixer: x' = act(dw(x)+b) + x is the new skip
-                const int s2 = take(), t1 = take();
-                if (depthwise("depthwise", cv(SAYURI_L_BLOCK(b, SAYURI_S_DW_CONV)), bufs_[x], bufs_[s2], bufs_[x], act)) return -1;
-                if (conv("conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), bufs_[s2], bufs_[t1], nullptr, act)) return -1;
-                if (conv("conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), bufs_[t1], bufs_[y], se ? nullptr : bufs_[s2], last_act)) return -1;
-                give(t1);
-                give(x);
+                const int s2 = f.take(), t1 = f.take();
+                if (depthwise(f, "depthwise", cv(SAYURI_L_BLOCK(b, SAYURI_S_DW_CONV)), buf[x], buf[s2], buf[x], act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[s2], buf[t1], nullptr, act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t1], buf[y], se ? nullptr : buf[s2], last_act)) return -1;
+                f.give(t1);
+                f.give(x);
                 x = s2;
                 skip = s2;
             }
             if (se && !se_done) {
-                if (se_unit(fc(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE)), fc(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE)), bufs_[y],
-                            bufs_[skip], C, csC, act, rg_n0_, range_ns()))
+                if (se_unit(f, fc(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE)), fc(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE)), buf[y], buf[skip], C, csC,
+                            act, f.n0, f.ns))
                     return -1;
             }
-            give(x);
+            f.give(x);
             x = y;
         }
+        return heads(f, x);
+    }
 
-        // heads
+    // Both heads on the trunk in buffer x: head_board_kernel, one workgroup per sample, or the separate head kernels.
+    int heads(Fwd& f, int x) {
+        const auto& d = desc_;
+        const int C = d.residual_channels, csC = round_up(C, 32), act = d.default_act;
         const int Cp = d.policy_head_channels, Cv = d.value_head_channels;
+        T* const* buf = f.io.bufs;
+        const BatchGeom g = dgeom(f.io);
         HeadParams h;
         h.p_inter = fc(SAYURI_L_P_INTER_FC).dev();
         h.pass_fc = fc(SAYURI_L_PASS_FC).dev();
@@ -1518,7 +1557,7 @@ private:
         h.own_b = cv(SAYURI_L_V_OWNERSHIP).bias;
         h.Cp = Cp; h.cs_p = round_up(Cp, 32); h.Cv = Cv; h.cs_v = round_up(Cv, 32);
         h.prob_ch = d.probabilities_channels; h.act = act; h.board = board_;
-        h.prob = d_prob_; h.pass = zc_pass_ ? zc_pass_ : d_pass_; h.misc = zc_misc_ ? zc_misc_ : d_misc_; h.own = d_own_; h.perm = d_perm_;
+        h.prob = f.io.prob; h.pass = f.pass; h.misc = f.misc; h.own = f.io.own; h.perm = f.io.g_perm;
         if (head_img_ && heads_fused_enabled()) {
             // both heads of a sample in one workgroup: trunk -> LDS -> stacked 1x1 convolution on the matrix cores -> pooling,
             // FCs and the per-pixel planes (head_board.h)
@@ -1530,40 +1569,37 @@ private:
                 hp.dbg = d_hdbg_;
             }
 #endif
-            hp.trunk = bufs_[x]; hp.w = head_img_; hp.w2 = head_img2_; hp.bias = head_bias_; hp.g = g; hp.cs = csC; hp.PT = head_pt_; hp.VT = head_vt_; hp.h = h;
-            hp.n0 = rg_n0_;
+            hp.trunk = buf[x]; hp.w = head_img_; hp.w2 = head_img2_; hp.bias = head_bias_; hp.g = g; hp.cs = csC; hp.PT = head_pt_; hp.VT = head_vt_; hp.h = h;
+            hp.n0 = f.n0;
             const auto fn = head_fn_;
-            {
-                const int ns = range_ns();
-                const double flops = 2.0 * range_px() * C * (Cp + Cv);
-                return timed("heads_fused", flops, range_px() * csC * 2, [&] {
-                    hipLaunchKernelGGL(fn, dim3(ns), dim3(512), kMaxLds, stream_, hp);
-                });
-            }
+            const int ns = f.ns;
+            return timed(f, "heads_fused", 2.0 * f.px * C * (Cp + Cv), f.px * csC * 2, [&] {
+                hipLaunchKernelGGL(fn, dim3(ns), dim3(512), kMaxLds, f.stream, hp);
+            });
         }
-        if (rg_ns_ >= 0) return fail("chained forward reached the separate head kernels");
-        int pb = take();
-        const int vb = take();
-        if (conv("conv1x1_head", cv(SAYURI_L_P_HD_CONV), bufs_[x], bufs_[pb], nullptr, act)) return -1;
+        if (f.chained) return fail("chained forward reached the separate head kernels");
+        int pb = f.take();
+        const int vb = f.take();
+        if (conv(f, "conv1x1_head", cv(SAYURI_L_P_HD_CONV), buf[x], buf[pb], nullptr, act)) return -1;
         if (d.policy_head_type == 1) {
-            const int p2 = take();
-            if (depthwise("depthwise", cv(SAYURI_L_P_DW_CONV), bufs_[pb], bufs_[p2], nullptr, act)) return -1;
-            if (conv("conv1x1_head", cv(SAYURI_L_P_PT_CONV), bufs_[p2], bufs_[pb], nullptr, act)) return -1;
-            give(p2);
+            const int p2 = f.take();
+            if (depthwise(f, "depthwise", cv(SAYURI_L_P_DW_CONV), buf[pb], buf[p2], nullptr, act)) return -1;
+            if (conv(f, "conv1x1_head", cv(SAYURI_L_P_PT_CONV), buf[p2], buf[pb], nullptr, act)) return -1;
+            f.give(p2);
         }
-        if (conv("conv1x1_head", cv(SAYURI_L_V_HD_CONV), bufs_[x], bufs_[vb], nullptr, act)) return -1;
+        if (conv(f, "conv1x1_head", cv(SAYURI_L_V_HD_CONV), buf[x], buf[vb], nullptr, act)) return -1;
         const int maxc = std::max(Cp, Cv);
         const size_t smem = sizeof(float) * (7 * maxc + 512);
-        const T* pc = bufs_[pb];
-        const T* vc = bufs_[vb];
-        return timed("head_tail", 0, 0, [&] {
-            hipLaunchKernelGGL(head_tail_kernel<T>, dim3(2 * geom_.n), dim3(256), smem, stream_, pc, vc, g, h);
+        const T* pc = buf[pb];
+        const T* vc = buf[vb];
+        return timed(f, "head_tail", 0, 0, [&] {
+            hipLaunchKernelGGL(head_tail_kernel<T>, dim3(2 * geom_.n), dim3(256), smem, f.stream, pc, vc, g, h);
         });
     }
 
     // -------------------------------------------------------------- the persistent tower launch (conv_tower.h)
     // Consecutive board convolutions whose channel tile covers the layer are not launched one by one: conv() / conv_se()
-    // append them to run_, and the first launch of anything else (timed()) -- in practice the heads -- sends the whole run
+    // append them to f.run, and the first launch of anything else (timed()) -- in practice the heads -- sends the whole run
     // as ONE launch that walks a table of TowerLayer in device memory.  The table of a slot is re-uploaded only when its
     // contents change (another batch geometry; the buffers and weights of a slot never move).
     static constexpr int kTowerCap = 512;  // table elements per slot
@@ -1576,9 +1612,9 @@ private:
     };
     int tower_load() { return load_tower_module(&tower_mod_, tower_fn_); }
     bool tower_ok(int kot) const { return tower_mod_ && !profiling_ && (kot == 256 || kot == 128); }
-    int tower_append(int kot, const BoardSeParams& sp, bool has_se, double flops, double bytes) {
-        if (!run_.empty() && (run_kot_ != kot || (int)run_.size() + table_used_ >= kTowerCap) && tower_flush()) return -1;
-        if (run_.empty()) { run_kot_ = kot; run_flops_ = run_bytes_ = 0; }
+    int tower_append(Fwd& f, int kot, const BoardSeParams& sp, bool has_se, double flops, double bytes) {
+        if (!f.run.empty() && (f.run_kot != kot || (int)f.run.size() + f.table_used >= kTowerCap) && tower_flush(f)) return -1;
+        if (f.run.empty()) { f.run_kot = kot; f.run_flops = f.run_bytes = 0; }
         TowerLayer t;
         std::memset(&t, 0, sizeof(t));
         t.sp = sp;
@@ -1589,15 +1625,15 @@ private:
         c.num_pix_tiles = 0;
         c.g.n_samples = 0;
         c.g.total_pix = 0;
-        run_.push_back(t);
-        run_flops_ += flops;
-        run_bytes_ += bytes;
+        f.run.push_back(t);
+        f.run_flops += flops;
+        f.run_bytes += bytes;
         return 0;
     }
-    int tower_flush() {
+    int tower_flush(Fwd& f) {
         std::vector<TowerLayer> run;
-        run.swap(run_);  // timed() below must not see a pending run
-        TowerSlot& ts = tower_[cur_slot_];
+        run.swap(f.run);  // timed() below must not see a pending run
+        TowerSlot& ts = tower_[f.t];
         if (!ts.dev) {
             if (dev_alloc(&ts.dev, kTowerCap)) return -1;
             for (int i = 0; i < 2; ++i) {
@@ -1606,7 +1642,7 @@ private:
             }
             ts.cache.assign(kTowerCap, TowerLayer{});
         }
-        const int n = (int)run.size(), first = table_used_;
+        const int n = (int)run.size(), first = f.table_used;
         if (first + n > kTowerCap) return fail("tower table overflow");
         if (flags_.tower_noepi_after >= 0 && tower_launches_++ >= flags_.tower_noepi_after)
             for (auto& t : run)
@@ -1630,36 +1666,34 @@ private:
             ts.next_stage ^= 1;
             HIP_OK(hipEventSynchronize(ts.staged[st]));  // the copy that last read this staging area (never recorded: returns at once)
             std::memcpy(ts.stage[st], run.data(), sizeof(TowerLayer) * n);
-            HIP_OK(hipMemcpyAsync(ts.dev + first, ts.stage[st], sizeof(TowerLayer) * n, hipMemcpyHostToDevice, stream_));
+            HIP_OK(hipMemcpyAsync(ts.dev + first, ts.stage[st], sizeof(TowerLayer) * n, hipMemcpyHostToDevice, f.stream));
             ++table_uploads_;
-            HIP_OK(hipEventRecord(ts.staged[st], stream_));
+            HIP_OK(hipEventRecord(ts.staged[st], f.stream));
             std::memcpy(ts.cache.data() + first, run.data(), sizeof(TowerLayer) * n);
         }
-        table_used_ += n;
-        const hipFunction_t fn = tower_fn_[run_kot_ == 256 ? 0 : 1];
+        f.table_used += n;
+        const hipFunction_t fn = tower_fn_[f.run_kot == 256 ? 0 : 1];
         const TowerLayer* arg = ts.dev + first;
         const int grid = board_plan_.ntiles;
         hipError_t lrc = hipSuccess;
-        if (flags_.tower_sync) HIP_OK(hipStreamSynchronize(stream_));
-        const int rc = timed("tower_run", run_flops_, run_bytes_, [&] {
+        if (flags_.tower_sync) HIP_OK(hipStreamSynchronize(f.stream));
+        const int rc = timed(f, "tower_run", f.run_flops, f.run_bytes, [&] {
             void* params[] = {(void*)&arg};
-            lrc = hipModuleLaunchKernel(fn, grid, 1, 1, 512, 1, 1, 0, stream_, params, nullptr);
+            lrc = hipModuleLaunchKernel(fn, grid, 1, 1, 512, 1, 1, 0, f.stream, params, nullptr);
         });
-        if (flags_.tower_sync && lrc == hipSuccess) HIP_OK(hipStreamSynchronize(stream_));
+        if (flags_.tower_sync && lrc == hipSuccess) HIP_OK(hipStreamSynchronize(f.stream));
         if (lrc != hipSuccess) return fail(std::string("hipModuleLaunchKernel(conv_tower_kernel): ") + hipGetErrorString(lrc));
         return rc;
     }
     // conv_board_sx.h (SE units of layers split over channel tiles)
     int sx_kts_ = 0;                      // channel tiles per layer (0: the network has no such unit)
-    unsigned* sx_err_host_ = nullptr;     // host-visible word a workgroup sets when its wait for the siblings ran out
-    unsigned* sx_err_dev_ = nullptr;
-    unsigned sx_epoch0_ = 0;              // tags of the current forward: sx_epoch0_ + 1 + index of the SE layer
-    int sx_idx_ = 0;
     bool sx_disabled_ = false;            // set by sx_check(): the exchange timed out once on this ctx
-    int sx_check() {
-        if (sx_err_host_ && *(volatile unsigned*)sx_err_host_) {
-            const unsigned e = *(volatile unsigned*)sx_err_host_;
-            *(volatile unsigned*)sx_err_host_ = 0;
+    // ticket t's forwards: did a split SE workgroup's wait for its siblings run out (IoSlot::sx_err_host)?
+    int sx_check(int t) {
+        unsigned* err = io_[t].sx_err_host;
+        if (err && *(volatile unsigned*)err) {
+            const unsigned e = *(volatile unsigned*)err;
+            *(volatile unsigned*)err = 0;
             sx_disabled_ = true;  // this ctx goes on with the separate kernels: a wait that ran out once is not tried again
             return fail("SE exchange between the channel tiles of a board tile timed out (epoch " + std::to_string(e) +
                         "): the results of this forward are invalid; from here on this context runs the unit as separate kernels (SAYURI_SE_SPLIT=0)");
@@ -1670,20 +1704,16 @@ private:
     hipModule_t tower_mod_ = nullptr;
     hipFunction_t tower_fn_[2] = {nullptr, nullptr};
     TowerSlot tower_[2];
-    std::vector<TowerLayer> run_;
-    int run_kot_ = 0, table_used_ = 0;
     long tower_launches_ = 0;
     int table_uploads_ = 0;
     // SAYURI_HIP_FWDSTAT: device time of the forwards sent through submit(), by batch-size class
     hipEvent_t fs_ev_[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     double fs_d2h_ms_ = 0, fs_d2h_max_ = 0;
     long fs_d2h_slow_ = 0;
-    float *zc_pass_ = nullptr, *zc_misc_ = nullptr;  // this submit's pass / misc go straight to these (pinned host) buffers
     bool fs_pending_[2] = {false, false};
     int fs_n_[2] = {0, 0};
     double fs_ms_[3] = {0, 0, 0};
     long fs_cnt_[3] = {0, 0, 0}, fs_uploads_ = 0;
-    double run_flops_ = 0, run_bytes_ = 0;
 
     int device_;
     sayuri_hip_netdesc desc_;
@@ -1693,46 +1723,14 @@ private:
     std::map<int, ConvLayerDev> convs_;
     std::map<int, FcLayerDev> fcs_;
     bool finalized_ = false, have_batch_ = false, profiling_ = false;
-    hipStream_t stream_ = nullptr, h2d_stream_ = nullptr, d2h_stream_ = nullptr;
+    hipStream_t h2d_stream_ = nullptr, d2h_stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     hipEvent_t h2d_done_[2] = {nullptr, nullptr}, fwd_done_[2] = {nullptr, nullptr};
-    // device-side batch i/o, one set per ticket; the d_* members below alias the slot the current forward uses
-    struct IoSlot {
-        float *planes = nullptr, *prob = nullptr, *pass = nullptr, *misc = nullptr, *own = nullptr;
-        unsigned* packed = nullptr;  // packed records of the batch (allocated on first use)
-        const unsigned* packed_src = nullptr;  // non-null: the batch's records are read where the caller has them (pinned host memory)
-        int packed_binary = 0;       // > 0: the slot's current batch came as packed records with this many bit planes
-        int *off = nullptr, *bsz = nullptr, *perm = nullptr;
-        T* bufs[kNumBufs] = {};
-        float *gate = nullptr, *separt = nullptr;
-        unsigned long long* sx_xchg = nullptr;
-        unsigned sx_epoch = 0;  // the last tag used in sx_xchg
-        std::map<int, TileTabs> tabs;   // index tables of the geometry this slot last ran (keyed by tile variant)
-        BoardTabs board;
-        std::vector<int> tabs_bsz;
-        bool tabs_single = false;  // tabs_bsz is one board size with one sample per tile
-        int tabs_n = -1;           // batch size the across-sample tables (tabs) were last built for
-    };
     IoSlot io_[2];
-    hipStream_t compute_[2] = {nullptr, nullptr};
+    hipStream_t compute_[2] = {nullptr, nullptr};  // each ticket's forwards (init())
     bool inorder_ = false;  // a ticket's copies on the ticket's compute stream (init(), submit())
-    int cur_slot_ = 0;
-    void select_slot(int t) {
-        IoSlot& io = io_[t];
-        cur_slot_ = t;
-        d_planes_ = io.planes; d_off_ = io.off; d_bsz_ = io.bsz; d_perm_ = io.perm;
-        d_prob_ = io.prob; d_pass_ = io.pass; d_misc_ = io.misc; d_own_ = io.own;
-        for (int i = 0; i < kNumBufs; ++i) bufs_[i] = io.bufs[i];
-        d_gate_ = io.gate; d_separt_ = io.separt;
-        if (compute_[t]) stream_ = compute_[t];
-    }
     std::vector<void*> allocs_;
     size_t dev_bytes_ = 0;
-    T* bufs_[kNumBufs] = {};
-    bool busy_[kNumBufs] = {};
-    float *d_planes_ = nullptr, *d_gate_ = nullptr, *d_separt_ = nullptr, *d_prob_ = nullptr, *d_pass_ = nullptr, *d_misc_ = nullptr,
-          *d_own_ = nullptr;
-    int *d_off_ = nullptr, *d_bsz_ = nullptr, *d_perm_ = nullptr;
     std::vector<int> perm_;  // device sample -> caller's slot (enqueue_inputs)
     float* d_zeros_ = nullptr;
     int* h_geom_ = nullptr;  // pinned 2-slot ring: [slot][off(max_batch+1) | bsz(max_batch) | perm(max_batch)]
@@ -1750,7 +1748,6 @@ private:
     unsigned long long* d_hdbg_ = nullptr;  // SAYURI_HEADS_DBG timeline of head_board_kernel
     unsigned long long* d_dbg_ = nullptr;  // SAYURI_BOARD_DBG timeline of one tower convolution
     unsigned long long* d_sxdbg_ = nullptr;  // SAYURI_SX_DBG timeline of one split SE convolution
-    int dbg_call_ = 0, dbg_se_call_ = 0;
     bool dbg_is_se_ = false;
     bool board_plan_valid_ = false;
     std::map<int, TileChoice> tile_cache_;
