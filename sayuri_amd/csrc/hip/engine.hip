@@ -1,11 +1,12 @@
 // engine.hip -- the C-ABI of include/sayuri_hip.h: one translation unit in three parts
-//   engine_plan.h   kernel registries, environment switches, batch geometry and tile plans, device images of the layers
+//   engine_plan.h   kernel registries, environment switches, batch geometry, tile plans and the routing of a convolution to its
+//                   kernel family, the device images of the layers and the launch parameters the engine and the taps share
 //   engine_graph.h  Engine<T>: the per-GPU forward graph -- counterpart of the reference's CudaForwardPipe::NNGraph
 //                   (src/neural/cuda/cuda_forward_pipe.cc:133-1090) and its layer objects (src/neural/cuda/cuda_layers.cc),
 //                   re-designed for MI355X: compact NHWC activations (common.h), one workgroup per board with the whole residual
 //                   tower as ONE persistent launch (conv_board.h, conv_tower.h), SE units inside the convolutions (conv_board.h,
 //                   conv_board_sx.h), both heads in one kernel (head_board.h), mixed board sizes without masked work
-//   engine_taps.h   layer-level test taps (sayuri_hip_test_*)
+//   engine_taps.h   layer-level test taps (sayuri_hip_test_*): host layout conversion around ONE launch built by engine_plan.h's code
 // and, in this file, the entry points themselves.
 #include <hip/hip_runtime.h>
 

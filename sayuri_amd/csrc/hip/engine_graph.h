@@ -117,7 +117,7 @@ public:
         // ONE channel stride, and the packed input keeps a buffer of its own (forward_graph), so the chains' rows are disjoint
         // bytes in every buffer.  (The first version recycled the packed input's buffer, whose rows have another stride: a chain
         // that ran ahead overwrote a later chain's input -- a few dozen samples per batch off in two runs of three.)
-        if (sizeof(T) != 2 || flags_.chains == 1 || profiling_ || light_ || !head_img_ || !heads_fused_enabled()) return 1;
+        if (sizeof(T) != 2 || flags_.chains == 1 || profiling_ || light_ || !head_img_ || !flags_.heads_fused) return 1;
         if (desc_.policy_head_type != 0 || tower_covers_net()) return 1;
         for (const auto& b : blocks_)
             if (b.type != SAYURI_BLOCK_RESIDUAL) return 1;  // every layer of the graph must be a board convolution or a per-sample kernel
@@ -127,9 +127,9 @@ public:
             if (e.fn_se && e.kot == L.ko_pad)
                 for (const auto& b : blocks_)
                     if (b.apply_se) return 1;
-        int kts = 0;
-        if (!choose_board(L, &kts) || !board_plan_.ok) return 1;
-        const int wgs = board_plan_.ntiles * kts;
+        const ConvRoute& r = route(L);
+        if (!r.board || !board_plan_.ok) return 1;
+        const int wgs = board_plan_.ntiles * r.tiles;
         if (wgs <= kNumCU) return 1;  // one round already
         int G = flags_.chains > 1 ? flags_.chains : std::min(kMaxChains, std::max(2, (wgs + 159) / 160));
         G = std::min(G, board_plan_.ntiles / 8);
@@ -356,7 +356,7 @@ public:
         geom_.total = geom_.off[n];
         if (geom_.bsz != prev_bsz_) {  // tile choices and index tables depend on the geometry only
             tile_cache_.clear();
-            glds_cache_.clear();
+            route_cache_.clear();
             board_plan_valid_ = false;
         }
         IoSlot& io = io_[t];
@@ -665,7 +665,6 @@ private:
 
     static bool is_tiny_head_conv(int id) { return id == SAYURI_L_PROB_CONV || id == SAYURI_L_V_OWNERSHIP; }
 
-    bool heads_fused_enabled() const { return flags_.heads_fused; }
     // Stacked [policy | value] head-convolution image for head_board_kernel (fp16 engine, normal policy head).
     int build_head_image() {
         const sayuri_hip_netdesc& d = desc_;
@@ -699,41 +698,21 @@ private:
             if (is_tiny_head_conv(kv.first)) {  // consumed by head_tail_kernel in fp32
                 if (dev_upload(&L.w32, L.hw) || dev_upload(&L.bias, L.hb)) return -1;
             } else if (L.depthwise) {
-                const int kk = L.k * L.k;
-                std::vector<float> wt((size_t)kk * L.cout_s, 0.f), b(L.cout_s, 0.f);
-                for (int c = 0; c < L.cout; ++c) {
-                    for (int t = 0; t < kk; ++t) wt[(size_t)t * L.cout_s + c] = L.hw[(size_t)c * kk + t];
-                    b[c] = L.hb[c];
-                }
                 float* w = nullptr;
-                if (dev_upload(&w, wt) || dev_upload(&L.bias, b)) return -1;
+                if (dev_upload(&w, depthwise_image(L.hw.data(), L.cout, L.k * L.k, L.cout_s)) ||
+                    dev_upload(&L.bias, padded_bias(L.hb.data(), L.cout, L.cout_s)))
+                    return -1;
                 L.w = w;
             } else {
-                L.wmt = pick_wmt(L.cout_s, sizeof(T) == 2);
-                const int kot = L.wmt * 32;
-                L.ko_pad = round_up(L.cout_s, kot);
-                const int taps = L.k * L.k, nch = L.cin_s / 32;
-                std::vector<T> img((size_t)taps * nch * 4 * L.ko_pad * 8, from_float_host(0.f));
-                for (int t = 0; t < taps; ++t)
-                    for (int ch = 0; ch < nch; ++ch)
-                        for (int kg = 0; kg < 4; ++kg)
-                            for (int ko = 0; ko < L.cout; ++ko)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int c = ch * 32 + kg * 8 + e;
-                                    if (c >= L.cin) continue;
-                                    const float v = L.hw[((size_t)ko * L.cin + c) * taps + t];
-                                    img[((((size_t)t * nch + ch) * 4 + kg) * L.ko_pad + ko) * 8 + e] = from_float_host(v);
-                                }
-                std::vector<float> b(L.ko_pad, 0.f);
-                std::copy(L.hb.begin(), L.hb.end(), b.begin());
+                conv_tile(L.cout_s, sizeof(T) == 2, &L.wmt, &L.ko_pad);
+                const std::vector<T> img = conv_image<T>(L.hw.data(), L.cin, L.cout, L.k * L.k, L.ko_pad);
+                const std::vector<float> b = padded_bias(L.hb.data(), L.cout, L.ko_pad);
                 T* w = nullptr;
                 if (dev_upload(&w, img) || dev_upload(&L.bias, b)) return -1;
                 L.w = w;
                 if (sizeof(T) == 2 && L.k == 3 && L.ko_pad % 128 == 0) {
                     T* wb = nullptr;
-                    std::vector<float> bb(L.ko_pad);
-                    for (int r = 0; r < L.ko_pad; ++r) bb[r] = b[board_row_channel(r)];
-                    if (dev_upload(&wb, board_row_order(img, L.ko_pad)) || dev_upload(&L.bias_board, bb)) return -1;
+                    if (dev_upload(&wb, board_row_order(img, L.ko_pad)) || dev_upload(&L.bias_board, board_row_order(b, L.ko_pad, 1))) return -1;
                     L.w_board = wb;
                 }
             }
@@ -744,10 +723,7 @@ private:
         for (auto& kv : fcs_) {
             FcLayerDev& L = kv.second;
             if (L.hw.empty() || L.hb.empty()) return fail("missing tensors for fc layer " + std::to_string(kv.first));
-            std::vector<float> wt((size_t)L.in * L.out);
-            for (int o = 0; o < L.out; ++o)
-                for (int i = 0; i < L.in; ++i) wt[(size_t)i * L.out + o] = L.hw[(size_t)o * L.in + i];
-            if (dev_upload(&L.wt, wt) || dev_upload(&L.b, L.hb)) return -1;
+            if (dev_upload(&L.wt, fc_transposed(L.hw.data(), L.in, L.out)) || dev_upload(&L.b, L.hb)) return -1;
             std::vector<float>().swap(L.hw);
             std::vector<float>().swap(L.hb);
         }
@@ -792,8 +768,6 @@ private:
         finalized_ = true;
         return 0;
     }
-
-    static T from_float_host(float v) { return (T)v; }
 
     // fp16 images of the SE units' two FCs, laid out for the LDS-DMA staging of board_se_stage (conv_board.h): the squeeze
     // weights once per board size 2..board with the scaled-mean third of the pooled vector folded into the mean third
@@ -980,32 +954,15 @@ private:
         return 0;
     }
 
-    struct TileChoice { int wnt, npos, ntiles; const typename ConvKernelTable<T>::Entry* e; };
-
-    int choose_tile(int wmt, int kot_tiles, TileChoice* out) {
+    // the generic kernel's variant for the current batch geometry (cached: it depends on the geometry only)
+    int choose_tile(int wmt, int kot_tiles, TileChoice<T>* out) {
         auto it = tile_cache_.find(wmt * 1024 + kot_tiles);
         if (it != tile_cache_.end()) { *out = it->second; return 0; }
-        double best_cost = 1e30;
-        TileChoice best{};
-        bool found = false;
-        for (const auto& e : ConvKernelTable<T>::entries()) {
-            if (e.wmt != wmt) continue;
-            const int PT = 64 * e.wnt;
-            int npos, nsub;
-            geom_.tile_bounds(PT, &npos, &nsub);
-            if (npos > e.npos_cap || nsub > kMaxSub || e.lds(npos) > kMaxLds) continue;
-            const int ntiles = (geom_.total + PT - 1) / PT;
-            const double waves = std::ceil((double)ntiles * kot_tiles / kNumCU);
-            const double cost = waves * (PT + 24);
-            if (cost < best_cost) { best_cost = cost; best = TileChoice{e.wnt, npos, ntiles, &e}; found = true; }
-        }
-        if (!found) return fail("no conv tile configuration fits this batch geometry");
-        tile_cache_[wmt * 1024 + kot_tiles] = best;
-        *out = best;
+        if (!pick_tile<T>(geom_, wmt, kot_tiles, /*widest=*/false, out)) return fail("no conv tile configuration fits this batch geometry");
+        tile_cache_[wmt * 1024 + kot_tiles] = *out;
         return 0;
     }
 
-    struct GldsChoice { const GldsEntry* e; int ntiles; };
     // index tables of the current batch geometry for pixel-tile size 64*wnt (built on first use)
     int tile_tabs(Fwd& f, const GldsEntry& e, const TileTabs** out) {
         TileTabs& t = f.io.tabs[e.wnt];
@@ -1022,18 +979,6 @@ private:
         *out = &t;
         return 0;
     }
-    const GldsChoice* choose_glds(const ConvLayerDev& L) {
-        if (sizeof(T) != 2 || L.k != 3 || L.ko_pad % 128 != 0) return nullptr;
-        const int key = L.ko_pad % 256 == 0 ? 8 : 4;
-        auto it = glds_cache_.find(key);
-        if (it == glds_cache_.end()) {
-            GldsChoice c{nullptr, 0};
-            c.e = pick_glds(geom_, L.ko_pad, &c.ntiles, flags_.conv);
-            it = glds_cache_.emplace(key, c).first;
-        }
-        return it->second.e ? &it->second : nullptr;
-    }
-
     // index tables of the current batch geometry for conv_board_kernel (built on first use)
     int board_tabs(Fwd& f, const BoardTabs** out) {
         BoardTabs& t = f.io.board;
@@ -1061,31 +1006,28 @@ private:
         if (!board_plan_valid_) { board_plan_ = board_plan(geom_, flags_.conv); board_plan_valid_ = true; }
         return board_plan_;
     }
+    // Which kernel family runs layer L on the current batch geometry (route_conv; cached: it depends on the geometry only).
     // The one-workgroup-per-board kernel applies to fp16 3x3 layers whenever the batch's boards fit its tiles, however empty
     // the tiles are: which convolution kernel a sample meets must not depend on its batch mates (a lone 9x9 board fills a fifth
     // of its tile; with the across-sample kernel it came out ~1e-4 away from the same position inside a larger batch).
-    const BoardEntry* choose_board(const ConvLayerDev& L, int* kot_tiles) {
-        if (sizeof(T) != 2 || L.k != 3) return nullptr;
-        return pick_board(plan(), L.ko_pad, kot_tiles, flags_.board_kot);
-    }
-
-    // Does this layer of the persistent launch get the generated epilogue (tower_seam.py epi_hook)?  Then its weights and bias go
-    // in board_row_channel order and BoardParams::row_order says so.  What the generated text covers: Mish / ReLU / no activation, one sample per tile
-    // with computed table entries (arith), the layer's channels = the channel tile, an even number of row tiles per wave.
-    bool board_row_order_ok(const ConvLayerDev& L, const BoardEntry* be, const BoardParams& bp, int act) const {
-        return flags_.tower_gen_epi && tower_ok(be->kot) && !bp.dbg && board_uses_row_order(be->kot) && bp.arith &&
-               (act == kMish || act == kReLU || act == kIdentity) &&
-               L.cout_s == be->kot && L.ko_pad == be->kot && L.w_board && L.bias_board;
+    const ConvRoute& route(const ConvLayerDev& L) {
+        const BoardPlan& bp = plan();
+        auto it = route_cache_.find(L.k * 65536 + L.ko_pad);
+        if (it == route_cache_.end())
+            it = route_cache_.emplace(L.k * 65536 + L.ko_pad, route_conv(sizeof(T) == 2, L.k, L.ko_pad, geom_, bp, flags_.conv, flags_.board_kot)).first;
+        return it->second;
     }
 
     // The last step of a board convolution (conv, conv_se) once its parameters are built: it joins the pending persistent run
     // (to_run), or ends that run and is launched now -- `fn` with sp.b, or be->fn_se with sp when has_se.  Outside a chained
-    // forward the layer takes the row-order weights wherever the generated epilogue covers it.
+    // forward the layer takes the row-order weights wherever the generated epilogue covers it (board_row_order_ok).
     int board_launch(Fwd& f, const char* name, const ConvLayerDev& L, const BoardEntry* be, BoardFn fn, BoardSeParams& sp, bool has_se,
                      bool to_run, int grid, double flops, double bytes) {
         BoardParams& bp = sp.b;
         ConvParams& p = bp.c;
-        if (!f.chained && board_row_order_ok(L, be, bp, p.act)) { p.w = L.w_board; p.bias = L.bias_board; bp.row_order = 1; }
+        if (!f.chained && tower_ok(be->kot) && L.w_board && L.bias_board && board_row_order_ok(bp, be->kot, flags_.tower_gen_epi)) {
+            p.w = L.w_board; p.bias = L.bias_board; bp.row_order = 1;
+        }
         // a pending run this layer does not join ends here (a launch = an ordered point: the table starts afresh)
         if (!f.run.empty() && !(to_run && f.run_kot == be->kot) && tower_flush(f)) return -1;
         if (rows_use(f, p, name)) return -1;
@@ -1132,12 +1074,11 @@ private:
     // (conv_board.h).  Returns 1 when the fused kernel does not apply (the caller then runs conv + se_unit), 0 / -1.
     int conv_se(Fwd& f, const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const T* in, T* out, const T* res, int C, int act) {
         const bool off = !flags_.se_fused;
-        int bkt = 0;
         const BoardEntry* be = nullptr;
         // the variant whose channel tile covers the whole layer, whatever the batch size: a position's result must not
         // depend on how many others share its batch (a small batch would otherwise pick two half-width workgroups and
         // the separate SE kernels, which round x to fp16 before pooling)
-        if (!off && choose_board(L, &bkt))
+        if (!off && route(L).board)
             for (const auto& e : kBoardEntries)
                 if (e.fn_se && e.kot == L.ko_pad && e.lds(board_plan_.npos) <= kMaxLds) be = &e;
         if (!be || C > be->kot) return 1;
@@ -1184,8 +1125,7 @@ private:
     int conv_sx(Fwd& f, const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const T* in, T* out, const T* res, int C, int act) {
         if constexpr (sizeof(T) != 2) return 1;
         if (!flags_.se_split || sx_disabled_ || !sq.sx_img || !ex.sx_img || !sx_kts_ || L.ko_pad != sx_kts_ * 128 || L.cout_s != L.ko_pad) return 1;
-        int bkt = 0;
-        if (!choose_board(L, &bkt)) return 1;
+        if (!route(L).board) return 1;
         const BoardEntry* be = nullptr;
         for (const auto& e : kBoardEntries)
             if (e.kot == 128 && e.lds(board_plan_.npos) <= kMaxLds) be = &e;
@@ -1231,8 +1171,9 @@ private:
     }
 
     int conv(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
-        int bkt = 0;
-        if (const BoardEntry* be = choose_board(L, &bkt)) {
+        const ConvRoute& r = route(L);
+        if (const BoardEntry* be = r.board) {
+            const int bkt = r.tiles;
             const BoardTabs* tabs = nullptr;
             if (board_tabs(f, &tabs)) return -1;
             BoardSeParams sp;
@@ -1261,24 +1202,19 @@ private:
             return board_launch(f, name, L, be, fn, sp, false, to_run, f.ntiles * bkt, cost.flops, cost.bytes);
         }
         if (f.chained) return fail(std::string("chained forward: layer ") + name + " has no board kernel");
-        if (const GldsChoice* gc = choose_glds(L)) {
+        if (const GldsEntry* ge = r.glds) {
             const TileTabs* tabs = nullptr;
-            if (tile_tabs(f, *gc->e, &tabs)) return -1;
+            if (tile_tabs(f, *ge, &tabs)) return -1;
             GldsParams gp;
-            gp.tab_src = tabs->src;
-            gp.tab_pix = tabs->pix;
-            ConvParams& p = gp.c;
-            conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
-            p.npos = 0; p.num_pix_tiles = gc->ntiles;
-            gp.zeros = d_zeros_;
+            conv_params(gp.c, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+            const int grid = glds_params(gp, *ge, tabs->src, tabs->pix, d_zeros_, r.tiles);
             const ConvCost cost = conv_cost(geom_.total, L.cin, L.cout, 9, res, sizeof(T));
-            const auto fn = gc->e->fn;
-            const size_t lds = gc->e->lds;
-            const int grid = gc->ntiles * (L.ko_pad / (gc->e->wmt * 32));
+            const auto fn = ge->fn;
+            const size_t lds = ge->lds;
             return timed(f, name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, f.stream, gp); });
         }
         const int kot = L.wmt * 32, kot_tiles = L.ko_pad / kot;
-        TileChoice tc;
+        TileChoice<T> tc;
         if (choose_tile(L.wmt, kot_tiles, &tc)) return -1;
         ConvParams p;
         conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, L.k * L.k, act);
@@ -1304,29 +1240,9 @@ private:
 
     // the unit on the samples [n0, n0 + ns) of the batch
     int se_unit(Fwd& f, const FcLayerDev& sq, const FcLayerDev& ex, T* x, const T* res, int C, int cs, int act, int n0, int ns) {
-        const BatchGeom g = dgeom(f.io);
         const double px = geom_.off[n0 + ns] - geom_.off[n0];
-        constexpr int EPP = ElemTraits<T>::kPieceElems;
-        if (cs / EPP > 256) return fail("SE unit: more than 256*8 channels is not supported");
-        float *separt = f.io.separt, *gate = f.io.gate;
-        if (timed(f, "se_pool", 2.0 * px * C, sizeof(T) * px * C, [&] {
-                hipLaunchKernelGGL(se_pool_kernel<T>, dim3(ns * kSeSplit), dim3(256), 0, f.stream, (const T*)x,
-                                   separt, g, cs, n0);
-            }))
-            return -1;
-        const size_t smem = sizeof(float) * (3 * C + sq.out + kSeFcThreads);
-        if (timed(f, "se_fc", 2.0 * ns * ((double)sq.in * sq.out + (double)ex.in * ex.out),
-                  4.0 * ns * ((double)sq.in * sq.out + (double)ex.in * ex.out), [&] {
-                      hipLaunchKernelGGL(se_fc_kernel, dim3(ns), dim3(kSeFcThreads), smem, f.stream,
-                                         (const float*)separt, gate, g, C, cs, sq.dev(), ex.dev(), act, n0);
-                  }))
-            return -1;
-        const int ppr = cs / EPP;
-        const dim3 grid((slot_pix_ * ppr + 256 * kScaleUnroll - 1) / (256 * kScaleUnroll), ns);
-        return timed(f, "se_scale", 3.0 * px * C, sizeof(T) * px * C * 3, [&] {
-            hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, f.stream, (const T*)x, res, x,
-                               (const float*)gate, g, C, cs, act, n0);
-        });
+        return se_unit_launches<T>(f.stream, dgeom(f.io), px, x, res, f.io.separt, f.io.gate, sq.dev(), ex.dev(), C, cs, act, n0, ns,
+                                   [&](const char* name, double flops, double bytes, auto&& launch) { return timed(f, name, flops, bytes, launch); });
     }
 
     // -------------------------------------------------------------- who may write which bytes when (the buffer table)
@@ -1546,19 +1462,11 @@ private:
         const int Cp = d.policy_head_channels, Cv = d.value_head_channels;
         T* const* buf = f.io.bufs;
         const BatchGeom g = dgeom(f.io);
-        HeadParams h;
-        h.p_inter = fc(SAYURI_L_P_INTER_FC).dev();
-        h.pass_fc = fc(SAYURI_L_PASS_FC).dev();
-        h.v_inter = fc(SAYURI_L_V_INTER_FC).dev();
-        h.v_misc = fc(SAYURI_L_V_MISC).dev();
-        h.prob_w = cv(SAYURI_L_PROB_CONV).w32;
-        h.prob_b = cv(SAYURI_L_PROB_CONV).bias;
-        h.own_w = cv(SAYURI_L_V_OWNERSHIP).w32;
-        h.own_b = cv(SAYURI_L_V_OWNERSHIP).bias;
-        h.Cp = Cp; h.cs_p = round_up(Cp, 32); h.Cv = Cv; h.cs_v = round_up(Cv, 32);
-        h.prob_ch = d.probabilities_channels; h.act = act; h.board = board_;
-        h.prob = f.io.prob; h.pass = f.pass; h.misc = f.misc; h.own = f.io.own; h.perm = f.io.g_perm;
-        if (head_img_ && heads_fused_enabled()) {
+        const ConvLayerDev &pw = cv(SAYURI_L_PROB_CONV), &ow = cv(SAYURI_L_V_OWNERSHIP);
+        const HeadWeights hw{fc(SAYURI_L_P_INTER_FC).dev(), fc(SAYURI_L_PASS_FC).dev(), fc(SAYURI_L_V_INTER_FC).dev(), fc(SAYURI_L_V_MISC).dev(),
+                             pw.w32, pw.bias, ow.w32, ow.bias};
+        const HeadParams h = head_params(hw, Cp, Cv, d.probabilities_channels, act, board_, f.io.prob, f.pass, f.misc, f.io.own, f.io.g_perm);
+        if (head_img_ && flags_.heads_fused) {
             // both heads of a sample in one workgroup: trunk -> LDS -> stacked 1x1 convolution on the matrix cores -> pooling,
             // FCs and the per-pixel planes (head_board.h)
             HeadBoardParams hp;
@@ -1738,7 +1646,7 @@ private:
     hipEvent_t tick_ev_[2] = {nullptr, nullptr};
     HostGeom geom_;
     std::vector<int> prev_bsz_;
-    std::map<int, GldsChoice> glds_cache_;
+    std::map<int, ConvRoute> route_cache_;  // by (k, ko_pad), for the current batch geometry
     BoardPlan board_plan_;
     HeadFn head_fn_ = nullptr;
     void* head_img2_ = nullptr;  // per-pixel weights (policy planes, ownership) as an MFMA image
@@ -1750,7 +1658,7 @@ private:
     unsigned long long* d_sxdbg_ = nullptr;  // SAYURI_SX_DBG timeline of one split SE convolution
     bool dbg_is_se_ = false;
     bool board_plan_valid_ = false;
-    std::map<int, TileChoice> tile_cache_;
+    std::map<int, TileChoice<T>> tile_cache_;
     std::map<std::string, Stat> stats_;
     // light per-launch timing of one kernel class inside time_runs()
     bool light_ = false;

@@ -1,12 +1,13 @@
 // engine_plan.h -- what the engine decides on the host before anything is launched: the kernel registries, the switches read
-// from the environment, the batch geometry and the tile plans, the layers' device images, the tower code object's loader.
+// from the environment, the batch geometry, the tile plans and the routing of a convolution to its kernel family, the launch
+// parameters and the layers' device images that Engine<T> and the layer-level test taps share, the tower code object's loader.
 // (One translation unit: engine.hip includes engine_plan.h, engine_graph.h and engine_taps.h in this order.)
 #pragma once
 namespace sayuri {
 
 static thread_local std::string g_err;
 static std::atomic<unsigned> g_host_free_gen{0};  // sayuri_hip_host_free calls so far (Engine::zc_device_pointer)
-static thread_local int g_test_conv_kind = 0;  // kernel family the last sayuri_hip_test_conv call ran: 0 generic, 1 glds, 2 board, 3 depthwise
+static thread_local int g_test_conv_kind = 0;  // kernel family (ConvFamily) the last sayuri_hip_test_conv call ran
 static int fail(const std::string& m) { g_err = m; return -1; }
 
 #define HIP_OK(expr)                                                                      \
@@ -79,12 +80,13 @@ static void register_all_glds() {
 }
 // The weight image of the board kernels with an even tile count: the same planes with their rows in board_row_channel order
 // (conv_board.h: a lane then holds 8 consecutive channels of a row-tile pair without any exchange).
-template <typename T> static std::vector<T> board_row_order(const std::vector<T>& img, int ko_pad) {
+// `row` = elements per row: 8 for the image, 1 for the bias that goes with it.
+template <typename T> static std::vector<T> board_row_order(const std::vector<T>& img, int ko_pad, int row = 8) {
     std::vector<T> out(img.size());
-    const size_t planes = img.size() / ((size_t)ko_pad * 8);
+    const size_t planes = img.size() / ((size_t)ko_pad * row);
     for (size_t pl = 0; pl < planes; ++pl)
         for (int r = 0; r < ko_pad; ++r)
-            std::copy_n(img.begin() + (pl * ko_pad + board_row_channel(r)) * 8, 8, out.begin() + (pl * ko_pad + r) * 8);
+            std::copy_n(img.begin() + (pl * ko_pad + board_row_channel(r)) * row, row, out.begin() + (pl * ko_pad + r) * row);
     return out;
 }
 static bool board_uses_row_order(int kot) { return (kot / 64) % 2 == 0; }  // 256 / 128: yes; 192 (three row tiles per wave): natural order
@@ -217,12 +219,6 @@ static int pick_wmt(int cout_s, bool fp16) {
 struct HostGeom {
     std::vector<int> bsz, off;  // off has n+1 entries
     int n = 0, total = 0;
-    // bs*bs when every sample has the same board size, else 0
-    int uniform_sq() const {
-        for (int i = 1; i < n; ++i)
-            if (bsz[i] != bsz[0]) return 0;
-        return n > 0 ? bsz[0] * bsz[0] : 0;
-    }
     // worst-case LDS halo positions / subregions of any PT-pixel tile
     void tile_bounds(int PT, int* npos_out, int* nsub_out) const {
         int max_pos = 0, max_sub = 0;
@@ -246,6 +242,32 @@ struct HostGeom {
     }
 };
 
+// A kernel variant with PT-pixel tiles across samples fits this geometry: the worst tile's halo positions (*npos, what its
+// LDS is sized by) and samples.  Its cost: rounds of workgroups over the CUs times the time of a tile.
+static bool tile_fits(const HostGeom& geom, int PT, int npos_cap, int* npos) {
+    int nsub;
+    geom.tile_bounds(PT, npos, &nsub);
+    return *npos <= npos_cap && nsub <= kMaxSub;
+}
+static double tile_cost(const HostGeom& geom, int PT, int kot_tiles, int* ntiles) {
+    *ntiles = (geom.total + PT - 1) / PT;
+    return std::ceil((double)*ntiles * kot_tiles / kNumCU) * (PT + 24);
+}
+// The generic conv_mfma variant of channel tile `wmt` for this geometry: the cheapest that fits, or -- `widest`, the test
+// taps -- the one with the widest pixel tile.  false: none fits.
+template <typename T> struct TileChoice { int wnt, npos, ntiles; const typename ConvKernelTable<T>::Entry* e; };
+template <typename T> static bool pick_tile(const HostGeom& geom, int wmt, int kot_tiles, bool widest, TileChoice<T>* out) {
+    double best = 0;
+    out->e = nullptr;
+    for (const auto& e : ConvKernelTable<T>::entries()) {
+        int npos, ntiles;
+        if (e.wmt != wmt || !tile_fits(geom, 64 * e.wnt, e.npos_cap, &npos) || e.lds(npos) > kMaxLds) continue;
+        const double cost = tile_cost(geom, 64 * e.wnt, kot_tiles, &ntiles), score = widest ? -e.wnt : cost;
+        if (!out->e || score < best) { best = score; *out = TileChoice<T>{e.wnt, npos, ntiles, &e}; }
+    }
+    return out->e != nullptr;
+}
+
 // Choose the tuned LDS-DMA kernel variant for an fp16 3x3 layer with `ko_pad` weight rows on
 // this batch geometry; nullptr when none applies (the generic conv_mfma kernel is used then).
 static const GldsEntry* pick_glds(const HostGeom& geom, int ko_pad, int* ntiles_out, const ConvOverride& ov) {
@@ -258,13 +280,9 @@ static const GldsEntry* pick_glds(const HostGeom& geom, int ko_pad, int* ntiles_
     for (const auto& e : glds_entries()) {
         if (e.wmt != wmt) continue;
         if (ov.wnt && e.wnt != ov.wnt) continue;
-        const int PT = e.pt;
-        int npos, nsub;
-        geom.tile_bounds(PT, &npos, &nsub);
-        if (npos > e.npos_cap || nsub > kMaxSub || e.lds > kMaxLds) continue;
-        const int ntiles = (geom.total + PT - 1) / PT;
-        const double waves = std::ceil((double)ntiles * kot_tiles / kNumCU);
-        const double cost = waves * (PT + 24);
+        int npos, ntiles;
+        if (!tile_fits(geom, e.pt, e.npos_cap, &npos) || e.lds > kMaxLds) continue;
+        const double cost = tile_cost(geom, e.pt, kot_tiles, &ntiles);
         if (cost < best_cost) { best_cost = cost; best = &e; *ntiles_out = ntiles; }
     }
     return best;
@@ -322,6 +340,24 @@ static const BoardEntry* pick_board(const BoardPlan& bp, int ko_pad, int* kot_ti
     }
     return best;
 }
+// Which kernel runs a k x k convolution with `ko_pad` weight rows on this geometry (`plan` = board_plan(geom, ov)): fp16 3x3
+// layers one workgroup per board (`board`, `tiles` channel tiles per board tile), else the LDS-DMA tiles across samples
+// (`glds`, `tiles` pixel tiles), everything else the generic conv_mfma kernel (pick_tile).  The values are what
+// sayuri_hip_test_last_conv_kind reports.
+enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3 };
+struct ConvRoute {
+    ConvFamily family = kConvGeneric;
+    const BoardEntry* board = nullptr;
+    const GldsEntry* glds = nullptr;
+    int tiles = 0;
+};
+static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, const BoardPlan& plan, const ConvOverride& ov, int force_kot = 0) {
+    ConvRoute r;
+    if (!fp16 || k != 3) return r;
+    if ((r.board = pick_board(plan, ko_pad, &r.tiles, force_kot))) r.family = kConvBoard;
+    else if ((r.glds = pick_glds(geom, ko_pad, &r.tiles, ov))) r.family = kConvGlds;
+    return r;
+}
 
 // ------------------------------------------------------------------ the parameters of one 3x3 / 1x1 convolution launch
 // Shared by Engine<T> and the layer-level test taps.  conv_params fills every field but npos and num_pix_tiles (the kernel
@@ -343,6 +379,21 @@ static void board_params(BoardParams& bp, const BoardPlan& plan, const int* tab_
     bp.uniform_info = plan.uniform_info;
     bp.arith = plan.single && plan.uniform_info >= 0 && arith ? 1 : 0;
 }
+// Does a layer of the persistent launch get the generated epilogue (tower_seam.py epi_hook)?  Then its weights and bias go in
+// board_row_channel order and BoardParams::row_order says so.  What the generated text covers (`gen_epi`: SAYURI_TOWER_GEN_EPI):
+// Mish / ReLU / no activation, one sample per tile with computed table entries (arith), the layer's channels = the channel tile
+// `kot`, an even number of row tiles per wave.  bp.c filled (conv_params).
+static bool board_row_order_ok(const BoardParams& bp, int kot, bool gen_epi) {
+    const ConvParams& p = bp.c;
+    return gen_epi && !bp.dbg && board_uses_row_order(kot) && bp.arith && (p.act == kMish || p.act == kReLU || p.act == kIdentity) &&
+           p.cout_s == kot && p.ko_pad == kot;
+}
+// The across-sample kernel's part of a launch of `e` over `ntiles` pixel tiles (conv_params has filled gp.c); returns the grid.
+static int glds_params(GldsParams& gp, const GldsEntry& e, const int* tab_src, const int2* tab_pix, const float* zeros, int ntiles) {
+    gp.tab_src = tab_src; gp.tab_pix = tab_pix; gp.zeros = zeros;
+    gp.c.npos = 0; gp.c.num_pix_tiles = ntiles;
+    return ntiles * (gp.c.ko_pad / (e.wmt * 32));
+}
 // What a convolution over `px` pixels computes and moves (the flops / bytes of the profile rows and of bench.py's
 // tower_conv_mfma_frac): the activations in, out (and the residual), the weights once.
 struct ConvCost { double flops, bytes; };
@@ -359,7 +410,7 @@ struct Stat {
 // ------------------------------------------------------------------ layers
 struct ConvLayerDev {
     int cin = 0, cout = 0, k = 0;
-    bool depthwise = false, with_bn_fold = false;
+    bool depthwise = false;
     std::vector<float> hw, hb;  // host tensors as handed over the ABI
     int cin_s = 0, cout_s = 0, wmt = 0, ko_pad = 0;
     void* w = nullptr;      // MFMA image, or [k*k][cs] fp32 for depthwise
@@ -381,6 +432,41 @@ struct FcLayerDev {
 };
 
 // ------------------------------------------------------------------ host-side images shared by the engine and the test taps
+// A 1x1 / 3x3 layer's output-channel tile (32 * wmt) and its weight rows padded to whole tiles.
+static void conv_tile(int cout_s, bool fp16, int* wmt, int* ko_pad) {
+    *wmt = pick_wmt(cout_s, fp16);
+    *ko_pad = round_up(cout_s, *wmt * 32);
+}
+// Its MFMA image [tap][chunk of 32 input channels][k-group of 8][ko_pad][8] out of w [cout][cin][taps] (conv_mfma.h), ...
+template <typename T> static std::vector<T> conv_image(const float* w, int cin, int cout, int taps, int ko_pad) {
+    const int nch = round_up(cin, 32) / 32;
+    std::vector<T> img((size_t)taps * nch * 4 * ko_pad * 8, (T)0.f);
+    for (int t = 0; t < taps; ++t)
+        for (int ko = 0; ko < cout; ++ko)
+            for (int c = 0; c < cin; ++c)
+                img[((((size_t)t * nch + c / 32) * 4 + (c % 32) / 8) * ko_pad + ko) * 8 + c % 8] = (T)w[((size_t)ko * cin + c) * taps + t];
+    return img;
+}
+// ... and a layer's bias padded with zeros to `n_pad` entries (b == null: no bias).
+static std::vector<float> padded_bias(const float* b, int n, int n_pad) {
+    std::vector<float> out(n_pad, 0.f);
+    if (b) std::copy(b, b + n, out.begin());
+    return out;
+}
+// A depthwise layer's weights [c][taps] -> [tap][cout_s] (depthwise_kernel, small_ops.h).
+static std::vector<float> depthwise_image(const float* w, int cout, int taps, int cout_s) {
+    std::vector<float> wt((size_t)taps * cout_s, 0.f);
+    for (int c = 0; c < cout; ++c)
+        for (int t = 0; t < taps; ++t) wt[(size_t)t * cout_s + c] = w[(size_t)c * taps + t];
+    return wt;
+}
+static std::vector<float> fc_transposed(const float* w, int in, int out) {  // [out][in] -> [in][out] (FcDev::wt)
+    std::vector<float> t((size_t)in * out);
+    for (int o = 0; o < out; ++o)
+        for (int i = 0; i < in; ++i) t[(size_t)i * out + o] = w[(size_t)o * in + i];
+    return t;
+}
+
 // fp16 images of an SE unit's two FCs for the LDS staging of board_se_stage (conv_board.h, BoardSeParams::w1h / w2h):
 // the squeeze weights once per board size 2..board with the scaled-mean third of the pooled vector folded into the mean
 // third (reference GlobalPooling<false>, se_unit.cc:9-40: pool = (mean, mean * (B-14)/10, max)), the excite weights with
@@ -495,6 +581,43 @@ static HeadFn make_head_images(int C, int Cp, int Cv, int prob_ch, int board, co
     out->PT = PT;
     out->VT = VT;
     return fn;
+}
+
+// ------------------------------------------------------------------ launches shared by the engine and the test taps
+// The parameters of the head kernels (head_tail_kernel, head_board_kernel): the device weights of the four FCs and of the two
+// per-pixel convolutions, the dimensions, where the four outputs go (perm: device sample -> caller's slot, null = identity).
+struct HeadWeights {
+    FcDev p_inter, pass_fc, v_inter, v_misc;
+    const float *prob_w, *prob_b, *own_w, *own_b;
+};
+static HeadParams head_params(const HeadWeights& w, int Cp, int Cv, int prob_ch, int act, int board, float* prob, float* pass, float* misc,
+                              float* own, const int* perm) {
+    HeadParams h{};
+    h.p_inter = w.p_inter; h.pass_fc = w.pass_fc; h.v_inter = w.v_inter; h.v_misc = w.v_misc;
+    h.prob_w = w.prob_w; h.prob_b = w.prob_b; h.own_w = w.own_w; h.own_b = w.own_b;
+    h.Cp = Cp; h.cs_p = round_up(Cp, 32); h.Cv = Cv; h.cs_v = round_up(Cv, 32); h.prob_ch = prob_ch; h.act = act; h.board = board;
+    h.prob = prob; h.pass = pass; h.misc = misc; h.own = own; h.perm = perm;
+    return h;
+}
+// The SE unit as three kernels on the samples [n0, n0 + ns) (`px` pixels) of x, in place: se_pool -> se_fc -> se_scale.  Each
+// launch goes through run(name, flops, bytes, launch): the engine's timed(), or a plain call (the test tap).
+template <typename T, typename Run>
+static int se_unit_launches(hipStream_t s, const BatchGeom& g, double px, T* x, const T* res, float* separt, float* gate, const FcDev& sq,
+                            const FcDev& ex, int C, int cs, int act, int n0, int ns, Run&& run) {
+    constexpr int EPP = ElemTraits<T>::kPieceElems;
+    if (cs / EPP > 256) return fail("SE unit: more than 256*8 channels is not supported");
+    const double fc = (double)sq.in * sq.out + (double)ex.in * ex.out;
+    if (run("se_pool", 2.0 * px * C, sizeof(T) * px * C,
+            [&] { hipLaunchKernelGGL(se_pool_kernel<T>, dim3(ns * kSeSplit), dim3(256), 0, s, (const T*)x, separt, g, cs, n0); }))
+        return -1;
+    const size_t smem = sizeof(float) * (3 * C + sq.out + kSeFcThreads);
+    if (run("se_fc", 2.0 * ns * fc, 4.0 * ns * fc, [&] {
+            hipLaunchKernelGGL(se_fc_kernel, dim3(ns), dim3(kSeFcThreads), smem, s, (const float*)separt, gate, g, C, cs, sq, ex, act, n0);
+        }))
+        return -1;
+    const dim3 grid((g.slot_pix * (cs / EPP) + 256 * kScaleUnroll - 1) / (256 * kScaleUnroll), ns);
+    return run("se_scale", 3.0 * px * C, sizeof(T) * px * C * 3,
+               [&] { hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, s, (const T*)x, res, x, (const float*)gate, g, C, cs, act, n0); });
 }
 
 // the persistent tower kernels (conv_tower.h) out of the embedded code object: [0] 256-channel tile, [1] 128-channel tile

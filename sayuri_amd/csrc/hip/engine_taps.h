@@ -1,197 +1,10 @@
 // engine_taps.h -- layer-level test taps of the C-ABI (sayuri_hip_test_*): one kernel family at a time on host tensors, for the
-// parity tests (tests/test_gpu_layers.py, test_gpu_smallops.py).  Not used by the pipe.
+// parity tests (tests/test_gpu_layers.py, test_gpu_smallops.py).  Not used by the pipe.  A tap converts the layouts on the host,
+// in and out, and launches ONE layer; the device images, the routing of a convolution to its kernel family and the launch
+// parameters are the engine's own code (engine_plan.h), so the tests check the host code the engine runs.
 #pragma once
 #include "engine_graph.h"
 
-// ---------------------------------------------------------------------- layer-level test tap
-// Drives ONE convolution kernel directly (host-side layout conversion in, out) so the parity
-// tests can localise a defect to a layer kind.
-
-namespace sayuri {
-
-template <typename T>
-static int test_conv_impl(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int k,
-                          int depthwise, int act, int post_residual, const float* x, const float* w, const float* bias,
-                          const float* res, float* y) {
-    HIP_OK(hipSetDevice(device));
-    enable_big_lds<T>();
-    HostGeom hg;
-    hg.n = n;
-    hg.bsz.assign(board_sizes, board_sizes + n);
-    hg.off.resize(n + 1);
-    hg.off[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        if (hg.bsz[i] < 2 || hg.bsz[i] > max_board) return fail("test_conv: bad board size");
-        hg.off[i + 1] = hg.off[i] + hg.bsz[i] * hg.bsz[i];
-    }
-    hg.total = hg.off[n];
-    const int slot = max_board * max_board;
-    const int cin_s = round_up(depthwise ? cout : cin, 32), cout_s = round_up(cout, 32);
-    std::vector<void*> allocs;
-    auto cleanup = [&] { for (void* p : allocs) (void)hipFree(p); };
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
-        (void)hipMemset(p, 0, std::max<size_t>(bytes, 256));
-        allocs.push_back(p);
-        return p;
-    };
-    // host NCHW (compact per sample) -> compact NHWC
-    auto to_nhwc = [&](const float* src, int C, int cs) {
-        std::vector<T> h((size_t)n * slot * cs, (T)0.f);
-        size_t so = 0;
-        for (int i = 0; i < n; ++i) {
-            const int S = hg.bsz[i] * hg.bsz[i];
-            for (int c = 0; c < C; ++c)
-                for (int p = 0; p < S; ++p) h[((size_t)i * slot + p) * cs + c] = (T)src[so + (size_t)c * S + p];
-            so += (size_t)C * S;
-        }
-        return h;
-    };
-    const int xin_c = depthwise ? cout : cin;
-    std::vector<T> hx = to_nhwc(x, xin_c, cin_s);
-    T* dx = (T*)dalloc(hx.size() * sizeof(T) + kZeroPrefix);
-    if (dx) dx += kZeroPrefix / sizeof(T);  // conv_board.h reads its halo cells from a zero prefix in front of the activations
-    T* dy = (T*)dalloc((size_t)n * slot * cout_s * sizeof(T));
-    T* dres = nullptr;
-    if (!dx || !dy) { cleanup(); return fail("test_conv: hipMalloc failed"); }
-    HIP_OK(hipMemcpy(dx, hx.data(), hx.size() * sizeof(T), hipMemcpyHostToDevice));
-    if (res) {
-        std::vector<T> hr = to_nhwc(res, cout, cout_s);
-        dres = (T*)dalloc(hr.size() * sizeof(T));
-        if (!dres) { cleanup(); return fail("test_conv: hipMalloc failed"); }
-        HIP_OK(hipMemcpy(dres, hr.data(), hr.size() * sizeof(T), hipMemcpyHostToDevice));
-    }
-    int* d_off = (int*)dalloc(sizeof(int) * (n + 1));
-    int* d_bsz = (int*)dalloc(sizeof(int) * n);
-    HIP_OK(hipMemcpy(d_off, hg.off.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_bsz, hg.bsz.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-    const BatchGeom g{d_off, d_bsz, n, hg.total, slot};
-
-    if (depthwise) {
-        g_test_conv_kind = 3;
-        const int kk = k * k;
-        std::vector<float> wt((size_t)kk * cout_s, 0.f), b(cout_s, 0.f);
-        for (int c = 0; c < cout; ++c) {
-            for (int t = 0; t < kk; ++t) wt[(size_t)t * cout_s + c] = w[(size_t)c * kk + t];
-            b[c] = bias ? bias[c] : 0.f;
-        }
-        float* dw = (float*)dalloc(wt.size() * 4);
-        float* db = (float*)dalloc(b.size() * 4);
-        HIP_OK(hipMemcpy(dw, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(db, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-        const int EPP = ElemTraits<T>::kPieceElems;
-        const size_t total = (size_t)hg.total * (cout_s / EPP);
-        hipLaunchKernelGGL(depthwise_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, (const T*)dx,
-                           post_residual ? (const T*)dres : (const T*)nullptr, dy, (const float*)dw, (const float*)db, g,
-                           cout, cout_s, k, act);
-    } else {
-        const int wmt = pick_wmt(cout_s, sizeof(T) == 2);
-        const int kot = wmt * 32, ko_pad = round_up(cout_s, kot), taps = k * k, nch = cin_s / 32;
-        std::vector<T> img((size_t)taps * nch * 4 * ko_pad * 8, (T)0.f);
-        for (int t = 0; t < taps; ++t)
-            for (int ch = 0; ch < nch; ++ch)
-                for (int kg = 0; kg < 4; ++kg)
-                    for (int ko = 0; ko < cout; ++ko)
-                        for (int e = 0; e < 8; ++e) {
-                            const int c = ch * 32 + kg * 8 + e;
-                            if (c >= cin) continue;
-                            img[((((size_t)t * nch + ch) * 4 + kg) * ko_pad + ko) * 8 + e] =
-                                (T)w[((size_t)ko * cin + c) * taps + t];
-                        }
-        std::vector<float> b(ko_pad, 0.f);
-        if (bias) std::copy(bias, bias + cout, b.begin());
-        T* dw = (T*)dalloc(img.size() * sizeof(T));
-        float* db = (float*)dalloc(b.size() * 4);
-        HIP_OK(hipMemcpy(dw, img.data(), img.size() * sizeof(T), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(db, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-        int g_ntiles = 0;
-        const GldsEntry* ge = nullptr;
-        bool board_done = false;
-        if (sizeof(T) == 2 && k == 3) {
-            enable_big_lds_glds();
-            const BoardPlan plan = board_plan(hg, EngineFlags::from_env().conv);
-            int kot_tiles = 0;
-            const BoardEntry* be = pick_board(plan, ko_pad, &kot_tiles);
-            if (be) {
-                int* tsrc = (int*)dalloc(sizeof(int) * (size_t)plan.ntiles * plan.npos);
-                int2* tpix = (int2*)dalloc(sizeof(int2) * (size_t)plan.ntiles * kBoardPT);
-                int* tcols = (int*)dalloc(sizeof(int) * (size_t)plan.ntiles);
-                if (!tsrc || !tpix || !tcols) { cleanup(); return fail("test_conv: hipMalloc failed"); }
-                hipLaunchKernelGGL(board_setup_kernel, dim3(plan.ntiles), dim3(256), 0, 0, g, plan.npos, tsrc, tpix, tcols);
-                BoardParams bp;
-                board_params(bp, plan, tsrc, tpix, tcols, true);
-                ConvParams& p = bp.c;
-                conv_params(p, dx, dw, db, dres, dy, g, cin_s, cout_s, ko_pad, 9, act);
-                p.npos = 0; p.num_pix_tiles = plan.ntiles;
-                hipLaunchKernelGGL(be->fn, dim3(plan.ntiles * kot_tiles), dim3(512), be->lds(plan.npos), 0, bp);
-                HIP_OK(hipGetLastError());
-                HIP_OK(hipDeviceSynchronize());
-                board_done = true;
-                g_test_conv_kind = 2;
-            }
-        }
-        if (sizeof(T) == 2 && k == 3 && !board_done) {
-            enable_big_lds_glds();
-            ge = pick_glds(hg, ko_pad, &g_ntiles, EngineFlags::from_env().conv);
-        }
-        if (ge) {
-            float* dz = (float*)dalloc(256);
-            int* tsrc = (int*)dalloc(sizeof(int) * (size_t)g_ntiles * ge->npos);
-            int2* tpix = (int2*)dalloc(sizeof(int2) * (size_t)g_ntiles * ge->pt);
-            if (!dz || !tsrc || !tpix) { cleanup(); return fail("test_conv: hipMalloc failed"); }
-            hipLaunchKernelGGL(ge->setup, dim3(g_ntiles), dim3(256), 0, 0, g, tsrc, tpix);
-            GldsParams gp;
-            gp.tab_src = tsrc;
-            gp.tab_pix = tpix;
-            ConvParams& p = gp.c;
-            conv_params(p, dx, dw, db, dres, dy, g, cin_s, cout_s, ko_pad, 9, act);
-            p.npos = 0; p.num_pix_tiles = g_ntiles;
-            gp.zeros = dz;
-            hipLaunchKernelGGL(ge->fn, dim3(g_ntiles * (ko_pad / (ge->wmt * 32))), dim3(512), ge->lds, 0, gp);
-            g_test_conv_kind = 1;
-            HIP_OK(hipGetLastError());
-            HIP_OK(hipDeviceSynchronize());
-        }
-        const typename ConvKernelTable<T>::Entry* best = nullptr;
-        int best_npos = 0;
-        for (const auto& e : ConvKernelTable<T>::entries()) {
-            if (ge || board_done) break;
-            if (e.wmt != wmt) continue;
-            int npos, nsub;
-            hg.tile_bounds(64 * e.wnt, &npos, &nsub);
-            if (npos > e.npos_cap || nsub > kMaxSub || e.lds(npos) > kMaxLds) continue;
-            if (!best || e.wnt > best->wnt) { best = &e; best_npos = npos; }
-        }
-        if (!best && !ge && !board_done) { cleanup(); return fail("test_conv: no tile configuration fits"); }
-        if (best) {
-        g_test_conv_kind = 0;
-        ConvParams p;
-        conv_params(p, dx, dw, db, dres, dy, g, cin_s, cout_s, ko_pad, taps, act);
-        p.npos = best_npos;
-        const int PT = 64 * best->wnt;
-        p.num_pix_tiles = (hg.total + PT - 1) / PT;
-        hipLaunchKernelGGL(best->fn, dim3(p.num_pix_tiles * (ko_pad / kot)), dim3(512), best->lds(best_npos), 0, p);
-        }
-    }
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
-    std::vector<T> hy((size_t)n * slot * cout_s);
-    HIP_OK(hipMemcpy(hy.data(), dy, hy.size() * sizeof(T), hipMemcpyDeviceToHost));
-    size_t so = 0;
-    for (int i = 0; i < n; ++i) {
-        const int S = hg.bsz[i] * hg.bsz[i];
-        for (int c = 0; c < cout; ++c)
-            for (int pp = 0; pp < S; ++pp) y[so + (size_t)c * S + pp] = (float)hy[((size_t)i * slot + pp) * cout_s + c];
-        so += (size_t)cout * S;
-    }
-    cleanup();
-    return 0;
-}
-
-}  // namespace sayuri
-
-// ---------------------------------------------------------------------- small-op test taps
 namespace sayuri {
 
 struct TestGeom {
@@ -217,6 +30,13 @@ public:
         if (d && hipMemcpy(d, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
         return d;
     }
+    // activations with the kZeroPrefix zero bytes in front that the board kernels read their halo cells from (conv_board.h)
+    template <typename U> U* upload_prefixed(const std::vector<U>& h) {
+        U* d = (U*)alloc(h.size() * sizeof(U) + kZeroPrefix);
+        if (!d) return nullptr;
+        d += kZeroPrefix / sizeof(U);
+        return hipMemcpy(d, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice) == hipSuccess ? d : nullptr;
+    }
 private:
     std::vector<void*> ptrs_;
 };
@@ -237,7 +57,7 @@ static int make_test_geom(TestArena& A, int n, const int* board_sizes, int max_b
     tg->g = BatchGeom{tg->d_off, tg->d_bsz, n, tg->hg.total, tg->slot};
     return 0;
 }
-// host NCHW (compact per sample) <-> compact NHWC
+// host NCHW (compact per sample) -> compact NHWC with channel stride cs ...
 template <typename T> static std::vector<T> nchw_to_nhwc(const TestGeom& tg, const float* src, int C, int cs) {
     std::vector<T> h((size_t)tg.hg.n * tg.slot * cs, (T)0.f);
     size_t so = 0;
@@ -249,11 +69,96 @@ template <typename T> static std::vector<T> nchw_to_nhwc(const TestGeom& tg, con
     }
     return h;
 }
-static std::vector<float> fc_transposed(const float* w, int in, int out) {  // [out][in] -> [in][out]
-    std::vector<float> t((size_t)in * out);
-    for (int o = 0; o < out; ++o)
-        for (int i = 0; i < in; ++i) t[(size_t)i * out + o] = w[(size_t)o * in + i];
-    return t;
+// ... and a device tensor of that layout back into host NCHW
+template <typename T> static int nhwc_to_nchw(const TestGeom& tg, const T* dev, int C, int cs, float* dst) {
+    std::vector<T> h((size_t)tg.hg.n * tg.slot * cs);
+    HIP_OK(hipMemcpy(h.data(), dev, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+    size_t so = 0;
+    for (int i = 0; i < tg.hg.n; ++i) {
+        const int S = tg.hg.bsz[i] * tg.hg.bsz[i];
+        for (int c = 0; c < C; ++c)
+            for (int p = 0; p < S; ++p) dst[so + (size_t)c * S + p] = (float)h[((size_t)i * tg.slot + p) * cs + c];
+        so += (size_t)C * S;
+    }
+    return 0;
+}
+// The index tables of the board kernels for `plan` (board_setup_kernel), as board_params takes them.  false: out of memory.
+struct TestBoardTabs { int* src; int2* pix; int* cols; };
+static bool make_board_tabs(TestArena& A, const TestGeom& tg, const BoardPlan& plan, TestBoardTabs* t) {
+    t->src = (int*)A.alloc(sizeof(int) * (size_t)plan.ntiles * plan.npos);
+    t->pix = (int2*)A.alloc(sizeof(int2) * (size_t)plan.ntiles * kBoardPT);
+    t->cols = (int*)A.alloc(sizeof(int) * (size_t)plan.ntiles);
+    if (!t->src || !t->pix || !t->cols) return false;
+    hipLaunchKernelGGL(board_setup_kernel, dim3(plan.ntiles), dim3(256), 0, 0, tg.g, plan.npos, t->src, t->pix, t->cols);
+    return true;
+}
+
+// Drives ONE convolution kernel directly, so the parity tests can localise a defect to a layer kind.
+template <typename T>
+static int test_conv_impl(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int k,
+                          int depthwise, int act, int post_residual, const float* x, const float* w, const float* bias,
+                          const float* res, float* y) {
+    HIP_OK(hipSetDevice(device));
+    enable_big_lds<T>();
+    if (sizeof(T) == 2 && k == 3) enable_big_lds_glds();
+    TestArena A;
+    TestGeom tg;
+    if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
+    const HostGeom& hg = tg.hg;
+    const int cin_s = round_up(depthwise ? cout : cin, 32), cout_s = round_up(cout, 32);
+    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, depthwise ? cout : cin, cin_s));
+    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, cout, cout_s)) : nullptr;
+    T* dy = (T*)A.alloc((size_t)n * tg.slot * cout_s * sizeof(T));
+    if (!dx || !dy || (res && !dres)) return fail("test_conv: hipMalloc failed");
+    if (depthwise) {
+        g_test_conv_kind = kConvDepthwise;
+        const float* dw = A.upload(depthwise_image(w, cout, k * k, cout_s));
+        const float* db = A.upload(padded_bias(bias, cout, cout_s));
+        if (!dw || !db) return fail("test_conv: hipMalloc failed");
+        const size_t total = (size_t)hg.total * (cout_s / ElemTraits<T>::kPieceElems);
+        hipLaunchKernelGGL(depthwise_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, dx, post_residual ? dres : (const T*)nullptr,
+                           dy, dw, db, tg.g, cout, cout_s, k, act);
+    } else {
+        int wmt, ko_pad;
+        conv_tile(cout_s, sizeof(T) == 2, &wmt, &ko_pad);
+        const T* dw = A.upload(conv_image<T>(w, cin, cout, k * k, ko_pad));
+        const float* db = A.upload(padded_bias(bias, cout, ko_pad));
+        if (!dw || !db) return fail("test_conv: hipMalloc failed");
+        const ConvOverride ov = EngineFlags::from_env().conv;
+        const BoardPlan plan = board_plan(hg, ov);
+        const ConvRoute r = route_conv(sizeof(T) == 2, k, ko_pad, hg, plan, ov);
+        g_test_conv_kind = r.family;
+        if (r.board) {
+            TestBoardTabs tabs;
+            if (!make_board_tabs(A, tg, plan, &tabs)) return fail("test_conv: hipMalloc failed");
+            BoardParams bp;
+            board_params(bp, plan, tabs.src, tabs.pix, tabs.cols, true);
+            conv_params(bp.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 9, act);
+            bp.c.npos = 0; bp.c.num_pix_tiles = plan.ntiles;
+            hipLaunchKernelGGL(r.board->fn, dim3(plan.ntiles * r.tiles), dim3(512), r.board->lds(plan.npos), 0, bp);
+        } else if (r.glds) {
+            const float* dz = (const float*)A.alloc(256);
+            int* tsrc = (int*)A.alloc(sizeof(int) * (size_t)r.tiles * r.glds->npos);
+            int2* tpix = (int2*)A.alloc(sizeof(int2) * (size_t)r.tiles * r.glds->pt);
+            if (!dz || !tsrc || !tpix) return fail("test_conv: hipMalloc failed");
+            hipLaunchKernelGGL(r.glds->setup, dim3(r.tiles), dim3(256), 0, 0, tg.g, tsrc, tpix);
+            GldsParams gp;
+            conv_params(gp.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 9, act);
+            const int grid = glds_params(gp, *r.glds, tsrc, tpix, dz, r.tiles);
+            hipLaunchKernelGGL(r.glds->fn, dim3(grid), dim3(512), r.glds->lds, 0, gp);
+        } else {
+            // (deliberately not the engine's choice by cost: the widest pixel tile that fits, which is what the test cases were written to cover)
+            TileChoice<T> tc;
+            if (!pick_tile<T>(hg, wmt, ko_pad / (wmt * 32), /*widest=*/true, &tc)) return fail("test_conv: no tile configuration fits");
+            ConvParams p;
+            conv_params(p, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, k * k, act);
+            p.npos = tc.npos; p.num_pix_tiles = tc.ntiles;
+            hipLaunchKernelGGL(tc.e->fn, dim3(tc.ntiles * (ko_pad / (wmt * 32))), dim3(512), tc.e->lds(tc.npos), 0, p);
+        }
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    return nhwc_to_nchw(tg, dy, cout, cout_s, y);
 }
 
 template <typename T>
@@ -265,8 +170,6 @@ static int test_se_unit_impl(int device, int n, const int* board_sizes, int max_
     TestGeom tg;
     if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
     const int cs = round_up(C, 32);
-    constexpr int EPP = ElemTraits<T>::kPieceElems;
-    if (cs / EPP > 256) return fail("test_se_unit: too many channels");
     T* dx = A.upload(nchw_to_nhwc<T>(tg, x, C, cs));
     T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
     float* dw1 = A.upload(fc_transposed(w1, 3 * C, se));
@@ -276,24 +179,12 @@ static int test_se_unit_impl(int device, int n, const int* board_sizes, int max_
     float* separt = (float*)A.alloc(sizeof(float) * (size_t)n * kSeSplit * 2 * cs);
     float* gate = (float*)A.alloc(sizeof(float) * (size_t)n * 2 * cs);
     if (!dx || (res && !dres) || !dw1 || !dw2 || !db1 || !db2 || !separt || !gate) return fail("test_se_unit: hipMalloc failed");
-    const FcDev sq{dw1, db1, 3 * C, se}, ex{dw2, db2, se, 2 * C};
-    hipLaunchKernelGGL(se_pool_kernel<T>, dim3(n * kSeSplit), dim3(256), 0, 0, (const T*)dx, separt, tg.g, cs);
-    hipLaunchKernelGGL(se_fc_kernel, dim3(n), dim3(kSeFcThreads), sizeof(float) * (3 * C + se + kSeFcThreads), 0, (const float*)separt, gate, tg.g, C, cs, sq,
-                       ex, act);
-    const int ppr = cs / EPP;
-    const dim3 grid((tg.slot * ppr + 256 * kScaleUnroll - 1) / (256 * kScaleUnroll), n);
-    hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, 0, (const T*)dx, (const T*)dres, dx, (const float*)gate, tg.g, C, cs, act);
+    if (se_unit_launches<T>(nullptr, tg.g, tg.hg.total, dx, dres, separt, gate, FcDev{dw1, db1, 3 * C, se}, FcDev{dw2, db2, se, 2 * C}, C, cs, act, 0, n,
+                            [](const char*, double, double, auto&& launch) { launch(); return 0; }))
+        return -1;
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
-    std::vector<T> hy((size_t)n * tg.slot * cs);
-    HIP_OK(hipMemcpy(hy.data(), dx, hy.size() * sizeof(T), hipMemcpyDeviceToHost));
-    size_t so = 0;
-    for (int i = 0; i < n; ++i) {
-        const int S = tg.hg.bsz[i] * tg.hg.bsz[i];
-        for (int c = 0; c < C; ++c)
-            for (int pp = 0; pp < S; ++pp) y[so + (size_t)c * S + pp] = (float)hy[((size_t)i * tg.slot + pp) * cs + c];
-        so += (size_t)C * S;
-    }
+    if (nhwc_to_nchw(tg, dx, C, cs, y)) return -1;
     if (gate_out) {
         std::vector<float> hg((size_t)n * 2 * cs);
         HIP_OK(hipMemcpy(hg.data(), gate, hg.size() * 4, hipMemcpyDeviceToHost));
@@ -306,55 +197,65 @@ static int test_se_unit_impl(int device, int n, const int* board_sizes, int max_
     return 0;
 }
 
+// The twelve head weight tensors of a head tap (`w`: p_inter_w, p_inter_b, pass_w, pass_b, v_inter_w, v_inter_b, v_misc_w, v_misc_b,
+// prob_w, prob_b, own_w, own_b) on the device, as head_params takes them.  false: out of memory.
+static bool upload_head_weights(TestArena& A, const float* const* w, int Cp, int Cv, int prob_ch, int pass_outs, int misc_outs, HeadWeights* hw) {
+    const int in[4] = {3 * Cp, Cp, 3 * Cv, 3 * Cv}, out[4] = {Cp, pass_outs, 3 * Cv, misc_outs};
+    FcDev* fcs[4] = {&hw->p_inter, &hw->pass_fc, &hw->v_inter, &hw->v_misc};
+    for (int i = 0; i < 4; ++i) {
+        *fcs[i] = FcDev{A.upload(fc_transposed(w[2 * i], in[i], out[i])), A.upload(std::vector<float>(w[2 * i + 1], w[2 * i + 1] + out[i])), in[i], out[i]};
+        if (!fcs[i]->wt || !fcs[i]->b) return false;
+    }
+    hw->prob_w = A.upload(std::vector<float>(w[8], w[8] + (size_t)prob_ch * Cp));
+    hw->prob_b = A.upload(std::vector<float>(w[9], w[9] + prob_ch));
+    hw->own_w = A.upload(std::vector<float>(w[10], w[10] + Cv));
+    hw->own_b = A.upload(std::vector<float>(w[11], w[11] + 1));
+    return hw->prob_w && hw->prob_b && hw->own_w && hw->own_b;
+}
+// The four output tensors of a head tap on the device, and their way back to the caller.
+struct TestHeadOut {
+    float *prob = nullptr, *pass = nullptr, *misc = nullptr, *own = nullptr;
+    size_t n_prob, n_pass, n_misc, n_own;
+    bool alloc(TestArena& A, int n, int prob_ch, int pass_outs, int misc_outs, int B2) {
+        n_prob = (size_t)n * prob_ch * B2; n_pass = (size_t)n * pass_outs; n_misc = (size_t)n * misc_outs; n_own = (size_t)n * B2;
+        prob = (float*)A.alloc(sizeof(float) * n_prob);
+        pass = (float*)A.alloc(sizeof(float) * n_pass);
+        misc = (float*)A.alloc(sizeof(float) * n_misc);
+        own = (float*)A.alloc(sizeof(float) * n_own);
+        return prob && pass && misc && own;
+    }
+    int download(float* h_prob, float* h_pass, float* h_misc, float* h_own) const {
+        HIP_OK(hipMemcpy(h_prob, prob, sizeof(float) * n_prob, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(h_pass, pass, sizeof(float) * n_pass, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(h_misc, misc, sizeof(float) * n_misc, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(h_own, own, sizeof(float) * n_own, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
 template <typename T>
 static int test_head_tail_impl(int device, int n, const int* board_sizes, int max_board, int Cp, int Cv, int prob_ch, int pass_outs,
                                int misc_outs, int act, const float* pconv, const float* vconv, const float* const* w, float* prob,
                                float* pass, float* misc, float* own) {
-    // w: p_inter_w, p_inter_b, pass_w, pass_b, v_inter_w, v_inter_b, v_misc_w, v_misc_b, prob_w, prob_b, own_w, own_b
     HIP_OK(hipSetDevice(device));
     TestArena A;
     TestGeom tg;
     if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
     if (prob_ch > 8) return fail("test_head_tail: too many policy planes");
-    const int cs_p = round_up(Cp, 32), cs_v = round_up(Cv, 32), B2 = max_board * max_board;
-    T* dp = A.upload(nchw_to_nhwc<T>(tg, pconv, Cp, cs_p));
-    T* dv = A.upload(nchw_to_nhwc<T>(tg, vconv, Cv, cs_v));
-    HeadParams h;
-    float* d_pi = A.upload(fc_transposed(w[0], 3 * Cp, Cp));
-    float* d_pib = A.upload(std::vector<float>(w[1], w[1] + Cp));
-    float* d_pw = A.upload(fc_transposed(w[2], Cp, pass_outs));
-    float* d_pwb = A.upload(std::vector<float>(w[3], w[3] + pass_outs));
-    float* d_vi = A.upload(fc_transposed(w[4], 3 * Cv, 3 * Cv));
-    float* d_vib = A.upload(std::vector<float>(w[5], w[5] + 3 * Cv));
-    float* d_vm = A.upload(fc_transposed(w[6], 3 * Cv, misc_outs));
-    float* d_vmb = A.upload(std::vector<float>(w[7], w[7] + misc_outs));
-    float* d_prw = A.upload(std::vector<float>(w[8], w[8] + (size_t)prob_ch * Cp));
-    float* d_prb = A.upload(std::vector<float>(w[9], w[9] + prob_ch));
-    float* d_ow = A.upload(std::vector<float>(w[10], w[10] + Cv));
-    float* d_ob = A.upload(std::vector<float>(w[11], w[11] + 1));
-    float* d_prob = (float*)A.alloc(sizeof(float) * (size_t)n * prob_ch * B2);
-    float* d_pass = (float*)A.alloc(sizeof(float) * (size_t)n * pass_outs);
-    float* d_misc = (float*)A.alloc(sizeof(float) * (size_t)n * misc_outs);
-    float* d_own = (float*)A.alloc(sizeof(float) * (size_t)n * B2);
-    if (!dp || !dv || !d_pi || !d_pib || !d_pw || !d_pwb || !d_vi || !d_vib || !d_vm || !d_vmb || !d_prw || !d_prb || !d_ow || !d_ob ||
-        !d_prob || !d_pass || !d_misc || !d_own)
+    const int cs_p = round_up(Cp, 32), cs_v = round_up(Cv, 32);
+    const T* dp = A.upload(nchw_to_nhwc<T>(tg, pconv, Cp, cs_p));
+    const T* dv = A.upload(nchw_to_nhwc<T>(tg, vconv, Cv, cs_v));
+    HeadWeights hw;
+    TestHeadOut o;
+    if (!dp || !dv || !upload_head_weights(A, w, Cp, Cv, prob_ch, pass_outs, misc_outs, &hw) ||
+        !o.alloc(A, n, prob_ch, pass_outs, misc_outs, max_board * max_board))
         return fail("test_head_tail: hipMalloc failed");
-    h.p_inter = FcDev{d_pi, d_pib, 3 * Cp, Cp};
-    h.pass_fc = FcDev{d_pw, d_pwb, Cp, pass_outs};
-    h.v_inter = FcDev{d_vi, d_vib, 3 * Cv, 3 * Cv};
-    h.v_misc = FcDev{d_vm, d_vmb, 3 * Cv, misc_outs};
-    h.prob_w = d_prw; h.prob_b = d_prb; h.own_w = d_ow; h.own_b = d_ob;
-    h.Cp = Cp; h.cs_p = cs_p; h.Cv = Cv; h.cs_v = cs_v; h.prob_ch = prob_ch; h.act = act; h.board = max_board;
-    h.prob = d_prob; h.pass = d_pass; h.misc = d_misc; h.own = d_own; h.perm = nullptr;
+    const HeadParams h = head_params(hw, Cp, Cv, prob_ch, act, max_board, o.prob, o.pass, o.misc, o.own, nullptr);
     const int maxc = std::max(Cp, Cv);
-    hipLaunchKernelGGL(head_tail_kernel<T>, dim3(2 * n), dim3(256), sizeof(float) * (7 * maxc + 512), 0, (const T*)dp, (const T*)dv, tg.g, h);
+    hipLaunchKernelGGL(head_tail_kernel<T>, dim3(2 * n), dim3(256), sizeof(float) * (7 * maxc + 512), 0, dp, dv, tg.g, h);
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(prob, d_prob, sizeof(float) * (size_t)n * prob_ch * B2, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(pass, d_pass, sizeof(float) * (size_t)n * pass_outs, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(misc, d_misc, sizeof(float) * (size_t)n * misc_outs, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(own, d_own, sizeof(float) * (size_t)n * B2, hipMemcpyDeviceToHost));
-    return 0;
+    return o.download(prob, pass, misc, own);
 }
 
 // The convolution with the SE unit inside it (conv_board_se_kernel, or the same stage inside the persistent tower kernel
@@ -369,69 +270,47 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     TestArena A;
     TestGeom tg;
     if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
-    const int cs = round_up(C, 32), wmt = pick_wmt(cs, true), ko_pad = round_up(cs, wmt * 32);
+    const int cs = round_up(C, 32);
+    int wmt, ko_pad;
+    conv_tile(cs, true, &wmt, &ko_pad);
     const BoardPlan plan = board_plan(tg.hg, ConvOverride{});
     const BoardEntry* be = nullptr;
     if (plan.ok)
         for (const auto& e : kBoardEntries)
             if (e.fn_se && e.kot == ko_pad && e.lds(plan.npos) <= kMaxLds) be = &e;
+    // (deliberately the kernel's own rule, one sample per tile -- not Engine::conv_se's, which fuses only boards too large to share a tile)
     if (!be || !plan.single || C > be->kot) return 1;
     std::vector<f16> img1;
     std::vector<unsigned char> img2;
     int w1_bytes = 0, w2_bytes = 0;
     const bool staged = make_se_images(C, se, max_board, w1, b1, w2, b2, &img1, &img2, &w1_bytes, &w2_bytes);
     if (!staged && (se % 4 || se > 512 || (2 * C) % 4 || 512 % (se / 4) || 512 % (2 * C / 4))) return 1;
-    // activations (with the zero prefix the board kernels read their halo cells from), weights image, tables
-    std::vector<T> hx = nchw_to_nhwc<T>(tg, x, C, cs);
-    T* dx = (T*)A.alloc(hx.size() * sizeof(T) + kZeroPrefix);
-    if (!dx) return fail("test_conv_se: hipMalloc failed");
-    dx += kZeroPrefix / sizeof(T);
-    HIP_OK(hipMemcpy(dx, hx.data(), hx.size() * sizeof(T), hipMemcpyHostToDevice));
-    T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
+    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, C, cs));
+    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
     T* dy = (T*)A.alloc((size_t)n * tg.slot * cs * sizeof(T));
-    const int nch = cs / 32;
-    std::vector<T> img((size_t)9 * nch * 4 * ko_pad * 8, (T)0.f);
-    for (int t = 0; t < 9; ++t)
-        for (int ko = 0; ko < C; ++ko)
-            for (int c = 0; c < C; ++c)
-                img[((((size_t)t * nch + c / 32) * 4 + (c % 32) / 8) * ko_pad + ko) * 8 + c % 8] = (T)w[((size_t)ko * C + c) * 9 + t];
-    std::vector<float> hb(ko_pad, 0.f);
-    if (bias) std::copy(bias, bias + C, hb.begin());
-    // through the tower a Mish layer with computed table entries takes the generated epilogue: weights and bias in
-    // board_row_channel order (Engine::board_row_order_ok)
-    const bool row_order = via_tower && board_uses_row_order(be->kot) && (act == kMish || act == kReLU || act == kIdentity) && plan.single && plan.uniform_info >= 0 && cs == be->kot &&
-                           !EngineFlags::off("SAYURI_TOWER_GEN_EPI");
-    if (row_order) {
-        std::vector<float> hbb(ko_pad);
-        for (int r = 0; r < ko_pad; ++r) hbb[r] = hb[board_row_channel(r)];
-        hb.swap(hbb);
-    }
-    T* dw = A.upload(row_order ? board_row_order(img, ko_pad) : img);
-    float* db = A.upload(hb);
-    float* dw1 = A.upload(fc_transposed(w1, 3 * C, se));
-    float* dw2 = A.upload(fc_transposed(w2, se, 2 * C));
-    float* db1 = A.upload(std::vector<float>(b1, b1 + se));
-    float* db2 = A.upload(std::vector<float>(b2, b2 + 2 * C));
-    f16* d1 = staged ? A.upload(img1) : nullptr;
-    unsigned char* d2 = staged ? A.upload(img2) : nullptr;
-    int* tsrc = (int*)A.alloc(sizeof(int) * (size_t)plan.ntiles * plan.npos);
-    int2* tpix = (int2*)A.alloc(sizeof(int2) * (size_t)plan.ntiles * kBoardPT);
-    int* tcols = (int*)A.alloc(sizeof(int) * (size_t)plan.ntiles);
-    if ((res && !dres) || !dy || !dw || !db || !dw1 || !dw2 || !db1 || !db2 || (staged && (!d1 || !d2)) || !tsrc || !tpix || !tcols)
-        return fail("test_conv_se: hipMalloc failed");
-    hipLaunchKernelGGL(board_setup_kernel, dim3(plan.ntiles), dim3(256), 0, 0, tg.g, plan.npos, tsrc, tpix, tcols);
+    TestBoardTabs tabs;
+    if (!dx || (res && !dres) || !dy || !make_board_tabs(A, tg, plan, &tabs)) return fail("test_conv_se: hipMalloc failed");
     BoardSeParams sp;
     std::memset(&sp, 0, sizeof(sp));
     BoardParams& bp = sp.b;
-    board_params(bp, plan, tsrc, tpix, tcols, true);
-    bp.row_order = row_order ? 1 : 0;
+    board_params(bp, plan, tabs.src, tabs.pix, tabs.cols, true);
     ConvParams& p = bp.c;
-    conv_params(p, dx, dw, db, dres, dy, tg.g, cs, cs, ko_pad, 9, act);
+    conv_params(p, dx, nullptr, nullptr, dres, dy, tg.g, cs, cs, ko_pad, 9, act);
     p.num_pix_tiles = plan.ntiles;
-    sp.squeeze = FcDev{dw1, db1, 3 * C, se};
-    sp.excite = FcDev{dw2, db2, se, 2 * C};
+    // through the tower a layer the generated epilogue covers takes its weights and bias in board_row_channel order, as in Engine::board_launch
+    bp.row_order = via_tower && board_row_order_ok(bp, be->kot, !EngineFlags::off("SAYURI_TOWER_GEN_EPI")) ? 1 : 0;
+    const std::vector<T> img = conv_image<T>(w, C, C, 9, ko_pad);
+    const std::vector<float> hb = padded_bias(bias, C, ko_pad);
+    p.w = A.upload(bp.row_order ? board_row_order(img, ko_pad) : img);
+    p.bias = A.upload(bp.row_order ? board_row_order(hb, ko_pad, 1) : hb);
+    sp.squeeze = FcDev{A.upload(fc_transposed(w1, 3 * C, se)), A.upload(std::vector<float>(b1, b1 + se)), 3 * C, se};
+    sp.excite = FcDev{A.upload(fc_transposed(w2, se, 2 * C)), A.upload(std::vector<float>(b2, b2 + 2 * C)), se, 2 * C};
     sp.C = C;
-    sp.w1h = d1; sp.w2h = d2; sp.w1_bytes = w1_bytes; sp.w2_bytes = w2_bytes;
+    sp.w1h = staged ? A.upload(img1) : nullptr;
+    sp.w2h = staged ? A.upload(img2) : nullptr;
+    sp.w1_bytes = w1_bytes; sp.w2_bytes = w2_bytes;
+    if (!p.w || !p.bias || !sp.squeeze.wt || !sp.squeeze.b || !sp.excite.wt || !sp.excite.b || (staged && (!sp.w1h || !sp.w2h)))
+        return fail("test_conv_se: hipMalloc failed");
     hipModule_t mod = nullptr;
     if (via_tower) {
         hipFunction_t fn[2] = {nullptr, nullptr};
@@ -451,16 +330,7 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
     if (mod) (void)hipModuleUnload(mod);
-    std::vector<T> hy((size_t)n * tg.slot * cs);
-    HIP_OK(hipMemcpy(hy.data(), dy, hy.size() * sizeof(T), hipMemcpyDeviceToHost));
-    size_t so = 0;
-    for (int i = 0; i < n; ++i) {
-        const int S = tg.hg.bsz[i] * tg.hg.bsz[i];
-        for (int c = 0; c < C; ++c)
-            for (int pp = 0; pp < S; ++pp) y[so + (size_t)c * S + pp] = (float)hy[((size_t)i * tg.slot + pp) * cs + c];
-        so += (size_t)C * S;
-    }
-    return 0;
+    return nhwc_to_nchw(tg, dy, C, cs, y);
 }
 
 // Both heads of a sample in one workgroup (head_board_kernel): trunk [n][C][bs*bs] -> the four output tensors.
@@ -478,49 +348,24 @@ static int test_head_board_impl(int device, int n, const int* board_sizes, int m
     HeadImages hi;
     const HeadFn fn = make_head_images(C, Cp, Cv, prob_ch, max_board, p_w, p_b, v_w, v_b, w[8], w[10], &hi);
     if (!fn) return 1;
-    const int cs = round_up(C, 32), B2 = max_board * max_board;
-    T* dt = A.upload(nchw_to_nhwc<T>(tg, trunk, C, cs));
+    const int cs = round_up(C, 32);
+    const T* dt = A.upload(nchw_to_nhwc<T>(tg, trunk, C, cs));
+    const f16* d_img = A.upload(hi.img);
+    const f16* d_img2 = A.upload(hi.img2);
+    const float* d_bias = A.upload(hi.bias);
+    HeadWeights hw;
+    TestHeadOut o;
+    if (!dt || !d_img || !d_img2 || !d_bias || !upload_head_weights(A, w, Cp, Cv, prob_ch, pass_outs, misc_outs, &hw) ||
+        !o.alloc(A, n, prob_ch, pass_outs, misc_outs, max_board * max_board))
+        return fail("test_head_board: hipMalloc failed");
     HeadBoardParams hp;
     std::memset(&hp, 0, sizeof(hp));
-    HeadParams& h = hp.h;
-    float* d_pi = A.upload(fc_transposed(w[0], 3 * Cp, Cp));
-    float* d_pib = A.upload(std::vector<float>(w[1], w[1] + Cp));
-    float* d_pw = A.upload(fc_transposed(w[2], Cp, pass_outs));
-    float* d_pwb = A.upload(std::vector<float>(w[3], w[3] + pass_outs));
-    float* d_vi = A.upload(fc_transposed(w[4], 3 * Cv, 3 * Cv));
-    float* d_vib = A.upload(std::vector<float>(w[5], w[5] + 3 * Cv));
-    float* d_vm = A.upload(fc_transposed(w[6], 3 * Cv, misc_outs));
-    float* d_vmb = A.upload(std::vector<float>(w[7], w[7] + misc_outs));
-    float* d_prw = A.upload(std::vector<float>(w[8], w[8] + (size_t)prob_ch * Cp));
-    float* d_prb = A.upload(std::vector<float>(w[9], w[9] + prob_ch));
-    float* d_ow = A.upload(std::vector<float>(w[10], w[10] + Cv));
-    float* d_ob = A.upload(std::vector<float>(w[11], w[11] + 1));
-    f16* d_img = A.upload(hi.img);
-    f16* d_img2 = A.upload(hi.img2);
-    float* d_bias = A.upload(hi.bias);
-    float* d_prob = (float*)A.alloc(sizeof(float) * (size_t)n * prob_ch * B2);
-    float* d_pass = (float*)A.alloc(sizeof(float) * (size_t)n * pass_outs);
-    float* d_misc = (float*)A.alloc(sizeof(float) * (size_t)n * misc_outs);
-    float* d_own = (float*)A.alloc(sizeof(float) * (size_t)n * B2);
-    if (!dt || !d_pi || !d_pib || !d_pw || !d_pwb || !d_vi || !d_vib || !d_vm || !d_vmb || !d_prw || !d_prb || !d_ow || !d_ob || !d_img ||
-        !d_img2 || !d_bias || !d_prob || !d_pass || !d_misc || !d_own)
-        return fail("test_head_board: hipMalloc failed");
-    h.p_inter = FcDev{d_pi, d_pib, 3 * Cp, Cp};
-    h.pass_fc = FcDev{d_pw, d_pwb, Cp, pass_outs};
-    h.v_inter = FcDev{d_vi, d_vib, 3 * Cv, 3 * Cv};
-    h.v_misc = FcDev{d_vm, d_vmb, 3 * Cv, misc_outs};
-    h.prob_w = d_prw; h.prob_b = d_prb; h.own_w = d_ow; h.own_b = d_ob;
-    h.Cp = Cp; h.cs_p = round_up(Cp, 32); h.Cv = Cv; h.cs_v = round_up(Cv, 32); h.prob_ch = prob_ch; h.act = act; h.board = max_board;
-    h.prob = d_prob; h.pass = d_pass; h.misc = d_misc; h.own = d_own; h.perm = nullptr;
-    hp.trunk = dt; hp.w = d_img; hp.w2 = d_img2; hp.bias = d_bias; hp.g = tg.g; hp.cs = cs; hp.PT = hi.PT; hp.VT = hi.VT; hp.dbg = nullptr;
+    hp.h = head_params(hw, Cp, Cv, prob_ch, act, max_board, o.prob, o.pass, o.misc, o.own, nullptr);
+    hp.trunk = dt; hp.w = d_img; hp.w2 = d_img2; hp.bias = d_bias; hp.g = tg.g; hp.cs = cs; hp.PT = hi.PT; hp.VT = hi.VT;
     hipLaunchKernelGGL(fn, dim3(n), dim3(512), kMaxLds, 0, hp);
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(prob, d_prob, sizeof(float) * (size_t)n * prob_ch * B2, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(pass, d_pass, sizeof(float) * (size_t)n * pass_outs, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(misc, d_misc, sizeof(float) * (size_t)n * misc_outs, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(own, d_own, sizeof(float) * (size_t)n * B2, hipMemcpyDeviceToHost));
-    return 0;
+    return o.download(prob, pass, misc, own);
 }
 
 }  // namespace sayuri
