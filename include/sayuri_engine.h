@@ -31,6 +31,10 @@ long sayuri_weights_tensor(void* weights, const char* name, float* dst, long cap
 /* ---- forward pipe (reference NetworkForwardPipe / BatchForwardPipe, src/neural/network_basic.h:132-161,
  *      src/neural/batch_forward_pipe.cc:7-193) ---------------------------------------------------------------- */
 void* sayuri_pipe_create(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms);
+/* the same with the context flags of include/sayuri_hip.h (SAYURI_HIP_LATENCY = 1: a latency context per GPU); flags = 0 is
+ * sayuri_pipe_create.  A device library that lacks the flagged create entry point is an error only when a flag is set. */
+void* sayuri_pipe_create_ex(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms,
+                            unsigned flags);
 void sayuri_pipe_destroy(void* pipe);
 int sayuri_pipe_num_workers(void* pipe);
 void* sayuri_pipe_ctx(void* pipe, int gpu);                 /* the sayuri_hip_ctx of one GPU */

@@ -91,6 +91,20 @@ int sayuri_hip_device_count(void);
 sayuri_hip_ctx* sayuri_hip_create(int device, const sayuri_hip_netdesc* desc, int max_batch,
                                   int board, int use_fp16);
 
+/* The same with option flags.  SAYURI_HIP_LATENCY makes a LATENCY CONTEXT for the small batches of a playing or analysing engine
+ * (1 to 16 positions): every fp16 3x3 tower convolution whose padded output channels are a multiple of 64 is cut into many
+ * small workgroups (csrc/hip/conv_split.h: 64 channels x a strip of board rows each), so that a lone board's layer runs on tens
+ * of CUs instead of one to three.  Such a context takes that route for EVERY batch, whatever its size (a position's result
+ * does not depend on its batch), has no persistent tower launch (sayuri_hip_tower_state = 0), runs no chains and runs its SE
+ * units as separate kernels; its outputs are those of a default context created under SAYURI_TOWER=0 SAYURI_SE_FUSED=0
+ * SAYURI_SE_SPLIT=0, bit for bit.  Full batches are what the default context is for (INTEGRATION.md says where they cross).
+ * fp16 engine only: flags != 0 with use_fp16 == 0 returns NULL with a message.  sayuri_hip_create is create_ex(..., 0) --
+ * unless SAYURI_LATENCY=1 is set in the environment, which gives an fp16 context the flag (for callers that cannot pass one).
+ * SAYURI_LATENCY_SPLIT=n forces n strips per board instead of the engine's choice (measurements, tests). */
+enum { SAYURI_HIP_LATENCY = 1 };
+sayuri_hip_ctx* sayuri_hip_create_ex(int device, const sayuri_hip_netdesc* desc, int max_batch,
+                                     int board, int use_fp16, unsigned flags);
+
 /* Hand one host tensor of DNNWeights to the device (replaces the LoadWeights calls of
  * cuda_layers.cc:621-716).  Tensors are the BN-folded fp32 arrays the reference loader
  * produces: conv weights [K][C][k][k] (depthwise [C][1][k][k]), fc weights [out][in],
@@ -183,6 +197,10 @@ int sayuri_hip_last_chains(const sayuri_hip_ctx* ctx);
  * The reference always launches per layer (cuda_forward_pipe.cc:713-981). */
 int sayuri_hip_tower_state(const sayuri_hip_ctx* ctx);
 
+/* 1 when the ctx is a latency context (sayuri_hip_create_ex with SAYURI_HIP_LATENCY, or SAYURI_LATENCY=1): its fp16 3x3 layers
+ * take the split route; 0 for a default context. */
+int sayuri_hip_latency_state(const sayuri_hip_ctx* ctx);
+
 /* Release everything (replaces NNGraph::DestroyGraph, cuda_forward_pipe.cc:1092-1130). */
 void sayuri_hip_destroy(sayuri_hip_ctx* ctx);
 
@@ -197,8 +215,17 @@ int sayuri_hip_test_conv(int device, int use_fp16, int n, const int* board_sizes
                          int cin, int cout, int k, int depthwise, int act, int post_residual,
                          const float* x, const float* w, const float* bias, const float* res,
                          float* y);
-/* Kernel family the calling thread's last sayuri_hip_test_conv ran: 0 generic implicit GEMM (conv_mfma.h),
- * 1 LDS-DMA tiles across samples (conv_glds.h), 2 one workgroup per board (conv_board.h), 3 depthwise. */
+/* The fp16 3x3 case of sayuri_hip_test_conv through the latency context's kernel (conv_split.h), with a forced split:
+ * strips = strips per board (0: the engine's choice for this batch; a board gets at most one strip per row),
+ * channel_tiles = 0 or the layer's number of 64-channel tiles (the kernel has one channel tile size; another count is an
+ * error, as is a layer whose padded output channels are not a multiple of 64).  Same results as sayuri_hip_test_conv's
+ * board kernel, bit for bit. */
+int sayuri_hip_test_conv_split(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act,
+                               const float* x, const float* w, const float* bias, const float* res, float* y,
+                               int channel_tiles, int strips);
+/* Kernel family the calling thread's last sayuri_hip_test_conv / sayuri_hip_test_conv_split ran: 0 generic implicit GEMM
+ * (conv_mfma.h), 1 LDS-DMA tiles across samples (conv_glds.h), 2 one workgroup per board (conv_board.h), 3 depthwise,
+ * 4 many small workgroups (conv_split.h). */
 int sayuri_hip_test_last_conv_kind(void);
 /* One squeeze-and-excitation unit through the se_pool / se_fc / se_scale kernels (reference SEUnit::Forward,
  * src/neural/blas/se_unit.cc:70-128): x, res (or NULL), y are [n][channels][bs*bs] like sayuri_hip_test_conv's tensors,

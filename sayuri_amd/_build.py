@@ -238,7 +238,7 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
             list(ex.map(subprocess.check_call, jobs))
         for obj, digest in stamps:
             _stamp(obj, digest)
-    cmd = ["g++", "-shared", "-o", HOST_SO] + objs + ["-L" + LIB, "-lsayuri_hip", "-Wl,-rpath,$ORIGIN", "-lpthread", "-lz"]
+    cmd = ["g++", "-shared", "-o", HOST_SO] + objs + ["-L" + LIB, "-lsayuri_hip", "-Wl,-rpath,$ORIGIN", "-lpthread", "-lz", "-ldl"]
     link_extra = [" ".join(os.path.relpath(c, ROOT) if os.path.isabs(c) else c for c in cmd)]  # the link line decides the output too
     link_digest = _stale(HOST_SO, objs, link_extra)
     if jobs or force or link_digest:

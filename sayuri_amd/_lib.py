@@ -18,7 +18,7 @@ class KernelStat(ctypes.Structure):
 
 # every symbol include/sayuri_hip.h declares
 HIP_SYMBOLS = [
-    "sayuri_hip_device_count", "sayuri_hip_create", "sayuri_hip_load_tensor", "sayuri_hip_forward",
+    "sayuri_hip_device_count", "sayuri_hip_create", "sayuri_hip_create_ex", "sayuri_hip_latency_state", "sayuri_hip_test_conv_split", "sayuri_hip_load_tensor", "sayuri_hip_forward",
     "sayuri_hip_submit", "sayuri_hip_wait", "sayuri_hip_query", "sayuri_hip_upload", "sayuri_hip_run", "sayuri_hip_sync", "sayuri_hip_download", "sayuri_hip_time_runs",
     "sayuri_hip_forward_packed", "sayuri_hip_submit_packed", "sayuri_hip_profile_run", "sayuri_hip_mark_kernel", "sayuri_hip_timed_stat", "sayuri_hip_host_alloc", "sayuri_hip_host_free", "sayuri_hip_device_bytes", "sayuri_hip_last_chains", "sayuri_hip_tower_state",
     "sayuri_hip_destroy", "sayuri_hip_last_error", "sayuri_hip_test_conv", "sayuri_hip_test_last_conv_kind",
@@ -68,6 +68,17 @@ def hip() -> ctypes.CDLL:
         lib.sayuri_hip_last_chains.argtypes = [ctypes.c_void_p]
         lib.sayuri_hip_tower_state.restype = ctypes.c_int
         lib.sayuri_hip_tower_state.argtypes = [ctypes.c_void_p]
+        # entry points a device library may lack (the stand-in knows the ABI it was written against): declared where present
+        if hasattr(lib, "sayuri_hip_latency_state"):
+            lib.sayuri_hip_latency_state.restype = ctypes.c_int
+            lib.sayuri_hip_latency_state.argtypes = [ctypes.c_void_p]
+        if hasattr(lib, "sayuri_hip_create_ex"):
+            lib.sayuri_hip_create_ex.restype = ctypes.c_void_p
+            lib.sayuri_hip_create_ex.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+        if hasattr(lib, "sayuri_hip_test_conv_split"):
+            lib.sayuri_hip_test_conv_split.argtypes = [ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                                       ctypes.c_int, ctypes.c_int]
         if not fake:  # the stand-in has no kernels to tap
             lib.sayuri_hip_test_conv.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -92,6 +103,9 @@ def host() -> ctypes.CDLL:
         lib.sayuri_pipe_create.restype = ctypes.c_void_p
         lib.sayuri_pipe_create.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int]
+        lib.sayuri_pipe_create_ex.restype = ctypes.c_void_p
+        lib.sayuri_pipe_create_ex.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_uint]
         lib.sayuri_pipe_destroy.argtypes = [ctypes.c_void_p]
         lib.sayuri_pipe_num_workers.argtypes = [ctypes.c_void_p]
         lib.sayuri_pipe_ctx.restype = ctypes.c_void_p

@@ -1,4 +1,5 @@
 // engine.hip -- the C-ABI of include/sayuri_hip.h: one translation unit in three parts
+//   (conv_split.h: the many-small-workgroups convolution of a latency context, sayuri_hip_create_ex)
 //   engine_plan.h   kernel registries, environment switches, batch geometry, tile plans and the routing of a convolution to its
 //                   kernel family, the device images of the layers and the launch parameters the engine and the taps share
 //   engine_graph.h  Engine<T>: the per-GPU forward graph -- counterpart of the reference's CudaForwardPipe::NNGraph
@@ -26,6 +27,7 @@
 #include "conv_glds.h"
 #include "conv_board.h"
 #include "conv_board_sx.h"
+#include "conv_split.h"
 #include "conv_tower.h"
 #include "head_board.h"
 #include "small_ops.h"
@@ -50,9 +52,17 @@ int sayuri_hip_device_count(void) {
     return n;
 }
 
-sayuri_hip_ctx* sayuri_hip_create(int device, const sayuri_hip_netdesc* desc, int max_batch, int board, int use_fp16) {
+sayuri_hip_ctx* sayuri_hip_create_ex(int device, const sayuri_hip_netdesc* desc, int max_batch, int board, int use_fp16, unsigned flags) {
     if (!desc || !desc->blocks || max_batch <= 0 || board < 2 || board > 25) {
         fail("sayuri_hip_create: bad arguments");
+        return nullptr;
+    }
+    if (flags & ~(unsigned)SAYURI_HIP_LATENCY) {
+        fail("sayuri_hip_create_ex: unknown flag bits " + std::to_string(flags & ~(unsigned)SAYURI_HIP_LATENCY));
+        return nullptr;
+    }
+    if (flags && !use_fp16) {
+        fail("sayuri_hip_create_ex: SAYURI_HIP_LATENCY needs the fp16 engine (use_fp16 = 1): the fp32 engine is the strict-parity mode and has no split kernels");
         return nullptr;
     }
     int ndev = sayuri_hip_device_count();
@@ -62,18 +72,27 @@ sayuri_hip_ctx* sayuri_hip_create(int device, const sayuri_hip_netdesc* desc, in
     }
     auto ctx = std::make_unique<sayuri_hip_ctx>();
     int rc;
-    const EngineFlags flags = EngineFlags::from_env();
+    const EngineFlags env = EngineFlags::from_env();
+    const EngineFlags eflags = (flags & SAYURI_HIP_LATENCY) ? env.for_latency() : env;
     if (use_fp16) {
-        auto e = std::make_unique<Engine<f16>>(device, *desc, max_batch, board, flags);
+        auto e = std::make_unique<Engine<f16>>(device, *desc, max_batch, board, eflags);
         rc = e->init();
         ctx->eng = std::move(e);
     } else {
-        auto e = std::make_unique<Engine<float>>(device, *desc, max_batch, board, flags);
+        auto e = std::make_unique<Engine<float>>(device, *desc, max_batch, board, eflags);
         rc = e->init();
         ctx->eng = std::move(e);
     }
     if (rc) return nullptr;
     return ctx.release();
+}
+
+sayuri_hip_ctx* sayuri_hip_create(int device, const sayuri_hip_netdesc* desc, int max_batch, int board, int use_fp16) {
+    // SAYURI_LATENCY=1: the flag for callers that cannot pass one (a reference tree with the pipe compiled in).  It asks for the
+    // fp16 engine's latency mode; an fp32 context is created as ever.
+    const char* e = getenv("SAYURI_LATENCY");
+    const unsigned flags = use_fp16 && e && atoi(e) != 0 ? (unsigned)SAYURI_HIP_LATENCY : 0u;
+    return sayuri_hip_create_ex(device, desc, max_batch, board, use_fp16, flags);
 }
 
 int sayuri_hip_load_tensor(sayuri_hip_ctx* ctx, int layer_id, int kind, const float* host, size_t n) {
@@ -154,6 +173,7 @@ void sayuri_hip_host_free(void* p) {
 size_t sayuri_hip_device_bytes(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->device_bytes() : 0; }
 int sayuri_hip_last_chains(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_chains() : 0; }
 int sayuri_hip_tower_state(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->tower_state() : -1; }
+int sayuri_hip_latency_state(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->latency_state() : -1; }
 // debugging tap (not part of the ABI, not in the header): activation buffer `buf` (0..5) of ticket 0 as it stands after the last forward
 extern "C" int sayuri_hip_debug_read_activations(sayuri_hip_ctx* ctx, int buf, void* host, size_t bytes) {
     return ctx ? ctx->eng->debug_read(buf, host, bytes) : -1;

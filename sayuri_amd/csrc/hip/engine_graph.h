@@ -26,6 +26,7 @@ public:
     virtual size_t device_bytes() const = 0;
     virtual int last_chains() const = 0;
     virtual int tower_state() const = 0;  // 1: the persistent tower kernel is loaded, 0: one launch per layer (fallback)
+    virtual int latency_state() const = 0;  // 1: a latency context (conv_split.h), 0: the default engine
     virtual int debug_read(int buf, void* host, size_t bytes) = 0;  // debugging tap: activation buffer `buf` of ticket 0
 };
 
@@ -74,7 +75,9 @@ public:
         // bit-identical to the solo result, profiles/r05_config5_pump_streams.json, tools/gpu/concurrent_ctx_dbg.py).  Without the code object
         // (SAYURI_TOWER=0, or a build whose seam was rejected) the older three-stream arrangement stays.
         if (describe_layers()) return -1;
-        inorder_ = tower_fn_[0] != nullptr;
+        // A latency context has no persistent launch to keep small copies waiting, and a round trip of one position is what it
+        // is for: a stream per ticket too, no event between streams.
+        inorder_ = tower_fn_[0] != nullptr || flags_.latency;
         if (inorder_) HIP_OK(hipStreamCreateWithFlags(&compute_[1], hipStreamNonBlocking));
         return 0;
     }
@@ -357,6 +360,7 @@ public:
         if (geom_.bsz != prev_bsz_) {  // tile choices and index tables depend on the geometry only
             tile_cache_.clear();
             route_cache_.clear();
+            split_cache_.clear();
             board_plan_valid_ = false;
         }
         IoSlot& io = io_[t];
@@ -557,6 +561,7 @@ public:
     size_t device_bytes() const override { return dev_bytes_; }
     int last_chains() const override { return last_chains_; }
     int tower_state() const override { return tower_fn_[0] != nullptr ? 1 : 0; }
+    int latency_state() const override { return flags_.latency ? 1 : 0; }
     int debug_read(int buf, void* host, size_t bytes) override {
         if (buf < 0 || buf >= kNumBufs || !io_[0].bufs[buf]) return fail("debug_read: no such buffer");
         HIP_OK(hipSetDevice(device_));
@@ -710,7 +715,7 @@ private:
                 T* w = nullptr;
                 if (dev_upload(&w, img) || dev_upload(&L.bias, b)) return -1;
                 L.w = w;
-                if (sizeof(T) == 2 && L.k == 3 && L.ko_pad % 128 == 0) {
+                if (sizeof(T) == 2 && L.k == 3 && L.ko_pad % 128 == 0 && !flags_.latency) {  // (conv_split.h reads the natural order)
                     T* wb = nullptr;
                     if (dev_upload(&wb, board_row_order(img, L.ko_pad)) || dev_upload(&L.bias_board, board_row_order(b, L.ko_pad, 1))) return -1;
                     L.w_board = wb;
@@ -1014,7 +1019,7 @@ private:
         const BoardPlan& bp = plan();
         auto it = route_cache_.find(L.k * 65536 + L.ko_pad);
         if (it == route_cache_.end())
-            it = route_cache_.emplace(L.k * 65536 + L.ko_pad, route_conv(sizeof(T) == 2, L.k, L.ko_pad, geom_, bp, flags_.conv, flags_.board_kot)).first;
+            it = route_cache_.emplace(L.k * 65536 + L.ko_pad, route_conv(sizeof(T) == 2, L.k, L.ko_pad, geom_, bp, flags_.conv, flags_.board_kot, flags_.latency)).first;
         return it->second;
     }
 
@@ -1170,8 +1175,24 @@ private:
         return 0;
     }
 
+    // A 3x3 layer of a latency context as many small workgroups (conv_split.h): one launch over the forward's samples, the
+    // split chosen from the batch geometry (split_plan; cached like the routes: it depends on the geometry only).
+    int conv_split(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
+        auto it = split_cache_.find(L.ko_pad);
+        if (it == split_cache_.end()) it = split_cache_.emplace(L.ko_pad, split_plan(geom_, f.n0, f.ns, L.ko_pad, flags_.latency_split)).first;
+        const SplitPlan& sp = it->second;
+        if (!sp.ok) return fail(std::string("latency context: no split of layer ") + name + " fits this batch geometry");
+        SplitParams q;
+        std::memset(&q, 0, sizeof(q));
+        conv_params(q.c, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
+        split_params(q, sp, f.n0);
+        const ConvCost cost = conv_cost(f.px, L.cin, L.cout, 9, res, sizeof(T));
+        return timed(f, name, cost.flops, cost.bytes, [&] { split_launch(sp, q, f.stream); });
+    }
+
     int conv(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
         const ConvRoute& r = route(L);
+        if (r.family == kConvSplit) return conv_split(f, name, L, in, out, res, act);
         if (const BoardEntry* be = r.board) {
             const int bkt = r.tiles;
             const BoardTabs* tabs = nullptr;
@@ -1647,6 +1668,7 @@ private:
     HostGeom geom_;
     std::vector<int> prev_bsz_;
     std::map<int, ConvRoute> route_cache_;  // by (k, ko_pad), for the current batch geometry
+    std::map<int, SplitPlan> split_cache_;  // latency context: by ko_pad, for the current batch geometry
     BoardPlan board_plan_;
     HeadFn head_fn_ = nullptr;
     void* head_img2_ = nullptr;  // per-pixel weights (policy planes, ownership) as an MFMA image

@@ -99,6 +99,12 @@ static const BoardEntry kBoardEntries[] = {
     {192, &conv_board_kernel<3>, nullptr, &BoardCfg<3>::lds_bytes},
     {128, &conv_board_kernel<2>, &conv_board_se_kernel<2>, &BoardCfg<2>::lds_bytes},
 };
+// many-small-workgroups kernels of the latency mode (conv_split.h), by column tiles per wave
+typedef void (*SplitFn)(const SplitParams);
+struct SplitEntry { int nj; SplitFn fn; };
+static const SplitEntry kSplitEntries[] = {
+    {1, &conv_split_kernel<1>}, {2, &conv_split_kernel<2>}, {3, &conv_split_kernel<3>}, {6, &conv_split_kernel<6>}, {12, &conv_split_kernel<12>},
+};
 // head_board_kernel variants: {row tiles, trunk chunks in flight}; the first that fits the LDS is used (head_board_fits)
 typedef void (*HeadFn)(const HeadBoardParams);
 struct HeadEntry { int rt, depth; HeadFn fn; };
@@ -113,6 +119,7 @@ static void enable_big_lds_glds() {
     (void)hipFuncSetAttribute((const void*)&conv_board_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     for (const auto& e : kHeadEntries) (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)&conv_board_sx_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    for (const auto& e : kSplitEntries) (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     for (const auto& e : kBoardEntries) {
         (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
         if (e.fn_se) (void)hipFuncSetAttribute((const void*)e.fn_se, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
@@ -130,6 +137,9 @@ static void enable_big_lds_glds() {
 //   SAYURI_CHAINS_SERIAL=1        debugging aid: the chains of a chained forward one after another (forward())
 //   SAYURI_TOWER_SYNC=1           debugging aid: nothing overlaps a persistent tower launch (tower_flush())
 //   SAYURI_HIP_FWDSTAT=1          measuring aid: device time of every forward sent through submit(), printed when the engine goes
+//   SAYURI_LATENCY=1              a plain sayuri_hip_create of the fp16 engine makes a latency context (sayuri_hip_create_ex's
+//                                 SAYURI_HIP_LATENCY; read in engine.hip, not here: the taps do not see it)
+//   SAYURI_LATENCY_SPLIT=n        latency context: n strips per board in every split convolution instead of the engine's choice
 // The other switches are described at their fields below.
 struct ConvOverride {
     bool v0 = false, no_board = false;
@@ -138,6 +148,10 @@ struct ConvOverride {
 struct EngineFlags {
     ConvOverride conv;
     bool tower = true, se_fused = true, heads_fused = true, arith = true;
+    bool latency = false;              // a latency context (sayuri_hip_create_ex): every fp16 3x3 layer whose padded output channels are a
+                                       // multiple of 64 runs as many small workgroups (conv_split.h), whatever the batch size; no persistent
+                                       // launch, no chains, SE units as separate kernels (for_latency())
+    int latency_split = 0;             // SAYURI_LATENCY_SPLIT=n: strips per board (0: split_auto)
     bool tower_chain = true;           // a layer of the persistent run fetches the next layer's first weight group (SAYURI_TOWER_CHAIN=0: off)
     bool tower_gen_epi = true;         // Mish layers of the run take the generated epilogue (SAYURI_TOWER_GEN_EPI=0: the compiled one)
     bool se_split = true;              // SAYURI_SE_SPLIT=0: SE units of layers split over several channel tiles (384 channels) as
@@ -180,6 +194,7 @@ struct EngineFlags {
         f.chains_serial = getenv("SAYURI_CHAINS_SERIAL") != nullptr;
         f.tower_sync = getenv("SAYURI_TOWER_SYNC") != nullptr;
         f.fwdstat = getenv("SAYURI_HIP_FWDSTAT") != nullptr;
+        if (const char* e = getenv("SAYURI_LATENCY_SPLIT")) f.latency_split = std::max(0, atoi(e));
 #ifdef SAYURI_EXPERIMENTS
         if (const char* e = getenv("SAYURI_BOARD_KOT")) f.board_kot = atoi(e);
         if (const char* e = getenv("SAYURI_ACT_OVERRIDE")) f.act_override = atoi(e);
@@ -187,6 +202,14 @@ struct EngineFlags {
         if (getenv("SAYURI_HEADS_DBG")) f.heads_dbg = 1;
         if (f.board_dbg || f.heads_dbg || f.act_override >= 0) f.tower = false;
 #endif
+        return f;
+    }
+    // The same switches for a latency context: one launch per layer, one chain, and the SE unit always as se_pool / se_fc /
+    // se_scale behind a split convolution -- the fused forms pool fp32 accumulators that no single workgroup holds here.
+    EngineFlags for_latency() const {
+        EngineFlags f = *this;
+        f.latency = true;
+        f.tower = false; f.se_fused = false; f.se_split = false; f.chains = 1;
         return f;
     }
 };
@@ -341,22 +364,70 @@ static const BoardEntry* pick_board(const BoardPlan& bp, int ko_pad, int* kot_ti
     return best;
 }
 // Which kernel runs a k x k convolution with `ko_pad` weight rows on this geometry (`plan` = board_plan(geom, ov)): fp16 3x3
-// layers one workgroup per board (`board`, `tiles` channel tiles per board tile), else the LDS-DMA tiles across samples
+// layers one workgroup per board (`board`, `tiles` channel tiles per board tile) -- in a latency context many small workgroups
+// (kConvSplit) --, else the LDS-DMA tiles across samples
 // (`glds`, `tiles` pixel tiles), everything else the generic conv_mfma kernel (pick_tile).  The values are what
 // sayuri_hip_test_last_conv_kind reports.
-enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3 };
+enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4 };
 struct ConvRoute {
     ConvFamily family = kConvGeneric;
     const BoardEntry* board = nullptr;
     const GldsEntry* glds = nullptr;
     int tiles = 0;
 };
-static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, const BoardPlan& plan, const ConvOverride& ov, int force_kot = 0) {
+static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, const BoardPlan& plan, const ConvOverride& ov, int force_kot = 0,
+                            bool latency = false) {
     ConvRoute r;
     if (!fp16 || k != 3) return r;
+    // a latency context: many small workgroups (`split`; the plan is split_plan's) for every batch; a layer whose weight rows
+    // are not whole 64-channel tiles keeps the route below
+    if (latency && ko_pad % kSplitKO == 0) { r.family = kConvSplit; return r; }
     if ((r.board = pick_board(plan, ko_pad, &r.tiles, force_kot))) r.family = kConvBoard;
     else if ((r.glds = pick_glds(geom, ko_pad, &r.tiles, ov))) r.family = kConvGlds;
     return r;
+}
+
+// The many-small-workgroups plan of a latency context (conv_split.h) for the samples [n0, n0 + ns) and a layer of `ko_pad`
+// weight rows: how many strips a board is cut into, the grid, the kernel variant and its LDS.
+// The split rule (strips == 0): as many strips per board as keep the launch near ONE round of the 256 CUs -- 256 / (samples x
+// channel tiles), at least one, at most kSplitAutoMax and never more than a board has rows (split_rows) -- so a lone board is
+// cut finely and a batch of 64 not at all.  It decides the speed only: the results do not depend on the split.
+constexpr int kSplitAutoMax = 19;
+struct SplitPlan {
+    bool ok = false;
+    int strips = 0, smax = 0, kts = 0, npos = 0, grid = 0;
+    const SplitEntry* e = nullptr;
+    size_t lds = 0;
+};
+static int split_auto(int ns, int kts) { return std::max(1, std::min(kSplitAutoMax, kNumCU / std::max(1, ns * kts))); }
+static SplitPlan split_plan(const HostGeom& geom, int n0, int ns, int ko_pad, int strips) {
+    SplitPlan sp;
+    if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || ko_pad <= 0 || ko_pad % kSplitKO) return sp;
+    sp.kts = ko_pad / kSplitKO;
+    sp.strips = strips > 0 ? strips : split_auto(ns, sp.kts);
+    int max_pos = 0, max_cols = 0;
+    for (int s = n0; s < n0 + ns; ++s) {
+        const int bs = geom.bsz[s], rp = split_rows(bs, sp.strips);
+        sp.smax = std::max(sp.smax, (bs + rp - 1) / rp);
+        max_pos = std::max(max_pos, (rp + 2) * (bs + 2));
+        max_cols = std::max(max_cols, (rp * bs + 15) / 16);
+    }
+    sp.npos = round_up(max_pos, 64);
+    if (sp.npos > kSplitMaxPos || max_cols > kSplitMaxCols) return sp;
+    for (const auto& e : kSplitEntries)
+        if (!sp.e && 2 * e.nj >= max_cols) sp.e = &e;
+    sp.lds = split_lds_bytes(sp.npos);
+    sp.grid = ns * sp.smax * sp.kts;
+    sp.ok = sp.e != nullptr && sp.lds <= kMaxLds;
+    return sp;
+}
+// The split kernels' part of a launch (conv_params fills q.c before): the halo bound, the split and the first sample.
+static void split_params(SplitParams& q, const SplitPlan& sp, int n0) {
+    q.c.npos = sp.npos; q.c.num_pix_tiles = 0;
+    q.strips = sp.strips; q.smax = sp.smax; q.kts = sp.kts; q.n0 = n0;
+}
+static void split_launch(const SplitPlan& sp, const SplitParams& q, hipStream_t s) {
+    hipLaunchKernelGGL(sp.e->fn, dim3(sp.grid), dim3(256), sp.lds, s, q);
 }
 
 // ------------------------------------------------------------------ the parameters of one 3x3 / 1x1 convolution launch

@@ -161,6 +161,44 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
     return nhwc_to_nchw(tg, dy, cout, cout_s, y);
 }
 
+// The same fp16 3x3 layer as many small workgroups (conv_split.h, the latency context's route): the engine's image in natural
+// row order, split_plan's launch.  strips: strips per board (0: the engine's choice for this batch); channel_tiles: 0, or
+// the number of 64-channel tiles the layer has -- the kernel has one channel tile size, any other count is refused.
+static int test_conv_split_impl(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act, const float* x,
+                                const float* w, const float* bias, const float* res, float* y, int channel_tiles, int strips) {
+    typedef f16 T;
+    HIP_OK(hipSetDevice(device));
+    enable_big_lds_glds();
+    TestArena A;
+    TestGeom tg;
+    if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
+    const int cin_s = round_up(cin, 32), cout_s = round_up(cout, 32);
+    int wmt, ko_pad;
+    conv_tile(cout_s, true, &wmt, &ko_pad);
+    const ConvRoute r = route_conv(true, 3, ko_pad, tg.hg, BoardPlan{}, ConvOverride{}, 0, /*latency=*/true);
+    if (r.family != kConvSplit) return fail("test_conv_split: a layer of " + std::to_string(ko_pad) + " weight rows is not whole 64-channel tiles: it keeps the default route");
+    if (channel_tiles && channel_tiles != ko_pad / kSplitKO)
+        return fail("test_conv_split: the split kernel's channel tile is 64: this layer has " + std::to_string(ko_pad / kSplitKO) + " channel tiles");
+    if (strips < 0) return fail("test_conv_split: bad strip count");
+    const SplitPlan sp = split_plan(tg.hg, 0, n, ko_pad, strips);
+    if (!sp.ok) return fail("test_conv_split: no split fits this batch geometry");
+    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, cin, cin_s));
+    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, cout, cout_s)) : nullptr;
+    T* dy = (T*)A.alloc((size_t)n * tg.slot * cout_s * sizeof(T));
+    const T* dw = A.upload(conv_image<T>(w, cin, cout, 9, ko_pad));
+    const float* db = A.upload(padded_bias(bias, cout, ko_pad));
+    if (!dx || !dy || (res && !dres) || !dw || !db) return fail("test_conv_split: hipMalloc failed");
+    g_test_conv_kind = kConvSplit;
+    SplitParams q;
+    std::memset(&q, 0, sizeof(q));
+    conv_params(q.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 9, act);
+    split_params(q, sp, 0);
+    split_launch(sp, q, nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    return nhwc_to_nchw(tg, dy, cout, cout_s, y);
+}
+
 template <typename T>
 static int test_se_unit_impl(int device, int n, const int* board_sizes, int max_board, int C, int se, int act, const float* x,
                              const float* res, const float* w1, const float* b1, const float* w2, const float* b2, float* y,
@@ -405,6 +443,12 @@ extern "C" int sayuri_hip_test_head_tail(int device, int use_fp16, int n, const 
                                         misc_outs, act, pconv, vconv, weights12, prob, pass, misc, own);
     return test_head_tail_impl<float>(device, n, board_sizes, max_board, policy_channels, value_channels, prob_channels, pass_outs,
                                       misc_outs, act, pconv, vconv, weights12, prob, pass, misc, own);
+}
+
+extern "C" int sayuri_hip_test_conv_split(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act, const float* x,
+                                          const float* w, const float* bias, const float* res, float* y, int channel_tiles, int strips) {
+    if (!board_sizes || !x || !w || !y || n <= 0) return fail("test_conv_split: bad argument");
+    return test_conv_split_impl(device, n, board_sizes, max_board, cin, cout, act, x, w, bias, res, y, channel_tiles, strips);
 }
 
 extern "C" int sayuri_hip_test_last_conv_kind(void) { return sayuri::g_test_conv_kind; }

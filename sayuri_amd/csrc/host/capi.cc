@@ -102,7 +102,7 @@ long sayuri_weights_tensor(void* h, const char* name, float* dst, long cap) {
 }
 
 // ---- the pipe
-void* sayuri_pipe_create(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms) {
+void* sayuri_pipe_create_ex(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms, unsigned flags) {
     try {
         auto h = std::make_unique<PipeHandle>();
         h->weights = std::make_shared<DNNWeights>();
@@ -116,6 +116,7 @@ void* sayuri_pipe_create(const char* weights_path, int board, int batch, int fp1
         cfg.fp16 = fp16 != 0;
         cfg.default_boardsize = board;
         cfg.gpu_waittime_ms = waittime_ms;
+        cfg.hip_flags = flags;
         if (device >= 0) cfg.gpus = {device};
         h->pipe = std::make_unique<HipForwardPipe>(cfg);
         h->pipe->Initialize(h->weights);
@@ -124,6 +125,10 @@ void* sayuri_pipe_create(const char* weights_path, int board, int batch, int fp1
         g_err = e.what();
         return nullptr;
     }
+}
+
+void* sayuri_pipe_create(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms) {
+    return sayuri_pipe_create_ex(weights_path, board, batch, fp16, device, waittime_ms, 0u);
 }
 
 void sayuri_pipe_destroy(void* hp) {

@@ -2,6 +2,7 @@
 #include "hip_forward_pipe.h"
 #include "fiber.h"
 
+#include <dlfcn.h>
 #include <pthread.h>
 #include <algorithm>
 #include <chrono>
@@ -62,7 +63,23 @@ int BlockTypeCode(BlockBasic& b) {  // the reference's Is*Block() are non-const
 
 // Network description + tensors -> one device graph (NNGraph::ConstructGraph,
 // cuda_forward_pipe.cc:133-613).
-sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bool fp16) {
+// sayuri_hip_create_ex of the device library IN USE -- the one whose sayuri_hip_create this library calls -- or null when that
+// library has none (an older build, or the serial stand-in of the host tests).  Looked up by name, and only when a flag is set: a
+// device library without the entry point keeps serving every pipe that asks for nothing new.
+typedef sayuri_hip_ctx* (*CreateExFn)(int, const sayuri_hip_netdesc*, int, int, int, unsigned);
+CreateExFn FindCreateEx() {
+    Dl_info info;
+    if (!dladdr(reinterpret_cast<void*>(&sayuri_hip_create), &info) || !info.dli_fname) return nullptr;
+    void* lib = dlopen(info.dli_fname, RTLD_NOW | RTLD_NOLOAD);
+    if (!lib) return nullptr;
+    void* sym = dlsym(lib, "sayuri_hip_create_ex");
+    Dl_info where;  // (a handle's lookup also searches the library's dependencies: the entry point must be the library's own)
+    if (sym && (!dladdr(sym, &where) || !where.dli_fname || std::strcmp(where.dli_fname, info.dli_fname) != 0)) sym = nullptr;
+    dlclose(lib);  // drops the extra reference only: the library stays loaded
+    return reinterpret_cast<CreateExFn>(sym);
+}
+
+sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bool fp16, unsigned hip_flags) {
     std::vector<sayuri_hip_blockdesc> blocks(w.residual_blocks);
     for (int i = 0; i < w.residual_blocks; ++i) {
         BlockBasic& b = *w.tower[i];
@@ -89,8 +106,18 @@ sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bo
     d.policy_dw_filter = d.policy_head_type ? w.p_dw_conv.GetFilter() : 0;
     d.blocks = blocks.data();
 
-    sayuri_hip_ctx* ctx = sayuri_hip_create(device, &d, max_batch, board, fp16 ? 1 : 0);
-    if (!ctx) ThrowHip("sayuri_hip_create");
+    sayuri_hip_ctx* ctx = nullptr;
+    if (hip_flags) {
+        const CreateExFn create_ex = FindCreateEx();
+        if (!create_ex)
+            throw std::runtime_error("the device library has no entry point sayuri_hip_create_ex: it cannot make a context with flags " +
+                                     std::to_string(hip_flags) + " (latency mode needs a current libsayuri_hip.so)");
+        ctx = create_ex(device, &d, max_batch, board, fp16 ? 1 : 0, hip_flags);
+        if (!ctx) ThrowHip("sayuri_hip_create_ex");
+    } else {
+        ctx = sayuri_hip_create(device, &d, max_batch, board, fp16 ? 1 : 0);
+        if (!ctx) ThrowHip("sayuri_hip_create");
+    }
     try {
         LoadConv(ctx, SAYURI_L_INPUT_CONV, w.input_conv);
         for (int i = 0; i < w.residual_blocks; ++i) {
@@ -190,7 +217,7 @@ void HipForwardPipe::BuildGraphs() {
     for (int dev : devices) {
         auto g = std::make_unique<Graph>();
         g->device = dev;
-        g->ctx = BuildCtx(dev, w, max_batch_, board_size_, cfg_.fp16);
+        g->ctx = BuildCtx(dev, w, max_batch_, board_size_, cfg_.fp16, cfg_.hip_flags);
         auto pinned = [&](size_t count) {
             float* p = static_cast<float*>(sayuri_hip_host_alloc(sizeof(float) * count));
             if (!p) ThrowHip("sayuri_hip_host_alloc");

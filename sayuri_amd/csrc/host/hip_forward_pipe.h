@@ -53,6 +53,7 @@ struct HipPipeConfig {
     int gpu_waittime_ms{2};
     int default_boardsize{kBoardSize};
     int fixed_nn_boardsize{0};
+    unsigned hip_flags{0};       // sayuri_hip_create_ex flags of every GPU's context (SAYURI_HIP_LATENCY); 0 = sayuri_hip_create
 };
 
 class HipForwardPipe : public NetworkForwardPipe {

@@ -12,6 +12,7 @@ from . import _lib
 PLANES_LEN = 43 * 361  # InputData::planes
 OUT_LEN = 2 * 361 + 9
 MAX_BOARD = 19
+HIP_LATENCY = 1  # include/sayuri_hip.h: SAYURI_HIP_LATENCY
 
 
 def _fp(a: np.ndarray):
@@ -66,15 +67,22 @@ class HipForwardPipe:
     """One process, one pipe; `device` = -1 uses every visible GPU (one pump thread each)."""
 
     def __init__(self, weights_path: str, board_size: int = MAX_BOARD, batch_size: int = 256, fp16: bool = True,
-                 device: int = 0, waittime_ms: int = 2):
+                 device: int = 0, waittime_ms: int = 2, latency: bool = False):
+        """latency: a latency context per GPU (include/sayuri_hip.h, SAYURI_HIP_LATENCY) -- every 3x3 tower convolution cut
+        into many small workgroups, for the batches of 1 to 16 positions of a playing or analysing engine.  fp16 only."""
         lib = _lib.host()
-        self._h = lib.sayuri_pipe_create(weights_path.encode(), board_size, batch_size, int(fp16), device,
-                                         waittime_ms)
+        if latency:
+            self._h = lib.sayuri_pipe_create_ex(weights_path.encode(), board_size, batch_size, int(fp16), device,
+                                                waittime_ms, HIP_LATENCY)
+        else:
+            self._h = lib.sayuri_pipe_create(weights_path.encode(), board_size, batch_size, int(fp16), device,
+                                             waittime_ms)
         if not self._h:
             raise RuntimeError(f"HipForwardPipe: {lib.sayuri_host_last_error().decode()}")
         self.board_size = board_size
         self.batch_size = batch_size
         self.fp16 = fp16
+        self.latency = latency
 
     # -- NetworkForwardPipe surface
     def Valid(self) -> bool:

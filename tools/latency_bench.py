@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""Small batches: a default context against a latency context (include/sayuri_hip.h, SAYURI_HIP_LATENCY), in one process.
+
+For n in {1, 2, 4, 8, 16, 32, 64} boards of 19x19, and one board of 9x9 and of 13x13, on 20b x 256 and 40b x 384:
+  device_ms  device time per forward, inputs resident (sayuri_hip_time_runs)
+  rt_ms      wall time of one sayuri_hip_submit_packed / sayuri_hip_wait round trip (packed records in pinned memory)
+each for both contexts, interleaved default / latency / default / latency; a point is --warmup forwards, then --rounds rounds
+of --iters timed ones per context, and the MEDIAN of the rounds is reported.  Only the same-process ratios count (boxes differ
+by a few percent).  At n = 1 of 19x19 the per-kernel-class device time of one forward (events around every launch) shows
+where a latency context's time goes: heads and pack_input stay one workgroup per sample.
+
+--mode default measures the default context alone: it uses nothing newer than the first ABI, so it runs on older trees.
+Prints ONE JSON object.
+
+    python tools/latency_bench.py > profiles/r07_latency_small_batch.json
+"""
+import argparse
+import ctypes
+import json
+import os
+import socket
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from sayuri_amd import _lib  # noqa: E402
+from sayuri_amd import weights as W  # noqa: E402
+from sayuri_amd.engine import pack_planes  # noqa: E402
+from sayuri_amd.pipe import HipForwardPipe  # noqa: E402
+
+B = 19
+WORDS = 37 * 12 + 8
+FP = ctypes.POINTER(ctypes.c_float)
+IP = ctypes.POINTER(ctypes.c_int)
+NETS = {"20b256": (W.spec_20b256, 22), "40b384": (W.spec_40b384, 23)}
+POINTS = [(n, 19) for n in (1, 2, 4, 8, 16, 32, 64)] + [(1, 9), (1, 13)]
+
+
+def weights_path(net):
+    spec, seed = NETS[net]
+    path = f"/tmp/sayuri_bench_{net}_seed{seed}_{os.getuid()}.bin"
+    if not os.path.exists(path):
+        W.write_weights(path, spec(), seed=seed)
+    return path
+
+
+class Staging:
+    """Pinned buffers for submit_packed / wait (what the pump owns)."""
+
+    def __init__(self, lib, nmax):
+        self.lib = lib
+        lib.sayuri_hip_host_alloc.restype = ctypes.c_void_p
+        lib.sayuri_hip_host_alloc.argtypes = [ctypes.c_size_t]
+        lib.sayuri_hip_host_free.argtypes = [ctypes.c_void_p]
+        lib.sayuri_hip_submit_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, IP, FP, FP, FP, FP, IP]
+        lib.sayuri_hip_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        self.ptrs = [lib.sayuri_hip_host_alloc(k * 4) for k in (nmax * WORDS, nmax * 5 * B * B, nmax * 5, nmax * 15, nmax * B * B, nmax)]
+        assert all(self.ptrs)
+
+    def close(self):
+        for q in self.ptrs:
+            self.lib.sayuri_hip_host_free(ctypes.c_void_p(q))
+
+    def load(self, rec, bsz):
+        n = len(bsz)
+        np.ctypeslib.as_array(ctypes.cast(self.ptrs[0], ctypes.POINTER(ctypes.c_uint32)), (n * WORDS,))[:] = rec.ravel()
+        np.ctypeslib.as_array(ctypes.cast(self.ptrs[5], ctypes.POINTER(ctypes.c_int32)), (n,))[:] = bsz
+
+    def round_trips(self, ctx, n, iters):
+        """-> wall ms per submit_packed / wait round trip."""
+        rec, pr, pa, mi, ow, bz = self.ptrs
+        tick = ctypes.c_int(-1)
+        args = (ctypes.c_void_p(rec), 37, ctypes.cast(bz, IP), ctypes.cast(pr, FP), ctypes.cast(pa, FP), ctypes.cast(mi, FP), ctypes.cast(ow, FP),
+                ctypes.byref(tick))
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            if self.lib.sayuri_hip_submit_packed(ctx, n, *args) or self.lib.sayuri_hip_wait(ctx, tick.value):
+                raise RuntimeError(self.lib.sayuri_hip_last_error().decode())
+        return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def device_ms(lib, ctx, iters):
+    ms = ctypes.c_float(0)
+    if lib.sayuri_hip_time_runs(ctx, iters, ctypes.byref(ms)):
+        raise RuntimeError(lib.sayuri_hip_last_error().decode())
+    return ms.value / iters
+
+
+def kernel_classes(lib, ctx):
+    rows = (_lib.KernelStat * 64)()
+    k = lib.sayuri_hip_profile_run(ctx, rows, 64)
+    if k < 0:
+        raise RuntimeError(lib.sayuri_hip_last_error().decode())
+    return {rows[i].name.decode(): {"launches": rows[i].launches, "ms": round(rows[i].total_ms, 5)} for i in range(k)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["both", "default"], default="both")
+    ap.add_argument("--nets", default="20b256,40b384")
+    ap.add_argument("--iters", type=int, default=200, help="timed forwards per round and context")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--split", default="", help="also time latency contexts with these forced strips per board at n = 1 (e.g. 4,7,10)")
+    args = ap.parse_args()
+    lib = _lib.hip()
+    try:
+        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    except OSError:
+        commit = ""
+    out = {"tool": "tools/latency_bench.py", "box": socket.gethostname(), "commit": commit or "unknown", "mode": args.mode,
+           "iters": args.iters, "rounds": args.rounds, "warmup": args.warmup, "statistic": "median of rounds", "nets": {}}
+    kinds = ["default"] + (["latency"] if args.mode == "both" else [])
+    for net in args.nets.split(","):
+        path = weights_path(net)
+        pipes = {k: HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, **({"latency": True} if k == "latency" else {})) for k in kinds}
+        for s in (int(x) for x in args.split.split(",") if x and args.mode == "both"):
+            os.environ["SAYURI_LATENCY_SPLIT"] = str(s)
+            try:
+                pipes[f"latency_split{s}"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
+            finally:
+                del os.environ["SAYURI_LATENCY_SPLIT"]
+        stage = Staging(lib, 64)
+        res = {"points": [], "tower_state": {k: lib.sayuri_hip_tower_state(p.ctx(0)) for k, p in pipes.items()}}
+        try:
+            for n, bs in POINTS:
+                planes = W.synthetic_planes(n, [bs] * n, seed=100 + n)
+                grid = np.zeros((n, 43, B * B), np.float32)
+                for i, p in enumerate(planes):
+                    grid[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
+                bsz = np.full(n, bs, np.int32)
+                stage.load(np.stack([pack_planes(p, 37) for p in planes]).astype(np.uint32), bsz)
+                use = {k: p for k, p in pipes.items() if n == 1 or "split" not in k}
+                dev = {k: [] for k in use}
+                rt = {k: [] for k in use}
+                for r in range(-1, args.rounds):  # round -1: the warm-up
+                    for k, p in use.items():
+                        ctx = p.ctx(0)
+                        if lib.sayuri_hip_upload(ctx, n, grid.ctypes.data_as(FP), bsz.ctypes.data_as(IP)):
+                            raise RuntimeError(lib.sayuri_hip_last_error().decode())
+                        it = args.warmup if r < 0 else args.iters
+                        d, w = device_ms(lib, ctx, it), stage.round_trips(ctx, n, it)
+                        if r >= 0:
+                            dev[k].append(d)
+                            rt[k].append(w)
+                pt = {"n": n, "board": bs}
+                for k in use:
+                    pt[k] = {"device_ms": round(float(np.median(dev[k])), 5), "rt_ms": round(float(np.median(rt[k])), 5)}
+                if "latency" in use:
+                    pt["device_ratio"] = round(pt["latency"]["device_ms"] / pt["default"]["device_ms"], 4)
+                    pt["rt_ratio"] = round(pt["latency"]["rt_ms"] / pt["default"]["rt_ms"], 4)
+                if n == 1 and bs == 19:
+                    for k, p in use.items():
+                        if "split" in k:
+                            continue
+                        lib.sayuri_hip_upload(p.ctx(0), n, grid.ctypes.data_as(FP), bsz.ctypes.data_as(IP))
+                        pt[k]["kernel_classes_one_forward"] = kernel_classes(lib, p.ctx(0))
+                res["points"].append(pt)
+        finally:
+            stage.close()
+            for p in pipes.values():
+                p.Destroy()
+        if args.mode == "both":
+            # the batch size of 19x19 boards from which the default context's device time is the smaller one
+            cross = [pt["n"] for pt in res["points"] if pt["board"] == 19 and pt["device_ratio"] > 1.0]
+            res["default_wins_from_n"] = min(cross) if cross else None
+        out["nets"][net] = res
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
