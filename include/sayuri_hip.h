@@ -223,9 +223,9 @@ int sayuri_hip_test_conv(int device, int use_fp16, int n, const int* board_sizes
 int sayuri_hip_test_conv_split(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act,
                                const float* x, const float* w, const float* bias, const float* res, float* y,
                                int channel_tiles, int strips);
-/* Kernel family the calling thread's last sayuri_hip_test_conv / sayuri_hip_test_conv_split ran: 0 generic implicit GEMM
- * (conv_mfma.h), 1 LDS-DMA tiles across samples (conv_glds.h), 2 one workgroup per board (conv_board.h), 3 depthwise,
- * 4 many small workgroups (conv_split.h). */
+/* Kernel family the calling thread's last sayuri_hip_test_conv / sayuri_hip_test_conv_split / sayuri_hip_test_conv_sx ran:
+ * 0 generic implicit GEMM (conv_mfma.h), 1 LDS-DMA tiles across samples (conv_glds.h), 2 one workgroup per board
+ * (conv_board.h), 3 depthwise, 4 many small workgroups (conv_split.h), 5 the split-channel SE convolution (conv_board_sx.h). */
 int sayuri_hip_test_last_conv_kind(void);
 /* One squeeze-and-excitation unit through the se_pool / se_fc / se_scale kernels (reference SEUnit::Forward,
  * src/neural/blas/se_unit.cc:70-128): x, res (or NULL), y are [n][channels][bs*bs] like sayuri_hip_test_conv's tensors,
@@ -256,6 +256,19 @@ int sayuri_hip_test_head_tail(int device, int use_fp16, int n, const int* board_
 int sayuri_hip_test_conv_se(int device, int n, const int* board_sizes, int max_board, int channels, int se_size, int act,
                             int via_tower, const float* x, const float* w, const float* bias, const float* res, const float* w1,
                             const float* b1, const float* w2, const float* b2, float* y);
+/* sayuri_hip_test_conv_se's layer when its channels are split over 2..4 workgroups of 128 per board tile, which exchange their
+ * partial squeeze sums inside the launch (conv_board_sx_kernel, conv_board_sx.h; the 40b x 384 network): same tensors, same
+ * y = act(sigmoid(gamma) * conv(x) + beta + res).  The images, the board plan and the launch are the engine's own host code;
+ * the exchange buffer is fresh and zeroed, the tag fixed.  Returns 1 (not an error) when the form does not apply: channels
+ * (padded to 32) that are not 2..4 whole tiles of 128, an SE width the images do not fit (se_size % 4, se_size > 128, or
+ * the two images larger than the kernel's LDS stage), or a board of the batch of which more than 4 fit a tile (8x8 and
+ * smaller).  -1 when a workgroup's wait for its siblings ran out.
+ * sayuri_hip_test_last_sx_kts: channel tiles per board tile of the calling thread's last sayuri_hip_test_conv_sx launch
+ * (0: that call launched nothing). */
+int sayuri_hip_test_conv_sx(int device, int n, const int* board_sizes, int max_board, int channels, int se_size, int act,
+                            const float* x, const float* w, const float* bias, const float* res, const float* w1,
+                            const float* b1, const float* w2, const float* b2, float* y);
+int sayuri_hip_test_last_sx_kts(void);
 int sayuri_hip_test_head_board(int device, int n, const int* board_sizes, int max_board, int channels, int policy_channels,
                                int value_channels, int prob_channels, int pass_outs, int misc_outs, int act, const float* trunk,
                                const float* p_w, const float* p_b, const float* v_w, const float* v_b,

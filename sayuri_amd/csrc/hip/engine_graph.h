@@ -1131,16 +1131,9 @@ private:
         if constexpr (sizeof(T) != 2) return 1;
         if (!flags_.se_split || sx_disabled_ || !sq.sx_img || !ex.sx_img || !sx_kts_ || L.ko_pad != sx_kts_ * 128 || L.cout_s != L.ko_pad) return 1;
         if (!route(L).board) return 1;
-        const BoardEntry* be = nullptr;
-        for (const auto& e : kBoardEntries)
-            if (e.kot == 128 && e.lds(board_plan_.npos) <= kMaxLds) be = &e;
+        const BoardEntry* be = sx_board_entry(board_plan_.npos);
         if (!be) return 1;
-        const auto [f0, f1, r0, r1] = se_split(f, [](int bs) {
-            BoardPack pk;
-            int k = 0;
-            while (pk.fits(bs)) { pk.add(bs); ++k; }
-            return k <= kSxMaxSub;
-        });
+        const auto [f0, f1, r0, r1] = se_split(f, sx_board_fused);
         if (!f.run.empty() && tower_flush(f)) return -1;
         const BoardTabs* tabs = nullptr;
         if (board_tabs(f, &tabs)) return -1;
@@ -1156,10 +1149,7 @@ private:
         const int kts = sx_kts_;
         if (f1 > f0) {
             p.npos = f0; p.num_pix_tiles = f1 - f0;
-            sp.w1t = sq.sx_img; sp.w2t = ex.sx_img; sp.w1_bytes = sq.sx_bytes; sp.w2_bytes = ex.sx_bytes;
-            sp.nsizes = board_ - 1; sp.se = sq.out; sp.kts = kts;
-            sp.xchg = f.io.sx_xchg; sp.epoch = epoch; sp.err = f.io.sx_err_dev;
-            sp.dbg_stall = flags_.dbg_sx_stall ? 1 : 0;
+            sx_params(sp, sq.sx_img, ex.sx_img, sq.sx_bytes, ex.sx_bytes, board_, sq.out, kts, f.io.sx_xchg, epoch, f.io.sx_err_dev, flags_.dbg_sx_stall);
             if (flags_.sx_dbg > 0 && profiling_ && f.sx_idx == flags_.sx_dbg) {
                 if (!d_sxdbg_ && dev_alloc(&d_sxdbg_, 4 * 64)) return -1;
                 sp.b.dbg = d_sxdbg_;
@@ -1167,7 +1157,7 @@ private:
             const int s0 = board_plan_.tile_first[f0], s1 = board_plan_.tile_first[f1];
             const ConvCost cost = conv_cost(geom_.off[s1] - geom_.off[s0], L.cin, L.cout, 9, res, sizeof(T));
             const double flops = cost.flops + 2.0 * (s1 - s0) * ((double)sq.in * sq.out + (double)ex.in * ex.out);
-            const int grid = (f1 - f0 + 7) / 8 * 8 * kts;
+            const int grid = sx_grid(f1 - f0, kts);
             if (timed(f, "conv3x3_tower_sx", flops, cost.bytes, [&] { hipLaunchKernelGGL(conv_board_sx_kernel<2>, dim3(grid), dim3(512), lds, f.stream, sp); }))
                 return -1;
         }

@@ -367,8 +367,9 @@ static const BoardEntry* pick_board(const BoardPlan& bp, int ko_pad, int* kot_ti
 // layers one workgroup per board (`board`, `tiles` channel tiles per board tile) -- in a latency context many small workgroups
 // (kConvSplit) --, else the LDS-DMA tiles across samples
 // (`glds`, `tiles` pixel tiles), everything else the generic conv_mfma kernel (pick_tile).  The values are what
-// sayuri_hip_test_last_conv_kind reports.
-enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4 };
+// sayuri_hip_test_last_conv_kind reports (kConvBoardSx: never a route -- a block's last convolution with its SE unit inside,
+// Engine::conv_sx; the tap sayuri_hip_test_conv_sx reports it).
+enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4, kConvBoardSx = 5 };
 struct ConvRoute {
     ConvFamily family = kConvGeneric;
     const BoardEntry* board = nullptr;
@@ -465,6 +466,35 @@ static int glds_params(GldsParams& gp, const GldsEntry& e, const int* tab_src, c
     gp.c.npos = 0; gp.c.num_pix_tiles = ntiles;
     return ntiles * (gp.c.ko_pad / (e.wmt * 32));
 }
+// The split-channel SE convolution (conv_board_sx.h): which boards it takes, its board kernel entry, its part of a launch and
+// its grid.  A board takes the form when at most kSxMaxSub samples of its size fit a tile (9x9 and larger): the kernel pools
+// that many samples per tile.
+static bool sx_board_fused(int bs) {
+    BoardPack pk;
+    int k = 0;
+    while (pk.fits(bs)) { pk.add(bs); ++k; }
+    return k <= kSxMaxSub;
+}
+// The 128-row board entry whose rings fit a tile of `npos` halo positions (the kernel's channel tile is 128), or nullptr.
+static const BoardEntry* sx_board_entry(int npos) {
+    const BoardEntry* be = nullptr;
+    for (const auto& e : kBoardEntries)
+        if (e.kot == 128 && e.lds(npos) <= kMaxLds) be = &e;
+    return be;
+}
+// The kernel's own fields of a launch (board_params and conv_params fill sp.b; c.npos / c.num_pix_tiles = the launch's first tile
+// and tile count): the per-channel-tile images of make_sx_images for boards 2..`board`, the exchange buffer
+// [tile][kt][kSxMaxSub][kSxSlots], this launch's tag (never 0) and the host-visible error word.
+static void sx_params(BoardSxParams& sp, const void* w1t, const void* w2t, int w1_bytes, int w2_bytes, int board, int se, int kts,
+                      unsigned long long* xchg, unsigned epoch, unsigned* err, bool dbg_stall) {
+    sp.w1t = w1t; sp.w2t = w2t; sp.w1_bytes = w1_bytes; sp.w2_bytes = w2_bytes;
+    sp.nsizes = board - 1; sp.se = se; sp.kts = kts;
+    sp.xchg = xchg; sp.epoch = epoch; sp.err = err;
+    sp.dbg_stall = dbg_stall ? 1 : 0;
+}
+// Workgroups of a launch over `tiles` board tiles: whole groups of 8 tiles x kts siblings (the last group's empty places leave at once).
+static int sx_grid(int tiles, int kts) { return (tiles + 7) / 8 * 8 * kts; }
+
 // What a convolution over `px` pixels computes and moves (the flops / bytes of the profile rows and of bench.py's
 // tower_conv_mfma_frac): the activations in, out (and the residual), the weights once.
 struct ConvCost { double flops, bytes; };

@@ -371,6 +371,74 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     return nhwc_to_nchw(tg, dy, C, cs, y);
 }
 
+// The same layer when its channels are split over kts = 2..4 workgroups of 128 (conv_board_sx_kernel, conv_board_sx.h): the
+// images of make_sx_images, the launch of Engine::conv_sx (sx_board_entry / sx_params / sx_grid) over every tile of the batch,
+// on a zeroed exchange buffer with a fixed tag.  Returns 1 when the form does not apply: the channels are not 2..4 whole tiles
+// of 128 (after padding to 32), the unit's images do not fit, no 128-row board entry fits, or a board of the batch is too small
+// (sx_board_fused: the engine runs such samples through se_tail).  -1 when a workgroup's wait for its siblings ran out.
+struct TestHostWord {  // a zeroed host-visible word the device can write (BoardSxParams::err)
+    unsigned *host = nullptr, *dev = nullptr;
+    ~TestHostWord() { if (host) (void)hipHostFree(host); }
+    bool alloc() {
+        if (hipHostMalloc((void**)&host, 64, hipHostMallocMapped) != hipSuccess) { host = nullptr; return false; }
+        std::memset(host, 0, 64);
+        return hipHostGetDevicePointer((void**)&dev, host, 0) == hipSuccess;
+    }
+};
+static thread_local int g_test_sx_kts = 0;  // channel tiles per board tile of the last sayuri_hip_test_conv_sx launch (0: it launched nothing)
+static int test_conv_sx_impl(int device, int n, const int* board_sizes, int max_board, int C, int se, int act, const float* x,
+                             const float* w, const float* bias, const float* res, const float* w1, const float* b1, const float* w2,
+                             const float* b2, float* y) {
+    typedef f16 T;
+    constexpr unsigned kEpoch = 0x5e17u;
+    g_test_sx_kts = 0;
+    HIP_OK(hipSetDevice(device));
+    enable_big_lds_glds();
+    TestArena A;
+    TestGeom tg;
+    if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
+    const int cs = round_up(C, 32), kts = round_up(C, 128) / 128;
+    int wmt, ko_pad;
+    conv_tile(cs, true, &wmt, &ko_pad);
+    if (cs != kts * 128 || ko_pad != kts * 128) return 1;  // Engine::build_se_images / conv_sx: the layer is whole 128-channel tiles
+    std::vector<f16> img1;
+    std::vector<unsigned char> img2;
+    int w1_bytes = 0, w2_bytes = 0;
+    if (!make_sx_images(C, se, kts, max_board, w1, b1, w2, b2, &img1, &img2, &w1_bytes, &w2_bytes)) return 1;
+    const BoardPlan plan = board_plan(tg.hg, ConvOverride{});
+    const BoardEntry* be = plan.ok ? sx_board_entry(plan.npos) : nullptr;
+    if (!be) return 1;
+    for (int i = 0; i < n; ++i)
+        if (!sx_board_fused(tg.hg.bsz[i])) return 1;
+    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, C, cs));
+    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
+    T* dy = (T*)A.alloc((size_t)n * tg.slot * cs * sizeof(T));
+    const T* dw = A.upload(conv_image<T>(w, C, C, 9, ko_pad));
+    const float* db = A.upload(padded_bias(bias, C, ko_pad));
+    const f16* d1 = A.upload(img1);
+    const unsigned char* d2 = A.upload(img2);
+    unsigned long long* xchg = (unsigned long long*)A.alloc(sizeof(unsigned long long) * (size_t)plan.ntiles * kts * kSxMaxSub * kSxSlots);
+    TestBoardTabs tabs;
+    TestHostWord err;
+    if (!dx || (res && !dres) || !dy || !dw || !db || !d1 || !d2 || !xchg || !make_board_tabs(A, tg, plan, &tabs) || !err.alloc())
+        return fail("test_conv_sx: hipMalloc failed");
+    BoardSxParams sp;
+    std::memset(&sp, 0, sizeof(sp));
+    board_params(sp.b, plan, tabs.src, tabs.pix, tabs.cols, true);
+    conv_params(sp.b.c, dx, dw, db, dres, dy, tg.g, cs, cs, ko_pad, 9, act);
+    sp.b.c.npos = 0; sp.b.c.num_pix_tiles = plan.ntiles;
+    sx_params(sp, d1, d2, w1_bytes, w2_bytes, max_board, se, kts, xchg, kEpoch, err.dev, /*dbg_stall=*/false);
+    // y starts as fp16 NaN (0xffff): an output no workgroup wrote comes back as NaN, not as a plausible 0
+    HIP_OK(hipMemset(dy, 0xff, (size_t)n * tg.slot * cs * sizeof(T)));
+    g_test_conv_kind = kConvBoardSx;
+    g_test_sx_kts = kts;
+    hipLaunchKernelGGL(conv_board_sx_kernel<2>, dim3(sx_grid(plan.ntiles, kts)), dim3(512), be->lds(plan.npos), 0, sp);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    if (*(volatile unsigned*)err.host) return fail("test_conv_sx: a workgroup's wait for its sibling channel tiles ran out");
+    return nhwc_to_nchw(tg, dy, C, cs, y);
+}
+
 // Both heads of a sample in one workgroup (head_board_kernel): trunk [n][C][bs*bs] -> the four output tensors.
 // Returns 1 when no head_board_kernel variant fits these channel counts (the engine then runs conv1x1 x2 + head_tail).
 static int test_head_board_impl(int device, int n, const int* board_sizes, int max_board, int C, int Cp, int Cv, int prob_ch,
@@ -414,6 +482,15 @@ extern "C" int sayuri_hip_test_conv_se(int device, int n, const int* board_sizes
     if (!board_sizes || !x || !w || !w1 || !b1 || !w2 || !b2 || !y || n <= 0) return fail("test_conv_se: bad argument");
     return test_conv_se_impl(device, n, board_sizes, max_board, channels, se_size, act, via_tower, x, w, bias, res, w1, b1, w2, b2, y);
 }
+
+extern "C" int sayuri_hip_test_conv_sx(int device, int n, const int* board_sizes, int max_board, int channels, int se_size, int act,
+                                       const float* x, const float* w, const float* bias, const float* res, const float* w1,
+                                       const float* b1, const float* w2, const float* b2, float* y) {
+    if (!board_sizes || !x || !w || !w1 || !b1 || !w2 || !b2 || !y || n <= 0) return fail("test_conv_sx: bad argument");
+    return test_conv_sx_impl(device, n, board_sizes, max_board, channels, se_size, act, x, w, bias, res, w1, b1, w2, b2, y);
+}
+
+extern "C" int sayuri_hip_test_last_sx_kts(void) { return sayuri::g_test_sx_kts; }
 
 extern "C" int sayuri_hip_test_head_board(int device, int n, const int* board_sizes, int max_board, int channels, int policy_channels,
                                           int value_channels, int prob_channels, int pass_outs, int misc_outs, int act, const float* trunk,
