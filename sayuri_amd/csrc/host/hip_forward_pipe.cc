@@ -41,6 +41,10 @@ inline void FutexWakeAll(std::atomic<int>* w) {
 [[noreturn]] void ThrowHip(const char* what) {
     throw std::runtime_error(std::string(what) + ": " + sayuri_hip_last_error());
 }
+[[noreturn]] void ThrowBatchFailed() { throw std::runtime_error("HIP forward pipe failed while evaluating a batch"); }
+
+using Clock = std::chrono::steady_clock;
+inline long long Ns(Clock::duration d) { return std::chrono::duration_cast<std::chrono::nanoseconds>(d).count(); }
 
 void LoadConv(sayuri_hip_ctx* ctx, int id, ConvLayer& c) {
     if (sayuri_hip_load_tensor(ctx, id, SAYURI_T_WEIGHTS, c.GetWeights().data(), c.GetWeights().size()) ||
@@ -165,6 +169,13 @@ sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bo
 
 }  // namespace
 
+struct HipForwardPipe::PumpTimer {
+    const HipForwardPipe* pipe;
+    PumpCounter slot;
+    Clock::time_point t0 = Clock::now();
+    ~PumpTimer() { pipe->pump_stat_[slot] += Ns(Clock::now() - t0); }
+};
+
 HipForwardPipe::HipForwardPipe(HipPipeConfig cfg) : cfg_(std::move(cfg)) {}
 
 HipForwardPipe::~HipForwardPipe() {
@@ -239,30 +250,30 @@ void HipForwardPipe::BuildGraphs() {
         }
         graphs_.push_back(std::move(g));
     }
-    trace_ = std::getenv("SAYURI_PIPE_TRACE") != nullptr;
+    trace_.on = std::getenv("SAYURI_PIPE_TRACE") != nullptr;
     if (const char* e = std::getenv("SAYURI_PIPE_TAIL")) tail_frac_ = std::atof(e);
-    if (const char* e = std::getenv("SAYURI_AB_ROTATE_NOTIFY")) rotate_notify_ = std::atoi(e) != 0;
     running_.store(true);
     for (auto& g : graphs_) g->pump = std::thread([this, gp = g.get()] { PumpLoop(gp); });
 }
 
-void HipForwardPipe::TraceDump() const {
-    std::fprintf(stderr, "[pipe trace] arrivals after the last finished batch, 250 us bins:");
-    for (const auto& a : trace_arrival_) std::fprintf(stderr, " %ld", a.load());
-    std::fprintf(stderr, "\n[pipe trace] fibers, last finished batch -> the game runs again:");
-    for (const auto& a : trace_resume_) std::fprintf(stderr, " %ld", a.load());
-    std::fprintf(stderr, "\n[pipe trace] fibers, the game runs again -> its next request:");
-    for (const auto& a : trace_think_) std::fprintf(stderr, " %ld", a.load());
-    std::fprintf(stderr, "\n[pipe trace] tail rule (SAYURI_PIPE_TAIL), age of the running batch at the close:");
-    for (const auto& a : trace_tail_) std::fprintf(stderr, " %ld", a.load());
-    std::fprintf(stderr, "\n[pipe trace] batch sizes /16:");
-    for (const auto& a : trace_size_) std::fprintf(stderr, " %ld", a.load());
-    std::fprintf(stderr, "\n[pipe trace] closed: full %ld, idle-wait %ld, 85%%-rule %ld, stray %ld\n", trace_reason_[0].load(),
-                 trace_reason_[1].load(), trace_reason_[2].load(), trace_reason_[3].load());
+long long HipForwardPipe::Trace::now_ns() { return Ns(Clock::now().time_since_epoch()); }
+
+void HipForwardPipe::Trace::Dump() const {
+    auto row = [](const char* title, const auto& bins) {
+        std::fprintf(stderr, "%s", title);
+        for (const auto& a : bins) std::fprintf(stderr, " %ld", a.load());
+    };
+    row("[pipe trace] arrivals after the last finished batch, 250 us bins:", arrival);
+    row("\n[pipe trace] fibers, last finished batch -> the game runs again:", resume);
+    row("\n[pipe trace] fibers, the game runs again -> its next request:", think);
+    row("\n[pipe trace] tail rule (SAYURI_PIPE_TAIL), age of the running batch at the close:", tail);
+    row("\n[pipe trace] batch sizes /16:", size);
+    std::fprintf(stderr, "\n[pipe trace] closed: full %ld, idle-wait %ld, 85%%-rule %ld, stray %ld\n", reason[kCloseFull].load(),
+                 reason[kCloseIdleWait].load(), reason[kCloseTail].load(), reason[kCloseStray].load());
 }
 
 void HipForwardPipe::DestroyGraphs() {
-    if (trace_ && !graphs_.empty()) TraceDump();
+    if (trace_.on && !graphs_.empty()) trace_.Dump();
     running_.store(false);
     for (auto& g : graphs_) {
         {
@@ -384,31 +395,28 @@ void HipForwardPipe::FillOutput(const Staging* g, int slot, const Echo& in, bool
 }
 
 void HipForwardPipe::SubmitBatch(Graph* g, Staging* s, int n) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     int npacked = 0;
     for (int i = 0; i < n; ++i) npacked += s->is_packed[i];
     if (npacked > 0 && npacked < n)  // a mixed batch travels as fp32 planes
         for (int i = 0; i < n; ++i)
             if (s->is_packed[i]) ExpandPacked(s, i);
     std::lock_guard<std::mutex> dev(g->dev_mu);
-    if (npacked == n) {
-        if (sayuri_hip_submit_packed(g->ctx, n, s->packed, BinaryPlanes(), s->bsz.data(), s->prob, s->pass, s->misc, s->own, &s->ticket))
-            ThrowHip("sayuri_hip_submit_packed");
-    } else if (sayuri_hip_submit(g->ctx, n, s->planes, s->bsz.data(), s->prob, s->pass, s->misc, s->own, &s->ticket)) {
-        ThrowHip("sayuri_hip_submit");
-    }
-    s->n_inflight = n;
-    pump_ns_[0] += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (npacked == n ? sayuri_hip_submit_packed(g->ctx, n, s->packed, BinaryPlanes(), s->bsz.data(), s->prob, s->pass, s->misc, s->own, &s->ticket)
+                     : sayuri_hip_submit(g->ctx, n, s->planes, s->bsz.data(), s->prob, s->pass, s->misc, s->own, &s->ticket))
+        ThrowHip(npacked == n ? "sayuri_hip_submit_packed" : "sayuri_hip_submit");
+    // (a submit that failed has thrown: its time is not counted)
+    pump_stat_[kSubmitCall] += Ns(Clock::now() - t0);
 }
 
 void HipForwardPipe::FinishBatch(Graph* g, Staging* s, int n) {
-    const auto t0 = std::chrono::steady_clock::now();
     int rc;
     {
+        const PumpTimer t{this, kDeviceWait};
         std::lock_guard<std::mutex> dev(g->dev_mu);
         rc = sayuri_hip_wait(g->ctx, s->ticket);
     }
-    const auto t1 = std::chrono::steady_clock::now();
+    const PumpTimer t{this, kHandOut};
     // the previous batch of this set was handed out at least one batch time ago
     while (s->wakes_done.load(std::memory_order_acquire) < s->fin_count) std::this_thread::yield();
     int count = 0, fibers = 0;
@@ -428,7 +436,6 @@ void HipForwardPipe::FinishBatch(Graph* g, Staging* s, int n) {
     }
     batches_.fetch_add(1, std::memory_order_relaxed);
     evals_.fetch_add(static_cast<size_t>(n), std::memory_order_relaxed);
-    s->n_inflight = 0;
     s->fin_count = count;
     s->fin_fibers = fibers;
     s->wakes_done.store(0, std::memory_order_relaxed);
@@ -448,17 +455,130 @@ void HipForwardPipe::FinishBatch(Graph* g, Staging* s, int n) {
     // independent of new reservations, and the pinned OUTPUT buffers are not written again before the set's next
     // batch is submitted -- SubmitBatch waits for `consumed` there (callers need microseconds, that is a batch away).
     Reopen(g, s);
-    const auto t2 = std::chrono::steady_clock::now();
-    pump_ns_[3] += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
-    pump_ns_[1] += std::chrono::duration_cast<std::chrono::nanoseconds>(t2 - t1).count();
+}
+
+// A set re-opened or the fill index moved: wake the callers parked for a free staging set.  Threads sleep on the epoch word;
+// fibers parked on it in Reserve() are woken by their scheduler threads, which may be asleep themselves -- only when a fiber IS
+// parked there (rare with four sets): a NotifyAll wakes every scheduler thread, one per rotation was half of a rank's wake-ups.
+void HipForwardPipe::AnnounceEpoch(Graph* g) {
+    g->epoch.fetch_add(1, std::memory_order_seq_cst);
+    FutexWakeAll(&g->epoch);
+    if (epoch_parked_.load(std::memory_order_seq_cst) > 0) sayuri_fiber::NotifyAll();
 }
 
 void HipForwardPipe::Reopen(Graph* g, Staging* s) {
     s->ready.store(0, std::memory_order_relaxed);
     s->reserved.store(0, std::memory_order_release);  // re-open for callers
-    g->epoch.fetch_add(1, std::memory_order_seq_cst);
-    FutexWakeAll(&g->epoch);
-    if (epoch_parked_.load(std::memory_order_seq_cst) > 0) sayuri_fiber::NotifyAll();  // fibers parked for a free staging set (wake_callers)
+    AnnounceEpoch(g);
+}
+
+// The pump thread's own state: nobody else reads or writes it.
+struct HipForwardPipe::Pump {
+    struct Batch { int set, n; };
+    struct Fifo {  // of closed sets and their sizes; the ring has kSets sets, so it never holds more
+        Batch b[Graph::kSets];
+        int size{0};
+        void push(Batch x) { b[size++] = x; }
+        Batch pop() { const Batch x = b[0]; std::copy(b + 1, b + size--, b); return x; }
+    };
+    Graph* const g;
+    int cur{0};                          // set currently filling
+    Fifo pending{}, inflight{};           // closed sets waiting for a GPU slot; sets on the GPU, at most two
+    bool timing{false};                  // idle-wait rule: a partial fill set was first seen at first_seen
+    Clock::time_point first_seen{};
+    Clock::time_point gpu_busy_since{};  // when the batch at the head of the GPU queue started executing (estimate)
+    double gpu_batch_us{1000.0};         // running mean of a batch's time on the GPU
+    Clock::time_point gpu_idle_since{};
+    bool ever_busy{false};
+};
+
+// Close an open set and queue its requests as a batch; false when it was empty (it is open again then).
+bool HipForwardPipe::CloseSet(Pump& p, int set, CloseReason reason) {
+    Staging& s = p.g->st[set];
+    const unsigned prev = s.reserved.fetch_or(Staging::kClosed, std::memory_order_acq_rel);
+    const int n = static_cast<int>(std::min<unsigned>(prev & ~Staging::kClosed, static_cast<unsigned>(max_batch_)));
+    if (n == 0) { s.reserved.store(0, std::memory_order_release); return false; }
+    const bool stray = reason == kCloseStray;  // counts as partial whatever its size, and is not in the size histogram
+    if (stray || static_cast<unsigned>(n) < WantNow()) pump_stat_[kPartialBatches] += 1;
+    if (trace_.on) {
+        if (!stray) Trace::Count(trace_.size[std::min(n / 16, 16)]);
+        Trace::Count(trace_.reason[reason]);
+    }
+    p.pending.push({set, n});
+    return true;
+}
+
+// close the fill set and point callers at the next one of the ring
+void HipForwardPipe::CloseFillSet(Pump& p, CloseReason reason) {
+    p.timing = false;
+    if (!CloseSet(p, p.cur, reason)) return;
+    p.cur = (p.cur + 1) % Graph::kSets;
+    p.g->fill.store(p.cur, std::memory_order_release);
+    const PumpTimer t{this, kWakeParked};
+    AnnounceEpoch(p.g);
+}
+
+// A caller that read `fill`, was preempted, and resumed after that set had been closed, evaluated and re-opened
+// finds `reserved` == 0 there and takes a slot in a set that is no longer the fill set.  Such a set is open, not
+// `cur`, and holds requests: close it where it stands and queue it like any other batch (the fill index does not
+// move).  Without this the request would wait until the ring wraps around to its set -- forever once traffic stops.
+bool HipForwardPipe::CloseStrays(Pump& p) {
+    bool any = false;
+    for (int k = 0; k < Graph::kSets && p.pending.size < Graph::kSets; ++k) {
+        if (k == p.cur) continue;
+        const unsigned seen = p.g->st[k].reserved.load(std::memory_order_acquire);
+        if ((seen & Staging::kClosed) || seen == 0) continue;
+        any |= CloseSet(p, k, kCloseStray);
+    }
+    return any;
+}
+
+// wait for the callers' plane copies of the oldest pending set, then enqueue it
+void HipForwardPipe::SubmitOldestPending(Pump& p) {
+    const Pump::Batch b = p.pending.pop();
+    Staging& s = p.g->st[b.set];
+    {
+        const PumpTimer t{this, kWaitCallers};
+        while (s.ready.load(std::memory_order_acquire) < static_cast<unsigned>(b.n)) std::this_thread::yield();
+        // every blocking caller of this set's previous batch has copied its result out of the pinned outputs
+        while (s.consumed.load(std::memory_order_acquire) < s.fin_count + s.fin_fibers) std::this_thread::yield();
+    }
+    try {
+        SubmitBatch(p.g, &s, b.n);
+    } catch (const std::exception&) {
+        // nothing was evaluated: every caller gets the failure directly (no tree: nothing to copy out)
+        for (int k = 0; k < b.n; ++k) {
+            s.reqs[k].done->store(-1, std::memory_order_release);
+            FutexWakeAll(s.reqs[k].done);
+        }
+        sayuri_fiber::NotifyAll();
+        Reopen(p.g, &s);
+        return;
+    }
+    if (p.inflight.size == 0) {
+        p.gpu_busy_since = Clock::now();
+        if (p.ever_busy) pump_stat_[kGpuQueueEmpty] += Ns(p.gpu_busy_since - p.gpu_idle_since);
+        p.ever_busy = true;
+    }
+    p.inflight.push(b);
+}
+
+bool HipForwardPipe::OldestIsDone(Pump& p) {
+    std::lock_guard<std::mutex> dev(p.g->dev_mu);
+    return sayuri_hip_query(p.g->ctx, p.g->st[p.inflight.b[0].set].ticket) != 0;
+}
+
+// wait for the batch at the head of the GPU queue and hand it out
+void HipForwardPipe::FinishOldest(Pump& p) {
+    const Pump::Batch b = p.inflight.b[0];
+    if (trace_.on) trace_.last_done_ns.store(Trace::now_ns(), std::memory_order_relaxed);
+    FinishBatch(p.g, &p.g->st[b.set], b.n);
+    const auto now = Clock::now();
+    const double us = std::chrono::duration<double, std::micro>(now - p.gpu_busy_since).count();
+    p.gpu_batch_us = 0.8 * p.gpu_batch_us + 0.2 * us;
+    p.gpu_busy_since = now;  // the next queued batch (if any) has the GPU from here
+    p.inflight.pop();
+    if (p.inflight.size == 0) p.gpu_idle_since = now;
 }
 
 // One persistent pump per GPU over a ring of staging sets.  Callers fill the set `fill` points at; when it holds
@@ -471,204 +591,62 @@ void HipForwardPipe::Reopen(Graph* g, Staging* s) {
 // batch_forward_pipe.cc:99-193).
 void HipForwardPipe::PumpLoop(Graph* g) {
     pthread_setname_np(pthread_self(), "sayuri-pump");
-    using clock = std::chrono::steady_clock;
-    constexpr int K = Graph::kSets;
-    auto count = [](const Staging& s) { return s.reserved.load(std::memory_order_acquire) & ~Staging::kClosed; };
-    auto closed = [](const Staging& s) { return (s.reserved.load(std::memory_order_acquire) & Staging::kClosed) != 0; };
-    // forwarding size, read live: Construct() may lower it while the pump runs (no rebuild)
-    auto want_now = [this] { return static_cast<unsigned>(std::min(forward_size_.load(std::memory_order_acquire), max_batch_)); };
-    int cur = 0;              // set currently filling
-    int pending[K], n_pending = 0, pending_n[K];  // closed sets (and their sizes) waiting for a GPU slot, FIFO
-    int inflight[2], n_in = 0;                    // FIFO of sets on the GPU
-    bool timing = false;
-    clock::time_point first_seen{};
-    clock::time_point gpu_busy_since{};  // when the batch at the head of the GPU queue started executing (estimate)
-    double gpu_batch_us = 1000.0;        // running mean of a batch's time on the GPU
-    clock::time_point gpu_idle_since{};
-    bool ever_busy = false;
-
-    auto wake_callers = [&] {
-        const auto t0 = clock::now();
-        g->epoch.fetch_add(1, std::memory_order_seq_cst);
-        FutexWakeAll(&g->epoch);
-        // fibers parked in Reserve() on the epoch word are woken by their scheduler threads, which may be asleep themselves
-        // -- only when a fiber IS parked there (with four staging sets that is rare): a NotifyAll wakes every scheduler thread,
-        // and one per rotation was half of all wake-ups of a self-play rank (futex calls: 11 % of its host time)
-        if (rotate_notify_ && epoch_parked_.load(std::memory_order_seq_cst) > 0) sayuri_fiber::NotifyAll();
-        pump_ns_[4] += std::chrono::duration_cast<std::chrono::nanoseconds>(clock::now() - t0).count();
-    };
-    // close the fill set and point callers at the next one of the ring
-    auto close_and_rotate = [&](int reason) {
-        Staging& s = g->st[cur];
-        const unsigned prev = s.reserved.fetch_or(Staging::kClosed, std::memory_order_acq_rel);
-        const int n = static_cast<int>(std::min<unsigned>(prev & ~Staging::kClosed, static_cast<unsigned>(max_batch_)));
-        if (n == 0) {
-            s.reserved.store(0, std::memory_order_release);
-            return;
-        }
-        if (static_cast<unsigned>(n) < want_now()) pump_ns_[5] += 1000;  // counts partial batches (reported /1000)
-        if (trace_) {
-            trace_size_[std::min(n / 16, 16)].fetch_add(1, std::memory_order_relaxed);
-            trace_reason_[reason].fetch_add(1, std::memory_order_relaxed);
-        }
-        pending[n_pending] = cur;
-        pending_n[n_pending++] = n;
-        cur = (cur + 1) % K;
-        g->fill.store(cur, std::memory_order_release);
-        wake_callers();
-    };
-    // A caller that read `fill`, was preempted, and resumed after that set had been closed, evaluated and re-opened
-    // finds `reserved` == 0 there and takes a slot in a set that is no longer the fill set.  Such a set is open, not
-    // `cur`, and holds requests: close it where it stands and queue it like any other batch (the fill index does not
-    // move).  Without this the request would wait until the ring wraps around to its set -- forever once traffic stops.
-    auto close_strays = [&] {
-        bool any = false;
-        for (int k = 0; k < K && n_pending < K; ++k) {
-            if (k == cur) continue;
-            Staging& s = g->st[k];
-            const unsigned seen = s.reserved.load(std::memory_order_acquire);
-            if ((seen & Staging::kClosed) || seen == 0) continue;
-            const unsigned prev = s.reserved.fetch_or(Staging::kClosed, std::memory_order_acq_rel);
-            const int n = static_cast<int>(std::min<unsigned>(prev & ~Staging::kClosed, static_cast<unsigned>(max_batch_)));
-            if (n == 0) { s.reserved.store(0, std::memory_order_release); continue; }
-            pump_ns_[5] += 1000;
-            if (trace_) trace_reason_[3].fetch_add(1, std::memory_order_relaxed);
-            pending[n_pending] = k;
-            pending_n[n_pending++] = n;
-            any = true;
-        }
-        return any;
-    };
-    // wait for the callers' plane copies of the oldest pending set, then enqueue it
-    auto submit_pending = [&] {
-        const int i = pending[0], n = pending_n[0];
-        for (int k = 1; k < n_pending; ++k) {
-            pending[k - 1] = pending[k];
-            pending_n[k - 1] = pending_n[k];
-        }
-        --n_pending;
-        Staging& s = g->st[i];
-        const auto tc0 = clock::now();
-        while (s.ready.load(std::memory_order_acquire) < static_cast<unsigned>(n)) std::this_thread::yield();
-        // every blocking caller of this set's previous batch has copied its result out of the pinned outputs
-        while (s.consumed.load(std::memory_order_acquire) < s.fin_count + s.fin_fibers) std::this_thread::yield();
-        pump_ns_[7] += std::chrono::duration_cast<std::chrono::nanoseconds>(clock::now() - tc0).count();
-        try {
-            SubmitBatch(g, &s, n);
-            if (n_in == 0) {
-                gpu_busy_since = clock::now();
-                if (ever_busy) pump_ns_[6] += std::chrono::duration_cast<std::chrono::nanoseconds>(gpu_busy_since - gpu_idle_since).count();
-                ever_busy = true;
-            }
-            inflight[n_in++] = i;
-        } catch (const std::exception&) {
-            // nothing was evaluated: every caller gets the failure directly (no tree: nothing to copy out)
-            for (int k = 0; k < n; ++k) {
-                s.reqs[k].done->store(-1, std::memory_order_release);
-                FutexWakeAll(s.reqs[k].done);
-            }
-            sayuri_fiber::NotifyAll();
-            Reopen(g, &s);
-        }
-    };
-    auto finish_oldest = [&] {
-        Staging& s = g->st[inflight[0]];
-        if (trace_) trace_last_done_ns_.store(std::chrono::duration_cast<std::chrono::nanoseconds>(clock::now().time_since_epoch()).count(), std::memory_order_relaxed);
-        FinishBatch(g, &s, s.n_inflight);
-        const auto now = clock::now();
-        const double us = std::chrono::duration<double, std::micro>(now - gpu_busy_since).count();
-        gpu_batch_us = 0.8 * gpu_batch_us + 0.2 * us;
-        gpu_busy_since = now;  // the next queued batch (if any) has the GPU from here
-        inflight[0] = inflight[1];
-        --n_in;
-        if (n_in == 0) gpu_idle_since = now;
-    };
-
+    Pump p{g};
     while (true) {
-        if (close_strays()) continue;
-        if (!running_.load() && n_in == 0 && n_pending == 0) {
-            bool idle = true;
-            for (const Staging& s : g->st) idle &= count(s) == 0;
-            if (idle) return;
-        }
+        if (CloseStrays(p)) continue;
+        if (!running_.load() && p.inflight.size == 0 && p.pending.size == 0 &&
+            std::all_of(g->st, g->st + Graph::kSets, [](const Staging& s) { return s.count() == 0; }))
+            return;
         // keep the GPU fed: closed sets go out while it has a free slot
-        if (n_pending > 0 && n_in < 2) {
-            submit_pending();
+        if (p.pending.size > 0 && p.inflight.size < 2) { SubmitOldestPending(p); continue; }
+        const Staging& s = g->st[p.cur];
+        if (s.closed()) {  // the ring is full: wait for the oldest batch, its set is the one callers are parked on
+            if (p.inflight.size > 0) FinishOldest(p);
+            p.timing = false;
             continue;
         }
-        Staging& s = g->st[cur];
-        if (closed(s)) {  // the ring is full: wait for the oldest batch, its set is the one callers are parked on
-            if (n_in > 0) finish_oldest();
-            timing = false;
-            continue;
-        }
-        const unsigned c = count(s);
-        if (c >= want_now() || (c > 0 && (cfg_.gpu_waittime_ms <= 0 || !running_.load()))) {
-            close_and_rotate(0);
-            timing = false;
-            continue;
-        }
-        if (c > 0 && n_in == 0) {
+        const unsigned c = s.count();
+        if (c >= WantNow() || (c > 0 && (cfg_.gpu_waittime_ms <= 0 || !running_.load()))) { CloseFillSet(p, kCloseFull); continue; }
+        if (c == 0 || p.inflight.size > 0) p.timing = false;  // the idle-wait clock runs for a partial set and an idle GPU only
+        if (c > 0 && p.inflight.size == 0) {
             // partial batch and an idle GPU: give stragglers gpu_waittime_ms, then send what is there
-            if (!timing) { timing = true; first_seen = clock::now(); }
-            if (clock::now() - first_seen >= std::chrono::milliseconds(cfg_.gpu_waittime_ms)) {
-                close_and_rotate(1);
-                timing = false;
-                continue;
-            }
-        } else if (c > 0 && n_in == 1) {
+            if (!p.timing) { p.timing = true; p.first_seen = Clock::now(); }
+            if (Clock::now() - p.first_seen >= std::chrono::milliseconds(cfg_.gpu_waittime_ms)) { CloseFillSet(p, kCloseIdleWait); continue; }
+        } else if (c > 0 && p.inflight.size == 1) {
             // one batch is running and nothing is queued behind it: let the partial set keep filling, but enqueue it
             // shortly before that batch is expected to finish, so its upload hides under the running batch's tail
-            timing = false;
-            const double run_us = std::chrono::duration<double, std::micro>(clock::now() - gpu_busy_since).count();
-            if (run_us >= tail_frac_ * gpu_batch_us) {
-                if (trace_) trace_tail_[std::min(static_cast<int>(run_us / 250.0), 31)].fetch_add(1, std::memory_order_relaxed);
-                close_and_rotate(2);
+            const auto run = Clock::now() - p.gpu_busy_since;
+            if (std::chrono::duration<double, std::micro>(run).count() >= tail_frac_ * p.gpu_batch_us) {
+                if (trace_.on) Trace::Count(trace_.tail[Trace::bin250us(Ns(run))]);
+                CloseFillSet(p, kCloseTail);
                 continue;
             }
-        } else {
-            timing = false;
         }
         // nothing to send yet: retire a finished batch if there is one, else nap
-        if (n_in > 0) {
-            int q;
-            {
-                std::lock_guard<std::mutex> dev(g->dev_mu);
-                q = sayuri_hip_query(g->ctx, g->st[inflight[0]].ticket);
-            }
-            if (q != 0) {
-                finish_oldest();
-                continue;
-            }
-        }
-        const auto tw0 = clock::now();
-        {
-            std::unique_lock<std::mutex> lk(g->mu);
-            g->cv.wait_for(lk, std::chrono::microseconds(n_in > 0 ? 50 : 200));
-        }
-        pump_ns_[2] += std::chrono::duration_cast<std::chrono::nanoseconds>(clock::now() - tw0).count();
+        if (p.inflight.size > 0 && OldestIsDone(p)) { FinishOldest(p); continue; }
+        const PumpTimer nap{this, kNap};
+        std::unique_lock<std::mutex> lk(g->mu);
+        g->cv.wait_for(lk, std::chrono::microseconds(p.inflight.size > 0 ? 50 : 200));
     }
 }
 
 HipForwardPipe::Ticket HipForwardPipe::Reserve(const InputData* input, const PackedPlanes* packed, OutputResult* out,
                                                std::atomic<int>* done, bool self_serve, bool fiber) {
     if (graphs_.empty()) throw std::runtime_error("HipForwardPipe is not constructed");
-    const Echo echo = input ? Echo{input->board_size, input->offset, input->komi}
-                            : Echo{packed->board_size, static_cast<PolicyBufferOffset>(packed->offset), packed->komi};
+    const Echo echo = EchoOf(input, packed);
     if (echo.board_size < 2 || echo.board_size > board_size_)
         throw std::runtime_error("InputData board size does not fit the NN board");
     done->store(0, std::memory_order_relaxed);
-    if (trace_) {
-        const long long now = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        const long long d = now - trace_last_done_ns_.load(std::memory_order_relaxed);
-        trace_arrival_[std::min<long long>(std::max<long long>(d, 0) / 250000, 31)].fetch_add(1, std::memory_order_relaxed);
+    if (trace_.on) {
+        const long long now = Trace::now_ns();
+        Trace::Count(trace_.arrival[Trace::bin250us(now - trace_.last_done_ns.load(std::memory_order_relaxed))]);
         if (long long* st = sayuri_fiber::FiberStamp()) {
-            if (*st) trace_think_[std::min<long long>(std::max<long long>(now - *st, 0) / 250000, 31)].fetch_add(1, std::memory_order_relaxed);
+            if (*st) Trace::Count(trace_.think[Trace::bin250us(now - *st)]);
         }
     }
     Graph* g = graphs_[next_graph_.fetch_add(1, std::memory_order_relaxed) % graphs_.size()].get();
     const unsigned cap = static_cast<unsigned>(max_batch_);
-    const unsigned want = static_cast<unsigned>(std::min(forward_size_.load(std::memory_order_acquire), max_batch_));
+    const unsigned want = WantNow();
     for (;;) {
         const int epoch = g->epoch.load(std::memory_order_acquire);
         Staging& s = g->st[g->fill.load(std::memory_order_acquire)];
@@ -709,33 +687,38 @@ OutputResult HipForwardPipe::Forward(const InputData& input) { return ForwardAny
 
 OutputResult HipForwardPipe::ForwardPacked(const PackedPlanes& input) { return ForwardAny(nullptr, &input); }
 
+HipForwardPipe::Echo HipForwardPipe::EchoOf(const InputData* input, const PackedPlanes* packed) {
+    return input ? Echo{input->board_size, input->offset, input->komi}
+                 : Echo{packed->board_size, static_cast<PolicyBufferOffset>(packed->offset), packed->komi};
+}
+
+// A Forward() caller copies its own result out of its set's pinned outputs, and says so: the set's next batch waits for that.
+void HipForwardPipe::TakeResult(Staging* s, int slot, const Echo& echo, int status, OutputResult* out) const {
+    if (status > 0) FillOutput(s, slot, echo, true, out);
+    s->consumed.fetch_add(1, std::memory_order_release);
+    if (status < 0) ThrowBatchFailed();
+}
+
 OutputResult HipForwardPipe::ForwardAny(const InputData* in, const PackedPlanes* pk) {
     OutputResult out;
     std::atomic<int> done{0};
-    const Echo input = in ? Echo{in->board_size, in->offset, in->komi}
-                          : Echo{pk->board_size, static_cast<PolicyBufferOffset>(pk->offset), pk->komi};
+    const Echo echo = EchoOf(in, pk);
     if (sayuri_fiber::InFiber()) {
-        fibers_seen_.store(true, std::memory_order_relaxed);
         // M:N game scheduling (fiber.h): hand the request over and run this thread's other games until the batch is back
         const Ticket t = Reserve(in, pk, nullptr, &done, false, true);
         sayuri_fiber::WaitWhileEqual(&done, 0);
-        if (trace_) {
-            const long long now = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-            const long long d = now - trace_last_done_ns_.load(std::memory_order_relaxed);
-            trace_resume_[std::min<long long>(std::max<long long>(d, 0) / 250000, 31)].fetch_add(1, std::memory_order_relaxed);
+        if (trace_.on) {
+            const long long now = Trace::now_ns();
+            Trace::Count(trace_.resume[Trace::bin250us(now - trace_.last_done_ns.load(std::memory_order_relaxed))]);
             if (long long* st = sayuri_fiber::FiberStamp()) *st = now;
         }
-        Staging& s = *t.s;
-        const int status = done.load(std::memory_order_acquire);
-        if (status > 0) FillOutput(&s, t.slot, input, true, &out);
-        s.consumed.fetch_add(1, std::memory_order_release);
-        if (status < 0) throw std::runtime_error("HIP forward pipe failed while evaluating a batch");
+        TakeResult(t.s, t.slot, echo, done.load(std::memory_order_acquire), &out);
         return out;
     }
     const Ticket t = Reserve(in, pk, nullptr, &done, true);
     int st;
     while ((st = done.load(std::memory_order_acquire)) == 0) FutexWait(&done, 0);
-    if (st < 0) throw std::runtime_error("HIP forward pipe failed while evaluating a batch");
+    if (st < 0) ThrowBatchFailed();  // the batch was never submitted: no tree, nothing to take
     // woken through the batch's tree: pass the wake-up on to this node's children first, then take the result
     Staging& s = *t.s;
     const int count = s.fin_count, pos = s.fin_pos[t.slot];
@@ -745,10 +728,7 @@ OutputResult HipForwardPipe::ForwardAny(const InputData* in, const PackedPlanes*
         FutexWakeAll(child);
     }
     s.wakes_done.fetch_add(1, std::memory_order_release);
-    const int status = s.fin_status.load(std::memory_order_relaxed);
-    if (status > 0) FillOutput(&s, t.slot, input, true, &out);
-    s.consumed.fetch_add(1, std::memory_order_release);
-    if (status < 0) throw std::runtime_error("HIP forward pipe failed while evaluating a batch");
+    TakeResult(&s, t.slot, echo, s.fin_status.load(std::memory_order_relaxed), &out);
     return out;
 }
 

@@ -14,6 +14,7 @@
 //     mutex+condvar pair per leaf.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <memory>
@@ -56,6 +57,19 @@ struct HipPipeConfig {
     unsigned hip_flags{0};       // sayuri_hip_create_ex flags of every GPU's context (SAYURI_HIP_LATENCY); 0 = sayuri_hip_create
 };
 
+// What the pump thread keeps count of, in the order pump_times() reports it: time spent ...
+enum PumpCounter {
+    kSubmitCall,      // ... in SubmitBatch: expanding a mixed batch, sayuri_hip_submit / sayuri_hip_submit_packed
+    kHandOut,         // ... handing a finished batch out: snapshot, flags, root of the wake tree, re-opening the set
+    kNap,             // ... asleep with nothing to send and nothing to retire
+    kDeviceWait,      // ... inside sayuri_hip_wait
+    kWakeParked,      // ... announcing a rotation of the fill set to callers parked for a free staging set
+    kPartialBatches,  // NOT a time: batches sent with fewer than batch_size requests
+    kGpuQueueEmpty,   // ... with nothing enqueued on the GPU between two batches
+    kWaitCallers,     // ... waiting for a closed set's plane copies and for the consumers of the set's previous batch
+    kPumpCounters
+};
+
 class HipForwardPipe : public NetworkForwardPipe {
 public:
     explicit HipForwardPipe(HipPipeConfig cfg = {});
@@ -91,12 +105,10 @@ public:
     sayuri_hip_ctx* ctx(int gpu) const;
     size_t num_batches() const { return batches_.load(std::memory_order_relaxed); }
     size_t num_evals() const { return evals_.load(std::memory_order_relaxed); }
-    // pump time split since construction, microseconds: [0] inside sayuri_hip_forward, [1] filling
-    // outputs + signalling, [2] waiting for a batch to form, [3] waiting for plane copies, [4] waking callers parked
-    // for a staging set, [5] batches sent with fewer than batch_size requests (a count, not a time)
-    // [6] time the GPU queue was empty while the pipe was in use, [7] waiting for callers to finish their plane copies
-    void pump_times(double out[8]) const {
-        for (int i = 0; i < 8; ++i) out[i] = static_cast<double>(pump_ns_[i].load(std::memory_order_relaxed)) * 1e-3;
+    // the PumpCounters since construction: microseconds, and the count of partial batches as it is
+    void pump_times(double out[kPumpCounters]) const {
+        for (int i = 0; i < kPumpCounters; ++i)
+            out[i] = static_cast<double>(pump_stat_[i].load(std::memory_order_relaxed)) * (i == kPartialBatches ? 1.0 : 1e-3);
     }
 
 private:
@@ -126,7 +138,8 @@ private:
         std::vector<Request> reqs;
         std::atomic<unsigned> reserved{0};  // slot counter | kClosed
         std::atomic<unsigned> ready{0};
-        int n_inflight{0};   // pump-private: batch size while on the GPU
+        unsigned count() const { return reserved.load(std::memory_order_acquire) & ~kClosed; }
+        bool closed() const { return (reserved.load(std::memory_order_acquire) & kClosed) != 0; }
         int ticket{-1};      // pump-private: sayuri_hip_submit ticket
         // ---- hand-out of a finished batch to blocking Forward() callers.  The pump wakes ONE of them; every woken
         // caller wakes up to kFanout others (a tree over the batch, log depth), then copies its own result out of the
@@ -159,16 +172,46 @@ private:
         std::condition_variable cv;
     };
 
+    struct Pump;  // the pump thread's own state and its two FIFOs (hip_forward_pipe.cc)
+    enum CloseReason { kCloseFull, kCloseIdleWait, kCloseTail, kCloseStray, kCloseReasons };
+    // SAYURI_PIPE_TRACE=1 (read once at construction; a measuring aid, printed to stderr when the graphs are destroyed):
+    // when do requests arrive relative to the last finished batch, how full are the batches and why were they closed
+    struct Trace {
+        bool on{false};
+        std::atomic<long long> last_done_ns{0};
+        std::atomic<long> arrival[32] = {};  // 250 us bins since the last finished batch
+        std::atomic<long> size[17] = {};     // batch size / 16
+        std::atomic<long> resume[32] = {};   // fibers: batch finished -> the game runs again
+        std::atomic<long> think[32] = {};    // fibers: the game runs again -> its next request
+        std::atomic<long> tail[32] = {};     // tail rule: how long the running batch had been running when the set was closed
+        std::atomic<long> reason[kCloseReasons] = {};
+        static long long now_ns();
+        static int bin250us(long long ns) { return static_cast<int>(ns < 0 ? 0 : ns / 250000 > 31 ? 31 : ns / 250000); }
+        static void Count(std::atomic<long>& bin) { bin.fetch_add(1, std::memory_order_relaxed); }
+        void Dump() const;
+    };
+
     struct Ticket { Graph* g; Staging* s; int slot; };
+    static Echo EchoOf(const InputData* input, const PackedPlanes* packed);
     // exactly one of input / packed is non-null
     Ticket Reserve(const InputData* input, const PackedPlanes* packed, OutputResult* out, std::atomic<int>* done, bool self_serve,
                    bool fiber = false);
     OutputResult ForwardAny(const InputData* input, const PackedPlanes* packed);
+    void TakeResult(Staging* s, int slot, const Echo& echo, int status, OutputResult* out) const;
     int BinaryPlanes() const;
+    // forwarding size, read live: Construct() may lower it while the pump runs (no rebuild)
+    unsigned WantNow() const { return static_cast<unsigned>(std::min(forward_size_.load(std::memory_order_acquire), max_batch_)); }
+    void AnnounceEpoch(Graph* g);
     void Reopen(Graph* g, Staging* s);
     void BuildGraphs();
     void DestroyGraphs();
     void PumpLoop(Graph* g);
+    bool CloseSet(Pump& p, int set, CloseReason reason);
+    bool CloseStrays(Pump& p);
+    void CloseFillSet(Pump& p, CloseReason reason);
+    void SubmitOldestPending(Pump& p);
+    bool OldestIsDone(Pump& p);
+    void FinishOldest(Pump& p);
     void SubmitBatch(Graph* g, Staging* s, int n);
     void FinishBatch(Graph* g, Staging* s, int n);
     void StageInput(Staging* s, int slot, const InputData& in, bool already_padded);
@@ -182,24 +225,14 @@ private:
     std::atomic<int> forward_size_{0};  // batch size the collector forwards at (<= max_batch_); Construct() may lower it live
     std::vector<std::unique_ptr<Graph>> graphs_;
     std::atomic<bool> running_{false};
-    std::atomic<bool> fibers_seen_{false};  // some caller is a fiber: re-opened staging sets are announced to the fiber schedulers too
     std::atomic<unsigned> next_graph_{0};
     std::atomic<size_t> batches_{0}, evals_{0};
-    mutable std::atomic<long long> pump_ns_[8] = {};
-    // SAYURI_PIPE_TRACE=1 (read once at construction; a measuring aid, printed to stderr when the graphs are destroyed):
-    // when do requests arrive relative to the last finished batch, how full are the batches and why were they closed
-    bool trace_{false};
-    bool rotate_notify_{true};  // SAYURI_AB_ROTATE_NOTIFY (measuring aid)
+    mutable std::atomic<long long> pump_stat_[kPumpCounters] = {};  // nanoseconds, but kPartialBatches: a count
+    struct PumpTimer;  // adds its own lifetime to one of them
     std::atomic<int> epoch_parked_{0};  // fibers suspended in Reserve() until a staging set re-opens
-    std::atomic<long long> trace_last_done_ns_{0};
-    std::atomic<long> trace_arrival_[32] = {};  // 250 us bins since the last finished batch
-    std::atomic<long> trace_size_[17] = {};     // batch size / 16
-    std::atomic<long> trace_resume_[32] = {};   // fibers: batch finished -> the game runs again
-    std::atomic<long> trace_think_[32] = {};    // fibers: the game runs again -> its next request
-    std::atomic<long> trace_tail_[32] = {};     // tail rule: how long the running batch had been running when the set was closed
-    std::atomic<long> trace_reason_[4] = {};
-    double tail_frac_{0.93};                    // SAYURI_PIPE_TAIL (measuring aid): the fraction of a batch's time after which a partial set is enqueued behind it    // closed because: full, GPU idle + wait expired, 93 % of the running batch, stray
-    void TraceDump() const;
+    Trace trace_;
+    // SAYURI_PIPE_TAIL (measuring aid): the fraction of a batch's time after which a partial set is enqueued behind it
+    double tail_frac_{0.93};
 };
 
 SAYURI_HOST_END

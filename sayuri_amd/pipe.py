@@ -116,7 +116,17 @@ class HipForwardPipe:
         return eps.value, tot.value
 
     def pump_times(self):
-        """-> dict of pump-thread time (us) since construction + batch / eval counters."""
+        """-> dict of pump-thread time (us) since construction + batch / eval counters (PumpCounter, hip_forward_pipe.h):
+        forward_us            in the submit call (expanding a mixed batch, sayuri_hip_submit / sayuri_hip_submit_packed)
+        fill_us               handing finished batches out (snapshot, flags, root of the wake tree) and re-opening their sets
+        wait_batch_us         asleep: nothing to send, nothing to retire
+        wait_copies_us        inside sayuri_hip_wait, i.e. waiting for the GPU (NOT for plane copies: wait_plane_copies_us)
+        wake_parked_us        waking callers parked for a free staging set when the fill set rotates
+        partial_batches       a count: batches sent with fewer than batch_size requests
+        gpu_queue_empty_us    nothing was enqueued on the GPU between two batches
+        wait_plane_copies_us  waiting for a closed set's callers to finish their plane copies, and for the consumers of the
+                              set's previous batch
+        batches, evals        batches and positions evaluated (BatchForward included)"""
         t = (ctypes.c_double * 8)()
         b, e = ctypes.c_long(0), ctypes.c_long(0)
         _lib.host().sayuri_pipe_pump_times(self._h, t, ctypes.byref(b), ctypes.byref(e))

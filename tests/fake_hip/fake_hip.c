@@ -13,8 +13,14 @@
  * the real one -- a batch occupies it for T microseconds whatever its size (3 800 us = one 256-batch of the 20b x 256
  * network on an MI355X), the next one starts when the previous has finished -- and FAKE_HIP_CHEAP=1 replaces the
  * per-plane checksum network by one that costs the host next to nothing (policy = the first bit planes plus a hash of
- * the position), so that the host cores measured are the engine's, not the stand-in's. */
+ * the position), so that the host cores measured are the engine's, not the stand-in's.
+ *
+ * Error returns for the collector's failure paths: FAKE_HIP_FAIL_SUBMIT=k makes the k-th sayuri_hip_submit /
+ * sayuri_hip_submit_packed of a context return -1 (nothing is enqueued), FAKE_HIP_FAIL_WAIT=k the k-th sayuri_hip_wait
+ * (the batch is waited for and its ticket freed, then -1); both set the last-error string, unset means never.
+ * fake_hip_failed_batches / fake_hip_failed_evals tell a test how many batches were failed and how many requests they held. */
 #include <pthread.h>
+#include <stdio.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -44,7 +50,20 @@ struct sayuri_hip_ctx {
     pthread_cond_t cv_work, cv_done;
     pthread_t worker;
     long submits, evals;
+    long fail_submit, fail_wait; /* FAKE_HIP_FAIL_SUBMIT / _WAIT: which call of this context fails (0 = none) */
+    long submit_calls, wait_calls;
 };
+static char g_last_error[96] = "fake_hip: no error text";
+static long g_failed_batches = 0, g_failed_evals = 0; /* written under a context's mu */
+long fake_hip_failed_batches(void) { return g_failed_batches; }
+long fake_hip_failed_evals(void) { return g_failed_evals; }
+/* the requested failure of one call: counts the batch, leaves the text for sayuri_hip_last_error.  c->mu is held. */
+static int fail_call(const char* what, long call, int n) {
+    ++g_failed_batches;
+    g_failed_evals += n;
+    snprintf(g_last_error, sizeof g_last_error, "fake_hip: %s %ld failed on request (%d positions)", what, call, n);
+    return -1;
+}
 
 static void fake_eval(const sayuri_hip_ctx* c, int n, const float* planes, const int* bsz, float* prob, float* pass,
                       float* misc, float* own) {
@@ -143,7 +162,7 @@ int sayuri_hip_device_count(void) {
     const char* e = getenv("FAKE_HIP_DEVICES");
     return e ? atoi(e) : 1;
 }
-const char* sayuri_hip_last_error(void) { return "fake_hip: no error text"; }
+const char* sayuri_hip_last_error(void) { return g_last_error; }
 
 sayuri_hip_ctx* sayuri_hip_create(int device, const sayuri_hip_netdesc* desc, int max_batch, int board, int use_fp16) {
     (void)device; (void)use_fp16;
@@ -157,6 +176,10 @@ sayuri_hip_ctx* sayuri_hip_create(int device, const sayuri_hip_netdesc* desc, in
     const char* su = getenv("FAKE_HIP_SERIAL_US");
     c->serial_us = su ? atol(su) : 0;
     c->cheap = getenv("FAKE_HIP_CHEAP") != NULL;
+    const char* fs = getenv("FAKE_HIP_FAIL_SUBMIT");
+    c->fail_submit = fs ? atol(fs) : 0;
+    const char* fw = getenv("FAKE_HIP_FAIL_WAIT");
+    c->fail_wait = fw ? atol(fw) : 0;
     pthread_mutex_init(&c->mu, NULL);
     pthread_cond_init(&c->cv_work, NULL);
     pthread_cond_init(&c->cv_done, NULL);
@@ -220,6 +243,11 @@ static int submit_any(sayuri_hip_ctx* c, int n, const float* planes, float* owne
                       float* misc, float* own, int* ticket) {
     if (!c || n <= 0 || n > c->max_batch) return -1;
     pthread_mutex_lock(&c->mu);
+    if (++c->submit_calls == c->fail_submit) {
+        const int rc = fail_call("submit", c->submit_calls, n);
+        pthread_mutex_unlock(&c->mu);
+        return rc;
+    }
     const int t = c->next;
     struct job* j = &c->jobs[t];
     if (j->state != 0) { pthread_mutex_unlock(&c->mu); return -1; } /* more than two batches in flight */
@@ -252,8 +280,9 @@ int sayuri_hip_wait(sayuri_hip_ctx* c, int t) {
     if (c->jobs[t].state == 0) { pthread_mutex_unlock(&c->mu); return -1; }
     while (c->jobs[t].state != 2) pthread_cond_wait(&c->cv_done, &c->mu);
     c->jobs[t].state = 0;
+    const int rc = ++c->wait_calls == c->fail_wait ? fail_call("wait", c->wait_calls, c->jobs[t].n) : 0;
     pthread_mutex_unlock(&c->mu);
-    return 0;
+    return rc;
 }
 int sayuri_hip_query(sayuri_hip_ctx* c, int t) {
     if (!c || t < 0 || t > 1) return -1;

@@ -220,3 +220,128 @@ def test_in_process_two_gpu_pumps(fake_lib, tmp_weights_dir):
                        timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "two pumps ok" in r.stdout
+
+
+FAILURE_DRIVER = textwrap.dedent(r"""
+    import ctypes, sys, threading
+    import numpy as np
+    fake = ctypes.CDLL(sys.argv[1], mode=ctypes.RTLD_GLOBAL)
+    fake.fake_hip_failed_batches.restype = fake.fake_hip_failed_evals.restype = ctypes.c_long
+    from sayuri_amd.pipe import HipForwardPipe
+
+    B, C = 19, 43
+    def expected(planes, bs, off):
+        grid = np.zeros((C, B, B), np.float32)
+        grid[:, :bs, :bs] = planes.reshape(C, bs, bs)
+        x = grid.reshape(C, B * B).astype(np.float64)
+        w = 1 + (np.arange(C * B * B) % 7)
+        s = float((x.ravel() * w).sum())
+        prob = (x[off] + 0.5 * x[5] + off).reshape(B, B)[:bs, :bs].ravel()
+        own = (x[7] - x[8]).reshape(B, B)[:bs, :bs].ravel()
+        misc = np.float32(s * 0.002) - np.arange(15, dtype=np.float32) + np.float32(bs)
+        tail = [np.float32(s * 0.001) + off, misc[0], misc[1], misc[2], misc[3], misc[8], misc[13], misc[14], off]
+        return np.concatenate([prob, own, np.asarray(tail, np.float64)])
+
+    def check(case, got, label):
+        exp = expected(*case)
+        assert got.shape == exp.shape, (label, got.shape, exp.shape)
+        err = np.abs(got - exp).max()
+        assert err <= 1e-3 * max(1.0, np.abs(exp).max()), (label, case[1], case[2], err)
+
+    rng = np.random.default_rng(7)
+    def make(n):                 # packable (0/1 binary planes, constant scalar planes), so both entry points take them
+        cases = []
+        for _ in range(n):
+            bs = int(rng.choice([19, 19, 13, 9, 7]))
+            p = np.zeros((C, bs * bs), np.float32)
+            p[:C - 6] = rng.integers(0, 2, size=(C - 6, bs * bs))
+            p[C - 6:] = rng.normal(size=(6, 1)).astype(np.float32)
+            cases.append((p, bs, int(rng.integers(0, 5))))
+        return cases
+
+    pipe = HipForwardPipe(sys.argv[2], board_size=19, batch_size=16, fp16=True)
+    forward = pipe.ForwardPacked if sys.argv[4] == "packed" else pipe.Forward
+    def callers(cases):          # one blocking caller per case, all at once; -> per caller its reply or its exception
+        res = [None] * len(cases)
+        def one(i):
+            p, bs, off = cases[i]
+            try:
+                res[i] = forward([p], [bs], offsets=[off])[0]
+            except RuntimeError as e:
+                res[i] = e
+        ths = [threading.Thread(target=one, args=(i,)) for i in range(len(cases))]
+        [t.start() for t in ths]; [t.join() for t in ths]
+        return res
+
+    # round 1: the second submit (or wait) of the context fails -- one batch's callers raise, everybody else is served
+    before = pipe.pump_times()
+    cases = make(40)
+    res = callers(cases)
+    raised = [r for r in res if isinstance(r, Exception)]
+    assert 1 <= len(raised) <= 16, len(raised)
+    assert all("failed while evaluating a batch" in str(e) for e in raised), raised[0]
+    assert fake.fake_hip_failed_batches() == 1, fake.fake_hip_failed_batches()
+    assert len(raised) == fake.fake_hip_failed_evals(), (len(raised), fake.fake_hip_failed_evals())   # the members of that batch
+    for case, r in zip(cases, res):
+        if not isinstance(r, Exception):
+            check(case, r, "round 1")
+    # a batch that was never submitted is not counted, one whose wait failed is (it was on the device)
+    mid = pipe.pump_times()
+    assert mid["evals"] - before["evals"] == 40 - (len(raised) if sys.argv[3] == "submit" else 0), (before, mid, len(raised))
+    # round 2: the failed batch's set was re-opened and the ring moves on
+    cases = make(40)
+    res = callers(cases)
+    for case, r in zip(cases, res):
+        assert not isinstance(r, Exception), r
+        check(case, r, "round 2")
+    assert fake.fake_hip_failed_batches() == 1
+    assert pipe.pump_times()["evals"] - mid["evals"] == 40
+    pipe.Destroy()
+    print("failure ok", len(raised))
+""")
+
+
+@pytest.mark.parametrize("delay_us", [0, 300])
+@pytest.mark.parametrize("knob,entry", [("submit", "fp32"), ("wait", "fp32"), ("submit", "packed")])
+def test_a_failed_batch_fails_its_callers_and_nobody_else(fake_lib, tmp_weights_dir, knob, entry, delay_us):
+    """The collector's failure paths (a submit that returns an error: nothing was enqueued, the pump fails every request
+    of the set directly; a wait that returns an error: the batch is handed out through the wake tree with a failed
+    status).  The fake device fails the context's second submit / wait: of 40 concurrent blocking callers exactly the
+    members of that one batch raise (1 to 16 of them), every other reply belongs to its request, a second round of 40
+    is served completely (the set was re-opened, the ring moves on) and Destroy() returns."""
+    weights = Golden("tiny_res", tmp_weights_dir).weights_path
+    env = dict(os.environ, FAKE_HIP_DELAY_US=str(delay_us), PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    env["FAKE_HIP_FAIL_" + knob.upper()] = "2"
+    r = subprocess.run([sys.executable, "-c", FAILURE_DRIVER, fake_lib, weights, knob, entry], env=env, cwd=ROOT,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "failure ok" in r.stdout
+
+
+COUNTER_DRIVER = textwrap.dedent(r"""
+    import ctypes, sys
+    import numpy as np
+    ctypes.CDLL(sys.argv[1], mode=ctypes.RTLD_GLOBAL)
+    from sayuri_amd.pipe import HipForwardPipe
+    pipe = HipForwardPipe(sys.argv[2], board_size=19, batch_size=16, fp16=True)
+    rng = np.random.default_rng(3)
+    before = pipe.pump_times()
+    for _ in range(5):
+        pipe.Forward([rng.integers(0, 4, size=(43, 361)).astype(np.float32)], [19])
+    after = pipe.pump_times()
+    grown = {k: after[k] - before[k] for k in ("batches", "evals", "partial_batches")}
+    assert grown == {"batches": 5, "evals": 5, "partial_batches": 5}, (before, after)
+    pipe.Destroy()
+    print("counters ok")
+""")
+
+
+def test_single_requests_count_as_partial_batches(fake_lib, tmp_weights_dir):
+    """Five Forward calls of one position each, one after another, at batch size 16: five batches, five evaluations, five
+    partial batches -- exactly."""
+    weights = Golden("tiny_res", tmp_weights_dir).weights_path
+    env = dict(os.environ, FAKE_HIP_DELAY_US="0", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-c", COUNTER_DRIVER, fake_lib, weights], env=env, cwd=ROOT, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "counters ok" in r.stdout

@@ -28,7 +28,6 @@ run head_$round . A=1
 run r02_$round ab/r02 A=1
 run r02x_$round ab/r02x A=1
 done
-run norotnotify . SAYURI_AB_ROTATE_NOTIFY=0
 run arenakeep . SAYURI_AB_ARENA_KEEP_MB=64
 run nopin . SAYURI_NO_PIN=1
 run tail2 . SAYURI_PIPE_TAIL=2.0
