@@ -33,6 +33,8 @@ constexpr int kBoardPT = kBoardCols * 16;   // pixel slots per tile
 constexpr int kBoardMaxPos = 512;           // halo positions per tile (DMA blocks of 64)
 constexpr int kBoardMaxSub = 32;            // samples per tile
 constexpr int kBoardNJ = kBoardCols / 2;    // column tiles per wave
+constexpr int kBoardLdsBytes = 160 * 1024;  // the LDS of a CU: a board launch asks for all of it
+constexpr int kBoardWaveLds = kBoardLdsBytes / 8;  // what the epilogue hands each of the 8 waves for its residual rows
 
 // Row order of the weight image for the GENERATED epilogue of the persistent launch (tower_seam.py epi_hook).  A lane of the
 // 16x16 accumulator layout holds rows 4q .. 4q+3 (q = lane >> 4) of each 16-row tile; a 16-byte store wants 8 CONSECUTIVE
@@ -149,7 +151,7 @@ template <int WMT_> struct BoardCfg {
     // K-loop rings; the launch always asks for the whole 160 KiB (one workgroup per CU either way): the epilogue hands
     // each wave 20 KiB of it for its residual rows
     static constexpr size_t ring_bytes(int npos) { return 2 * (size_t)A_BYTES + 2 * (size_t)npos * 64; }
-    static constexpr size_t lds_bytes(int npos) { return ring_bytes(npos) <= 160 * 1024 ? 160 * 1024 : ring_bytes(npos); }
+    static constexpr size_t lds_bytes(int npos) { return ring_bytes(npos) <= kBoardLdsBytes ? kBoardLdsBytes : ring_bytes(npos); }
 };
 
 // Measuring builds only (tools/gpu/lds_streams.sh): -DSAYURI_DROP_STREAM=1 leaves out the K loop's A-fragment reads, =2 its
@@ -517,9 +519,9 @@ __device__ __forceinline__ void board_epilogue(const BoardParams& bp, unsigned c
 
     if constexpr (!LONE) {
         // ---- even row-tile counts: residual through the dead LDS rings
-        constexpr int kWaveLds = 20 * 1024;                     // 160 KiB / 8 waves (the launch asks for all of the LDS)
+        constexpr int kWaveLds = kBoardWaveLds, kLdsPieces = kWaveLds / 1024;
         constexpr int kPieces = NJ * NPAIR;                      // residual pieces of a wave
-        constexpr int ND = kPieces > 20 ? kPieces - 20 : 0;      // pieces that go to registers instead (the first ones)
+        constexpr int ND = kPieces > kLdsPieces ? kPieces - kLdsPieces : 0;  // pieces that go to registers instead (the first ones)
         static_assert(ND % (NPAIR > 0 ? NPAIR : 1) == 0, "whole column tiles");
         int orow[NJ];
         f16x8 rrd[ND > 0 ? ND : 1];

@@ -27,19 +27,19 @@
 
 namespace sayuri {
 
-constexpr int kTowerStride = 320;  // bytes per TowerLayer in the device table (tower_seam.py: STRIDE)
+constexpr int kTowerStride = 320;  // bytes per TowerLayer in the device table (tower_seam.py steps by it: the hook's stride=)
 
 // One convolution of the run: an element of the device table the launch walks.
 struct alignas(16) TowerLayer {
     const TowerLayer* self;  // offset 0: the element's own address -- s[0:1] pointing AT an element is a valid kernarg
                              // segment for the compiled body, whose only argument is a pointer to the element
-    int last;                // offset 8 (tower_seam.py: LAST_OFFSET): 1 = the run ends with this layer
-    int has_se;              // the squeeze-and-excitation unit follows inside the kernel (sp.squeeze / sp.excite / sp.C valid)
+    int last;                // offset 8 (the hook's last=): 1 = the run ends with this layer
+    int has_se;              // (the hook's hasse=) the squeeze-and-excitation unit follows inside the kernel (sp.squeeze / sp.excite / sp.C valid)
     BoardSeParams sp;
     char pad[kTowerStride - 16 - sizeof(BoardSeParams)];
 };
 static_assert(sizeof(TowerLayer) == kTowerStride, "tower_seam.py steps the table by kTowerStride bytes");
-static_assert(offsetof(TowerLayer, self) == 0 && offsetof(TowerLayer, last) == 8, "tower_seam.py: SELF at 0, LAST at 8");
+static_assert(offsetof(TowerLayer, self) == 0, "the compiled bodies load their argument from s[0:1] + 0: the element itself");
 
 // The table lives in device memory and is never written while a launch runs: the body reads it through the constant
 // address space (scalar loads).  Such loads are invariant to the compiler, which would otherwise fetch every field up
@@ -121,14 +121,17 @@ __global__ __launch_bounds__(512, 2) void conv_tower_kernel(const TowerLayer* la
     int tid2 = tid;
     tower_anchor<WMT, 0>(acc);
     asm volatile("; TOWER_SE_HOOK elem=%0 tid=%1 wmt=%2 ui=%3 cols=%4 w1h=%5 w2h=%6 w1b=%7 w2b=%8 psum=%9 pmax=%10 gate=%11 kot=%12 "
-                 "res=%13 out=%14 couts=%15 slotpix=%16 act=%17 arith=%18 mish=%19 roword=%20 relu=%21 identity=%22"
+                 "res=%13 out=%14 couts=%15 slotpix=%16 act=%17 arith=%18 mish=%19 roword=%20 relu=%21 identity=%22 "
+                 "stride=%23 last=%24 hasse=%25 freev=%26 frees=%27 nj=%28 epilds=%29 lds=%30"
                  : "+s"(L2), "+v"(tid2)
                  : "n"(WMT), "n"(offsetof(TowerLayer, sp.b.uniform_info)), "n"(offsetof(TowerLayer, sp.b.tab_cols)),
                    "n"(offsetof(TowerLayer, sp.w1h)), "n"(offsetof(TowerLayer, sp.w2h)), "n"(offsetof(TowerLayer, sp.w1_bytes)),
                    "n"(offsetof(TowerLayer, sp.w2_bytes)), "n"(SeLds<WMT>::psum), "n"(SeLds<WMT>::pmax), "n"(SeLds<WMT>::gate),
                    "n"(BoardCfg<WMT>::KO_T), "n"(offsetof(TowerLayer, sp.b.c.res)), "n"(offsetof(TowerLayer, sp.b.c.out)),
                    "n"(offsetof(TowerLayer, sp.b.c.cout_s)), "n"(offsetof(TowerLayer, sp.b.c.g.slot_pix)), "n"(offsetof(TowerLayer, sp.b.c.act)),
-                   "n"(offsetof(TowerLayer, sp.b.arith)), "n"((int)kMish), "n"(offsetof(TowerLayer, sp.b.row_order)), "n"((int)kReLU), "n"((int)kIdentity)
+                   "n"(offsetof(TowerLayer, sp.b.arith)), "n"((int)kMish), "n"(offsetof(TowerLayer, sp.b.row_order)), "n"((int)kReLU), "n"((int)kIdentity),
+                   "n"(kTowerStride), "n"(offsetof(TowerLayer, last)), "n"(offsetof(TowerLayer, has_se)), "n"(kTowerFreeVgpr),
+                   "n"(kTowerFreeSgprs), "n"(kBoardNJ), "n"(kBoardWaveLds), "n"(kBoardLdsBytes)
                  : "memory", "vcc", "scc", SAYURI_TOWER_CLOBBER_V, SAYURI_TOWER_CLOBBER_S);
     const BoardSeParams& sp = *(const BoardSeParams*)&L2->sp;
     const BoardParams& bp = sp.b;
