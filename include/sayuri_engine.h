@@ -35,6 +35,23 @@ void* sayuri_pipe_create(const char* weights_path, int board, int batch, int fp1
  * sayuri_pipe_create.  A device library that lacks the flagged create entry point is an error only when a flag is set. */
 void* sayuri_pipe_create_ex(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms,
                             unsigned flags);
+/* the same with ensemble_slots = E (HipPipeConfig::ensemble_slots): every batch may expand up to E ensemble requests -- the eight
+ * board symmetries of one position as one request, include/sayuri_hip.h sayuri_hip_submit_packed_symm -- and every context
+ * takes batch + 7 E samples.  E = 0 is sayuri_pipe_create_ex. */
+void* sayuri_pipe_create_ens(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms,
+                             unsigned flags, int ensemble_slots);
+int sayuri_pipe_accepts_ensemble(void* pipe);       /* E > 0 and the device library in use has the entry point */
+long sayuri_pipe_ensemble_fallbacks(void* pipe);    /* ensemble requests served as a plain identity request (capacity) */
+/* one ensemble request from the calling thread: planes of one sample as for sayuri_pipe_eval mode 2, out [8][2*361 + 9] in
+ * sayuri_pipe_eval's packing; returns 8, or 1 when only out[0] (the identity) was evaluated, -1 on error */
+int sayuri_pipe_forward_ensemble(void* pipe, const float* planes, int board_size, float komi, int offset, float* out);
+/* test tap: n requests at once, request i sent as kind[i] -- 0 / 1 ForwardEnsemble from a fiber / an OS thread, 2 / 3
+ * ForwardPacked from a fiber / a thread, 4 Forward (fp32 planes) from a thread; the fibers share one pool over fiber_threads
+ * threads.  Arrays as for sayuri_pipe_eval, out [n][8][2*361 + 9], got[i] = results filled for request i (8 or 1) */
+int sayuri_pipe_ensemble_mix(void* pipe, int n, const float* planes, const int* board_sizes, const float* komi,
+                             const int* offsets, const int* kind, int fiber_threads, float* out, int* got);
+/* PackedPlanes::Symmetry on a record [binary*12 + 8] of a bs x bs board: the record Encoder::Packed builds for `symmetry` */
+int sayuri_packed_symmetry(const uint32_t* record, int binary, int bs, int symmetry, uint32_t* out);
 void sayuri_pipe_destroy(void* pipe);
 int sayuri_pipe_num_workers(void* pipe);
 void* sayuri_pipe_ctx(void* pipe, int gpu);                 /* the sayuri_hip_ctx of one GPU */
@@ -80,6 +97,9 @@ void* sayuri_engine_net_new_pipe(void* raw_pipe, int weights_version, const char
 void* sayuri_engine_net_new_callback(void* forward_fn, int kind, const void* user, int weights_version, const char* options);
 void sayuri_engine_net_free(void* net);
 unsigned long sayuri_engine_net_queries(void* net);
+/* NetworkOptions::device_ensemble (option "device_ensemble", default 1): kAverage as one ensemble request of a pipe that
+ * accepts them, or as eight evaluations in a row; the result is the same bit for bit */
+void sayuri_engine_net_set_device_ensemble(void* net, int on);
 void sayuri_engine_net_output(void* net, void* game, int ensemble, int symmetry, float temperature, int use_cache,
                               uint64_t seed, float* out /* [2N+9] */);
 void* sayuri_engine_search_new(void* game, void* net, const char* options);

@@ -151,6 +151,28 @@ int sayuri_hip_forward_packed(sayuri_hip_ctx* ctx, int n, const unsigned* record
                               float* prob, float* pass, float* misc, float* own);
 int sayuri_hip_submit_packed(sayuri_hip_ctx* ctx, int n, const unsigned* records, int binary_planes, const int* board_sizes,
                              float* prob, float* pass, float* misc, float* own, int* ticket);
+/* The same two entry points with a RECORD MAP and a BOARD SYMMETRY per device sample: the eight symmetries of a position
+ * (reference Network::kAverage, src/neural/network.cc:258) travel as ONE record and are expanded on the device.
+ *   n          device samples (<= max_batch); outputs are per device sample, in the caller's order, as above
+ *   records    [n_records] records as above (1 <= n_records <= max_batch)
+ *   src   [n]  the record of sample i, 0..n_records-1; several samples may name one record.  NULL = the identity map
+ *              (sample i reads record i; needs n <= n_records)
+ *   symm  [n]  the symmetry of sample i, 0..7: cell d = y*bs + x of the sample shows record cell Index(bs, symm, d) of
+ *              reference src/game/symmetry.cc:97-123 -- tx = x, ty = y; symm & 4: swap tx and ty; symm & 2: tx = bs-1-tx;
+ *              symm & 1: ty = bs-1-ty; source cell ty*bs + tx.  The broadcast planes are unaffected.  Sample i's outputs are
+ *              those of sayuri_hip_forward_packed on the record so permuted (the record Encoder::Packed builds for that
+ *              symmetry), bit for bit; the caller maps them back with its own tables.
+ *   board_sizes [n]  board_sizes[i] is the board size of record src[i]: the CALLER's contract, a record does not carry its
+ *              size.  NULL = all `board`.
+ * With symm all 0 and src the identity map the results are those of sayuri_hip_forward_packed.  A symm outside 0..7, a src
+ * outside the record array, n_records outside 1..max_batch or n outside 1..max_batch returns -1 with a message before
+ * anything is launched.  The two small tables are copied by the call (they need not outlive it, nor be page-locked). */
+int sayuri_hip_forward_packed_symm(sayuri_hip_ctx* ctx, int n, const unsigned* records, int n_records, int binary_planes,
+                                   const int* board_sizes, const int* src, const int* symm, float* prob, float* pass,
+                                   float* misc, float* own);
+int sayuri_hip_submit_packed_symm(sayuri_hip_ctx* ctx, int n, const unsigned* records, int n_records, int binary_planes,
+                                  const int* board_sizes, const int* src, const int* symm, float* prob, float* pass,
+                                  float* misc, float* own, int* ticket);
 int sayuri_hip_wait(sayuri_hip_ctx* ctx, int ticket);
 int sayuri_hip_query(sayuri_hip_ctx* ctx, int ticket); /* 1 = finished, 0 = still running, -1 = error */
 

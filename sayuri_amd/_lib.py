@@ -20,7 +20,7 @@ class KernelStat(ctypes.Structure):
 HIP_SYMBOLS = [
     "sayuri_hip_device_count", "sayuri_hip_create", "sayuri_hip_create_ex", "sayuri_hip_latency_state", "sayuri_hip_test_conv_split", "sayuri_hip_load_tensor", "sayuri_hip_forward",
     "sayuri_hip_submit", "sayuri_hip_wait", "sayuri_hip_query", "sayuri_hip_upload", "sayuri_hip_run", "sayuri_hip_sync", "sayuri_hip_download", "sayuri_hip_time_runs",
-    "sayuri_hip_forward_packed", "sayuri_hip_submit_packed", "sayuri_hip_profile_run", "sayuri_hip_mark_kernel", "sayuri_hip_timed_stat", "sayuri_hip_host_alloc", "sayuri_hip_host_free", "sayuri_hip_device_bytes", "sayuri_hip_last_chains", "sayuri_hip_tower_state",
+    "sayuri_hip_forward_packed", "sayuri_hip_submit_packed", "sayuri_hip_forward_packed_symm", "sayuri_hip_submit_packed_symm", "sayuri_hip_profile_run", "sayuri_hip_mark_kernel", "sayuri_hip_timed_stat", "sayuri_hip_host_alloc", "sayuri_hip_host_free", "sayuri_hip_device_bytes", "sayuri_hip_last_chains", "sayuri_hip_tower_state",
     "sayuri_hip_destroy", "sayuri_hip_last_error", "sayuri_hip_test_conv", "sayuri_hip_test_last_conv_kind",
     "sayuri_hip_test_se_unit", "sayuri_hip_test_head_tail", "sayuri_hip_test_conv_se", "sayuri_hip_test_head_board",
     "sayuri_hip_test_conv_sx", "sayuri_hip_test_last_sx_kts",
@@ -107,6 +107,16 @@ def host() -> ctypes.CDLL:
         lib.sayuri_pipe_create_ex.restype = ctypes.c_void_p
         lib.sayuri_pipe_create_ex.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_uint]
+        lib.sayuri_pipe_create_ens.restype = ctypes.c_void_p
+        lib.sayuri_pipe_create_ens.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_uint, ctypes.c_int]
+        lib.sayuri_pipe_accepts_ensemble.argtypes = [ctypes.c_void_p]
+        lib.sayuri_pipe_ensemble_fallbacks.restype = ctypes.c_long
+        lib.sayuri_pipe_ensemble_fallbacks.argtypes = [ctypes.c_void_p]
+        lib.sayuri_pipe_forward_ensemble.argtypes = [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, c_float_p]
+        lib.sayuri_pipe_ensemble_mix.argtypes = [ctypes.c_void_p, ctypes.c_int, c_float_p, c_int_p, c_float_p, c_int_p, c_int_p,
+                                                 ctypes.c_int, c_float_p, c_int_p]
+        lib.sayuri_packed_symmetry.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         lib.sayuri_pipe_destroy.argtypes = [ctypes.c_void_p]
         lib.sayuri_pipe_num_workers.argtypes = [ctypes.c_void_p]
         lib.sayuri_pipe_ctx.restype = ctypes.c_void_p

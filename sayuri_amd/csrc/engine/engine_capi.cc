@@ -115,6 +115,8 @@ void* sayuri_engine_net_new_callback(void* forward_fn, int kind, const void* use
 }
 void sayuri_engine_net_free(void* n) { delete static_cast<Network*>(n); }
 unsigned long sayuri_engine_net_queries(void* n) { return static_cast<Network*>(n)->GetNumQueries(); }
+// NetworkOptions::device_ensemble after construction (the option "device_ensemble=0/1" sets it at construction)
+void sayuri_engine_net_set_device_ensemble(void* n, int on) { static_cast<Network*>(n)->SetDeviceEnsemble(on != 0); }
 
 void sayuri_engine_net_output(void* n, void* game, int ensemble, int symmetry, float temperature, int use_cache,
                               std::uint64_t seed, float* out) {

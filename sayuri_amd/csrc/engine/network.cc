@@ -169,6 +169,49 @@ bool Network::ProbeCache(const GameState& state, Result& result) {
     return false;
 }
 
+// kAverage (network.cc:258): the mean over the eight board symmetries.  A function of its own: its eight raw results stay off
+// the stack of every other evaluation.
+Network::Result Network::GetAverage(const GameState& state, const Query& query, Rng& rng) {
+    Result result;
+    constexpr int k = SymmetryTables::kCount;
+    // One ensemble request when the pipe expands symmetries on the device: the position is encoded once (the record of
+    // symmetry s is a cell permutation of the identity's) and makes one trip; raw[s] is then what the pipe would have
+    // returned for Encoder::Packed(state, s).  A pipe that had no room returns false with raw[0] alone.
+    Result raw[k];
+    int have = 0;
+    if (Valid() && opt_.packed_inputs && opt_.device_ensemble && pipe_->AcceptsEnsemble()) {
+        sayuri_host::PackedPlanes pk;
+        Encoder::Packed(state, SymmetryTables::kIdentity, version_, &pk);
+        pk.offset = static_cast<int>((query.offset == PolicyBufferOffset::kDefault) ? opt_.default_policy_offset : query.offset);
+        have = pipe_->ForwardEnsemble(pk, raw) ? k : 1;
+        num_queries_.fetch_add(static_cast<size_t>(have), std::memory_order_relaxed);
+    }
+    for (int symm = 0; symm < k; ++symm) {
+        Result one;
+        if (symm < have) {
+            one = raw[symm];
+            TransformResult(one, symm);
+        } else {
+            one = GetOutputInternal(state, symm, query.offset, rng);
+        }
+        const int n = one.board_size * one.board_size;
+        ActivatePolicy(one, query.temperature);
+        result.pass_probability += one.pass_probability / k;
+        result.wdl_winrate += one.wdl_winrate / k;
+        result.stm_winrate += one.stm_winrate / k;
+        result.final_score += one.final_score / k;
+        result.q_error += one.q_error / k;
+        result.score_error += one.score_error / k;
+        for (int i = 0; i < 3; ++i) result.wdl[i] += one.wdl[i] / k;
+        for (int i = 0; i < n; ++i) {
+            result.probabilities[i] += one.probabilities[i] / k;
+            result.ownership[i] += one.ownership[i] / k;
+        }
+        if (symm == SymmetryTables::kIdentity) result.ImportQueryInfo(one);
+    }
+    return result;
+}
+
 Network::Result Network::GetOutput(const GameState& state, Ensemble ensemble, Query query, Rng& rng) {
     if (ensemble == kDirect) {
         if (query.symmetry < 0 || query.symmetry >= SymmetryTables::kCount) query.symmetry = SymmetryTables::kIdentity;
@@ -183,24 +226,7 @@ Network::Result Network::GetOutput(const GameState& state, Ensemble ensemble, Qu
         return result;
     }
     if (ensemble == kAverage) {
-        constexpr int k = SymmetryTables::kCount;
-        for (int symm = 0; symm < k; ++symm) {
-            Result one = GetOutputInternal(state, symm, query.offset, rng);
-            const int n = one.board_size * one.board_size;
-            ActivatePolicy(one, query.temperature);
-            result.pass_probability += one.pass_probability / k;
-            result.wdl_winrate += one.wdl_winrate / k;
-            result.stm_winrate += one.stm_winrate / k;
-            result.final_score += one.final_score / k;
-            result.q_error += one.q_error / k;
-            result.score_error += one.score_error / k;
-            for (int i = 0; i < 3; ++i) result.wdl[i] += one.wdl[i] / k;
-            for (int i = 0; i < n; ++i) {
-                result.probabilities[i] += one.probabilities[i] / k;
-                result.ownership[i] += one.ownership[i] / k;
-            }
-            if (symm == SymmetryTables::kIdentity) result.ImportQueryInfo(one);
-        }
+        result = GetAverage(state, query, rng);
     } else {
         result = GetOutputInternal(state, query.symmetry, query.offset, rng);
         if (query.write_cache) cache_.Insert(state.GetHash(), result); // stored before the policy softmax

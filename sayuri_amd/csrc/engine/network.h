@@ -86,6 +86,8 @@ struct NetworkOptions {
     bool early_symm_cache{false};
     size_t cache_memory_mib{400};
     bool packed_inputs{true};  // compact planes (packed_planes.h) when the pipe takes them; false = 43 fp32 planes as the reference
+    bool device_ensemble{true};  // kAverage as ONE ensemble request when the pipe takes them (AcceptsEnsemble): one encode, one
+                                 // trip, the symmetries expanded on the device; false = eight evaluations in a row.  Same result.
 };
 
 class Network {
@@ -104,6 +106,7 @@ public:
     size_t GetNumQueries() const { return num_queries_.load(std::memory_order_relaxed); }
     PolicyBufferOffset GetDefaultPolicyOffset() const { return opt_.default_policy_offset; }
     int GetVersion() const { return version_; }
+    void SetDeviceEnsemble(bool on) { opt_.device_ensemble = on; }
     const ResultCache& cache() const { return cache_; }
     NetworkForwardPipe* pipe() const { return pipe_.get(); }
 
@@ -112,6 +115,7 @@ public:
 
 private:
     Result GetOutputInternal(const GameState& state, int symmetry, PolicyBufferOffset offset, Rng& rng);
+    Result GetAverage(const GameState& state, const Query& query, Rng& rng);
     bool ProbeCache(const GameState& state, Result& result); // network.cc:197-235
     Result DummyForward(const InputData& inputs, Rng& rng) const; // network.cc:144-165
 

@@ -130,6 +130,22 @@ int sayuri_hip_submit_packed(sayuri_hip_ctx* ctx, int n, const unsigned* records
     if (!ctx || !records || !ticket) return fail("submit_packed: null argument");
     return ctx->eng->submit(n, nullptr, board_sizes, prob, pass, misc, own, ticket, records, binary_planes);
 }
+int sayuri_hip_forward_packed_symm(sayuri_hip_ctx* ctx, int n, const unsigned* records, int n_records, int binary_planes,
+                                   const int* board_sizes, const int* src, const int* symm, float* prob, float* pass, float* misc,
+                                   float* own) {
+    if (!ctx || !records || !symm) return fail("forward_packed_symm: null argument");
+    const SymmReq sy{n_records, src, symm};
+    if (ctx->eng->upload(n, nullptr, board_sizes, records, binary_planes, &sy)) return -1;
+    if (ctx->eng->run()) return -1;
+    return ctx->eng->download(prob, pass, misc, own);
+}
+int sayuri_hip_submit_packed_symm(sayuri_hip_ctx* ctx, int n, const unsigned* records, int n_records, int binary_planes,
+                                  const int* board_sizes, const int* src, const int* symm, float* prob, float* pass, float* misc,
+                                  float* own, int* ticket) {
+    if (!ctx || !records || !symm || !ticket) return fail("submit_packed_symm: null argument");
+    const SymmReq sy{n_records, src, symm};
+    return ctx->eng->submit(n, nullptr, board_sizes, prob, pass, misc, own, ticket, records, binary_planes, &sy);
+}
 int sayuri_hip_submit(sayuri_hip_ctx* ctx, int n, const float* planes, const int* board_sizes, float* prob,
                       float* pass, float* misc, float* own, int* ticket) {
     if (!ctx || !planes || !prob || !pass || !misc || !own || !ticket) return fail("submit: null argument");

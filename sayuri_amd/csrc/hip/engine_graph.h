@@ -6,19 +6,29 @@
 
 namespace sayuri {
 
+// A packed batch whose device samples name their record and board symmetry (sayuri_hip_forward_packed_symm): `n_records`
+// records in the caller's array, src[n] (null: sample i reads record i) and symm[n] in the caller's sample order.
+struct SymmReq {
+    int n_records = 0;
+    const int* src = nullptr;
+    const int* symm = nullptr;
+};
+
 class EngineBase {
 public:
     virtual ~EngineBase() {}
     virtual int load_tensor(int layer, int kind, const float* host, size_t n) = 0;
     // `packed` != null: the inputs are packed records (packed_planes.h) with `binary` bit planes, `planes` is ignored
-    virtual int upload(int n, const float* planes, const int* board_sizes, const unsigned* packed = nullptr, int binary = 0) = 0;
+    // `sy` != null (packed only): the records are expanded under a per-sample record map and symmetry (pack_bits_symm_kernel)
+    virtual int upload(int n, const float* planes, const int* board_sizes, const unsigned* packed = nullptr, int binary = 0,
+                       const SymmReq* sy = nullptr) = 0;
     virtual int run() = 0;
     virtual int sync() = 0;
     virtual int download(float* prob, float* pass, float* misc, float* own) = 0;
     virtual int time_runs(int iters, float* ms) = 0;
     virtual int profile_run(sayuri_hip_kernel_stat* rows, int cap) = 0;
     virtual int submit(int n, const float* planes, const int* bsz, float* prob, float* pass, float* misc, float* own,
-                       int* ticket, const unsigned* packed = nullptr, int binary = 0) = 0;
+                       int* ticket, const unsigned* packed = nullptr, int binary = 0, const SymmReq* sy = nullptr) = 0;
     virtual int wait(int ticket) = 0;
     virtual int query(int ticket) = 0;
     virtual int mark_kernel(const char* name) = 0;
@@ -166,7 +176,8 @@ public:
     // -------------------------------------------------------------- batch i/o
     // asynchronous: H2D, graph, D2H enqueued on the stream, an event marks the end
     int submit(int n, const float* planes, const int* board_sizes, float* prob, float* pass, float* misc, float* own,
-               int* ticket, const unsigned* packed = nullptr, int binary = 0) override {
+               int* ticket, const unsigned* packed = nullptr, int binary = 0, const SymmReq* sy = nullptr) override {
+        if (sy && check_symm(n, packed, *sy)) return -1;  // (before the ticket is taken: a refused call launches nothing)
         // The planes of batch k+1 cross PCIe while batch k computes, and the results of batch k while batch k+1 computes; each
         // of the two tickets owns its own device input / geometry / output buffers (and, by default, its own stream: below).
         const int t = next_ticket_;
@@ -190,7 +201,7 @@ public:
         hipStream_t up = inorder && !big_upload ? cs : h2d_stream_, down = inorder ? cs : d2h_stream_;
         if (!inorder) HIP_OK(hipStreamWaitEvent(h2d_stream_, fwd_done_[t], 0));  // the forward that last read this slot's inputs
         else if (big_upload && tick_ev_[t]) HIP_OK(hipStreamWaitEvent(h2d_stream_, tick_ev_[t], 0));
-        if (enqueue_inputs(t, n, planes, board_sizes, up, packed, binary, /*in_place=*/true)) return -1;
+        if (enqueue_inputs(t, n, planes, board_sizes, up, packed, binary, /*in_place=*/true, sy)) return -1;
         if (!inorder || big_upload) {
             HIP_OK(hipEventRecord(h2d_done_[t], h2d_stream_));
             HIP_OK(hipStreamWaitEvent(cs, h2d_done_[t], 0));
@@ -271,14 +282,16 @@ public:
         return fail(std::string("hipEventQuery: ") + hipGetErrorString(e));
     }
 
-    int upload(int n, const float* planes, const int* board_sizes, const unsigned* packed = nullptr, int binary = 0) override {
+    int upload(int n, const float* planes, const int* board_sizes, const unsigned* packed = nullptr, int binary = 0,
+               const SymmReq* sy = nullptr) override {
+        if (sy && check_symm(n, packed, *sy)) return -1;
         HIP_OK(hipSetDevice(device_));
         if (finalize()) return -1;
         HIP_OK(hipStreamSynchronize(h2d_stream_));
         HIP_OK(hipStreamSynchronize(d2h_stream_));
         for (hipStream_t cs : compute_)
             if (cs) HIP_OK(hipStreamSynchronize(cs));
-        if (enqueue_inputs(0, n, planes, board_sizes, compute_[0], packed, binary)) return -1;
+        if (enqueue_inputs(0, n, planes, board_sizes, compute_[0], packed, binary, false, sy)) return -1;
         HIP_OK(hipStreamSynchronize(compute_[0]));
         have_batch_ = true;
         return 0;
@@ -324,11 +337,29 @@ public:
     }
     std::map<int, IdentGeom> ident_;
 
+    // A symmetry request's arguments, checked before anything is enqueued.  The record array is bounded by max_batch: the copy
+    // path moves it into the slot's record buffer, which holds that many.
+    int check_symm(int n, const unsigned* packed, const SymmReq& sy) {
+        if (!packed || !sy.symm) return fail("packed_symm: null argument");
+        if (n <= 0 || n > max_batch_) return fail("batch size out of range");
+        if (sy.n_records <= 0 || sy.n_records > max_batch_)
+            return fail("packed_symm: n_records " + std::to_string(sy.n_records) + " out of range (1.." + std::to_string(max_batch_) + ")");
+        if (!sy.src && n > sy.n_records) return fail("packed_symm: the identity record map needs n <= n_records");
+        for (int i = 0; i < n; ++i) {
+            if (sy.symm[i] < 0 || sy.symm[i] > 7)
+                return fail("packed_symm: symm[" + std::to_string(i) + "] = " + std::to_string(sy.symm[i]) + " is no board symmetry (0..7)");
+            if (sy.src && (sy.src[i] < 0 || sy.src[i] >= sy.n_records))
+                return fail("packed_symm: src[" + std::to_string(i) + "] = " + std::to_string(sy.src[i]) + " is outside the " +
+                            std::to_string(sy.n_records) + " records");
+        }
+        return 0;
+    }
+
     // geometry + planes of ticket t to the device (no sync): the planes or packed records H2D on `copy_stream`, the geometry
     // arrays of a mixed batch from a 2-deep pinned ring (a second batch can be enqueued while the first is still in flight) on
     // the ticket's compute stream.
     int enqueue_inputs(int t, int n, const float* planes, const int* board_sizes, hipStream_t copy_stream, const unsigned* packed = nullptr,
-                       int binary = 0, bool in_place = false) {
+                       int binary = 0, bool in_place = false, const SymmReq* sy = nullptr) {
         HIP_OK(hipSetDevice(device_));
         if (n <= 0 || n > max_batch_) return fail("batch size out of range");
         if (packed && (binary <= 0 || binary > desc_.input_channels || desc_.input_channels - binary > 8 || board_ * board_ > 12 * 32))
@@ -402,8 +433,28 @@ public:
             HIP_OK(hipGetLastError());
         }
         io.packed_binary = packed ? binary : 0;
+        io.symm_on = packed && sy;
+        if (io.symm_on) {
+            // The record map and the symmetries (caller's order, a few hundred bytes): staged in a pinned ring like the geometry
+            // arrays and moved by a one-workgroup kernel on the forward's own stream, for the reason given there.  Ring and
+            // device arrays exist from the first such batch on: a ctx that never sees one holds what it always held.
+            if (!h_symm_) HIP_OK(hipHostMalloc((void**)&h_symm_, sizeof(int) * 2 * 2 * max_batch_, hipHostMallocDefault));
+            // (each pointer on its own: a second allocation that failed is tried again by the next batch.  Like every failure
+            // inside enqueue_inputs this one leaves submit()'s ticket taken and nothing enqueued on it.)
+            if (!io.sy_src && dev_alloc(&io.sy_src, max_batch_)) return -1;
+            if (!io.sy_symm && dev_alloc(&io.sy_symm, max_batch_)) return -1;
+            int* hs = h_symm_ + (size_t)symm_slot_ * 2 * max_batch_;
+            symm_slot_ ^= 1;
+            for (int i = 0; i < n; ++i) {
+                hs[i] = sy->src ? sy->src[i] : i;
+                hs[max_batch_ + i] = sy->symm[i];
+            }
+            hipLaunchKernelGGL(symm_stage_kernel, dim3(1), dim3(256), 0, compute_[t], (const int*)hs, max_batch_, n, io.sy_src, io.sy_symm);
+            HIP_OK(hipGetLastError());
+        }
         if (packed) {
             const size_t words = (size_t)binary * 12 + 8;
+            const int nrec = sy ? sy->n_records : n;
             // Packed records in device-addressable host memory (sayuri_hip_host_alloc: the pump's buffers) are not copied at all:
             // pack_bits_kernel reads the 1.8 KB per sample across PCIe itself.  The copy was 14 us of DMA -- but the copy engine
             // takes its packets in the order they were submitted, and the OTHER ticket's two downloads, submitted earlier and
@@ -415,7 +466,7 @@ public:
             if (in_place) io.packed_src = (const unsigned*)zc_device_pointer((float*)const_cast<unsigned*>(packed));
             if (io.packed_src) return 0;
             if (!io.packed && dev_alloc(&io.packed, (size_t)max_batch_ * (40 * 12 + 8))) return -1;
-            HIP_OK(hipMemcpyAsync(io.packed, packed, sizeof(unsigned) * n * words, hipMemcpyHostToDevice, copy_stream));
+            HIP_OK(hipMemcpyAsync(io.packed, packed, sizeof(unsigned) * nrec * words, hipMemcpyHostToDevice, copy_stream));
             return 0;
         }
         HIP_OK(hipMemcpyAsync(io.planes, planes, sizeof(float) * (size_t)n * desc_.input_channels * board_ * board_,
@@ -821,6 +872,8 @@ private:
         ident_.clear();
         if (h_geom_) (void)hipHostFree(h_geom_);
         h_geom_ = nullptr;
+        if (h_symm_) (void)hipHostFree(h_symm_);
+        h_symm_ = nullptr;
         for (IoSlot& io : io_) {
             if (io.sx_err_host) (void)hipHostFree(io.sx_err_host);
             io.sx_err_host = nullptr;
@@ -870,6 +923,8 @@ private:
         unsigned* packed = nullptr;  // packed records of the batch (allocated on first use)
         const unsigned* packed_src = nullptr;  // non-null: the batch's records are read where the caller has them (pinned host memory)
         int packed_binary = 0;       // > 0: the slot's current batch came as packed records with this many bit planes
+        bool symm_on = false;        // the current packed batch has a record map and symmetries (SymmReq) in sy_src / sy_symm
+        int *sy_src = nullptr, *sy_symm = nullptr;  // [max_batch], caller's order (allocated with the first such batch)
         int *off = nullptr, *bsz = nullptr, *perm = nullptr;  // a mixed batch's geometry arrays (enqueue_inputs)
         const int *g_off = nullptr, *g_bsz = nullptr, *g_perm = nullptr;  // the current batch's: off / bsz / perm, or resident ones
         T* bufs[kNumBufs] = {};
@@ -1364,6 +1419,11 @@ private:
             const unsigned* rec = io.packed_src ? io.packed_src : io.packed;
             const int split = io.packed_src ? 1 : kPackSplit;
             const int nbin = io.packed_binary, words = nbin * 12 + 8;
+            if (io.symm_on)
+                return timed(f, "pack_input", 0, (double)ns * words * 4 + px * cs * sizeof(T), [&] {
+                    hipLaunchKernelGGL(pack_bits_symm_kernel<T>, dim3(ns * split), dim3(256), 0, f.stream, rec, words, nbin, dst, g, cin, cs,
+                                       io.g_perm, (const int*)io.sy_src, (const int*)io.sy_symm, n0, split);
+                });
             return timed(f, "pack_input", 0, (double)ns * words * 4 + px * cs * sizeof(T), [&] {
                 hipLaunchKernelGGL(pack_bits_kernel<T>, dim3(ns * split), dim3(256), 0, f.stream, rec, words, nbin, dst, g, cin, cs,
                                    io.g_perm, n0, split);
@@ -1652,6 +1712,8 @@ private:
     size_t dev_bytes_ = 0;
     std::vector<int> perm_;  // device sample -> caller's slot (enqueue_inputs)
     float* d_zeros_ = nullptr;
+    int* h_symm_ = nullptr;  // pinned 2-slot ring: [slot][src(max_batch) | symm(max_batch)] (allocated with the first SymmReq batch)
+    int symm_slot_ = 0;
     int* h_geom_ = nullptr;  // pinned 2-slot ring: [slot][off(max_batch+1) | bsz(max_batch) | perm(max_batch)]
     int geom_slot_ = 0, next_ticket_ = 0;
     hipEvent_t tick_ev_[2] = {nullptr, nullptr};

@@ -168,6 +168,63 @@ __global__ __launch_bounds__(256) void pack_bits_kernel(const unsigned* __restri
     }
 }
 
+// The record map and the symmetries of a sayuri_hip_forward_packed_symm batch (caller's order), moved from the engine's pinned
+// staging ring to device memory by the forward's own stream, as geom_stage_kernel moves the geometry arrays: stage =
+// src[n] | symm[n] at a stride of max_batch.
+__global__ __launch_bounds__(256) void symm_stage_kernel(const int* __restrict__ stage, int max_batch, int n, int* __restrict__ src,
+                                                         int* __restrict__ symm) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        src[i] = stage[i];
+        symm[i] = stage[max_batch + i];
+    }
+}
+
+// pack_bits_kernel with a RECORD MAP and a SYMMETRY per sample (sayuri_hip_forward_packed_symm: the eight board symmetries of
+// one position evaluated in one batch from ONE record).  Device sample n has the caller's slot j = perm ? perm[n] : n; it reads
+// record src[j] of the caller's array -- several samples may name one record -- and writes that record's activations under
+// symmetry symm[j]: output cell d = y*bs + x of the bs x bs sample shows record cell Index(bs, symm, d), the engine's
+// SymmetryTables rule (csrc/engine/go_base.cc; reference src/game/symmetry.cc:97-123) computed here arithmetically, the
+// device library does not link the engine:
+//     tx = x, ty = y;  if (s & 4) swap(tx, ty);  if (s & 2) tx = bs-1-tx;  if (s & 1) ty = bs-1-ty;  source cell ty*bs + tx
+// The broadcast planes are one value per plane and know no symmetry.  As in pack_bits_kernel the record goes to LDS with one
+// coalesced read (an in-place record crosses PCIe once per workgroup that needs it) and thread = (output pixel, 16-byte piece)
+// in output order, so a wave's stores are whole contiguous rows; only the bit a thread picks from the LDS copy moves.
+// src_map / symm_map [n] in the caller's order (symm_stage_kernel above).
+template <typename T>
+__global__ __launch_bounds__(256) void pack_bits_symm_kernel(const unsigned* __restrict__ records, int rec_words, int nbin,
+                                                             T* __restrict__ out, BatchGeom g, int cin, int cs,
+                                                             const int* __restrict__ perm, const int* __restrict__ src_map,
+                                                             const int* __restrict__ symm_map, int n0, int split) {
+    constexpr int EPP = ElemTraits<T>::kPieceElems;
+    __shared__ unsigned rec[40 * 13 + 8];
+    const int n = n0 + blockIdx.x / split, part = blockIdx.x % split, tid = threadIdx.x;
+    const int bs = g.bsz[n], npix = bs * bs, ppr = cs / EPP;
+    const int per = (npix + split - 1) / split, pbeg = part * per, pend = min(npix, pbeg + per);
+    const int slot = perm ? perm[n] : n, s = symm_map[slot];
+    const unsigned* src = records + (size_t)src_map[slot] * rec_words;
+    for (int i = tid; i < rec_words; i += 256) rec[i < nbin * 12 ? (i / 12) * 13 + i % 12 : nbin * 13 + (i - nbin * 12)] = src[i];
+    __syncthreads();
+    T* dst = out + (size_t)n * g.slot_pix * cs;
+    for (int it = pbeg * ppr + tid; it < pend * ppr; it += 256) {
+        const int pp = it / ppr, piece = it - pp * ppr;
+        const int y = pp / bs, x = pp - y * bs;
+        int tx = (s & 4) ? y : x, ty = (s & 4) ? x : y;
+        if (s & 2) tx = bs - 1 - tx;
+        if (s & 1) ty = bs - 1 - ty;
+        const int q = ty * bs + tx, word = q >> 5, sh = q & 31;
+        T v[EPP];
+#pragma unroll
+        for (int e = 0; e < EPP; ++e) {
+            const int c = piece * EPP + e;
+            float f = 0.f;
+            if (c < nbin) f = (float)((rec[c * 13 + word] >> sh) & 1u);
+            else if (c < cin) f = __uint_as_float(rec[nbin * 13 + (c - nbin)]);
+            v[e] = from_float<T>(f);
+        }
+        *(uint4*)(dst + (size_t)it * EPP) = *(uint4*)v;
+    }
+}
+
 struct FcDev {
     const float* wt;  // transposed [in][out]
     const float* b;   // [out]

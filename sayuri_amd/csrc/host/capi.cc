@@ -102,7 +102,8 @@ long sayuri_weights_tensor(void* h, const char* name, float* dst, long cap) {
 }
 
 // ---- the pipe
-void* sayuri_pipe_create_ex(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms, unsigned flags) {
+void* sayuri_pipe_create_ens(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms, unsigned flags,
+                             int ensemble_slots) {
     try {
         auto h = std::make_unique<PipeHandle>();
         h->weights = std::make_shared<DNNWeights>();
@@ -117,6 +118,7 @@ void* sayuri_pipe_create_ex(const char* weights_path, int board, int batch, int 
         cfg.default_boardsize = board;
         cfg.gpu_waittime_ms = waittime_ms;
         cfg.hip_flags = flags;
+        cfg.ensemble_slots = ensemble_slots > 0 ? ensemble_slots : 0;
         if (device >= 0) cfg.gpus = {device};
         h->pipe = std::make_unique<HipForwardPipe>(cfg);
         h->pipe->Initialize(h->weights);
@@ -125,6 +127,10 @@ void* sayuri_pipe_create_ex(const char* weights_path, int board, int batch, int 
         g_err = e.what();
         return nullptr;
     }
+}
+
+void* sayuri_pipe_create_ex(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms, unsigned flags) {
+    return sayuri_pipe_create_ens(weights_path, board, batch, fp16, device, waittime_ms, flags, 0);
 }
 
 void* sayuri_pipe_create(const char* weights_path, int board, int batch, int fp16, int device, int waittime_ms) {
@@ -146,6 +152,21 @@ void sayuri_pipe_pump_times(void* hp, double* out8, long* batches, long* evals) 
     h->pipe->pump_times(out8);
     *batches = static_cast<long>(h->pipe->num_batches());
     *evals = static_cast<long>(h->pipe->num_evals());
+}
+// ensemble requests: does the pipe take them, and how many were served as a plain identity request (capacity fallback)
+int sayuri_pipe_accepts_ensemble(void* hp) { return static_cast<PipeHandle*>(hp)->pipe->AcceptsEnsemble() ? 1 : 0; }
+long sayuri_pipe_ensemble_fallbacks(void* hp) { return static_cast<long>(static_cast<PipeHandle*>(hp)->pipe->num_ensemble_fallbacks()); }
+// PackedPlanes::Symmetry on a record [binary*12 + 8] of a bs x bs board (tests)
+int sayuri_packed_symmetry(const std::uint32_t* record, int binary, int bs, int symmetry, std::uint32_t* out) {
+    if (!record || !out || binary <= 0 || binary > PackedPlanes::kMaxBinary || bs < 2 || bs > kBoardSize || symmetry < 0 || symmetry > 7) return -1;
+    PackedPlanes a, b;
+    a.Clear(binary);
+    a.board_size = bs;
+    std::memcpy(a.bits, record, sizeof(std::uint32_t) * PackedPlanes::kWords * static_cast<size_t>(binary));
+    std::memcpy(a.scalars, record + binary * PackedPlanes::kWords, sizeof(a.scalars));
+    a.Symmetry(symmetry, &b);
+    b.Store(out);
+    return 0;
 }
 int sayuri_pipe_num_workers(void* hp) { return static_cast<PipeHandle*>(hp)->pipe->GetNumWorkers(); }
 void* sayuri_pipe_ctx(void* hp, int gpu) { return static_cast<PipeHandle*>(hp)->pipe->ctx(gpu); }
@@ -279,6 +300,120 @@ extern "C" int sayuri_pipe_eval(void* hp, int mode, int gpu, int n, const float*
         g_err = e.what();
         return -1;
     }
+}
+
+// One ensemble request (HipForwardPipe::ForwardEnsemble) from the calling thread.  planes: one sample in InputData layout,
+// packable (sayuri_pipe_eval mode 2); out [8][2*361 + 9] in sayuri_pipe_eval's packing.  Returns 8 when all eight symmetries
+// were evaluated, 1 when only out[0] was (capacity fallback), -1 on error.
+extern "C" int sayuri_pipe_forward_ensemble(void* hp, const float* planes, int board_size, float komi, int offset, float* out) {
+    auto* h = static_cast<PipeHandle*>(hp);
+    if (!h || !planes || !out) return -1;
+    try {
+        const int C = h->weights->input_channels, nbin = PackedPlanes::BinaryPlanes(C), cells = board_size * board_size;
+        const int OL = 2 * kNumIntersections + 9;
+        PackedPlanes pk;
+        pk.Clear(nbin);
+        pk.board_size = board_size;
+        pk.komi = komi;
+        pk.offset = offset;
+        for (int c = 0; c < C; ++c) {
+            const float* pl = planes + static_cast<size_t>(c) * cells;
+            if (c >= nbin) { pk.scalars[c - nbin] = pl[0]; continue; }
+            for (int k = 0; k < cells; ++k)
+                if (pl[k] != 0.f) pk.Set(c, k);
+        }
+        std::vector<OutputResult> outs(8);
+        const int got = h->pipe->ForwardEnsemble(pk, outs.data()) ? 8 : 1;
+        for (int i = 0; i < got; ++i) {
+            float* o = out + static_cast<size_t>(i) * OL;
+            const OutputResult& r = outs[i];
+            std::memcpy(o, r.probabilities.data(), sizeof(float) * kNumIntersections);
+            std::memcpy(o + kNumIntersections, r.ownership.data(), sizeof(float) * kNumIntersections);
+            float* t = o + 2 * kNumIntersections;
+            t[0] = r.pass_probability; t[1] = r.wdl[0]; t[2] = r.wdl[1]; t[3] = r.wdl[2];
+            t[4] = r.stm_winrate; t[5] = r.final_score; t[6] = r.q_error; t[7] = r.score_error;
+            t[8] = static_cast<float>(static_cast<int>(r.offset));
+        }
+        return got;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
+#include "fiber.h"
+// Ensemble, packed and fp32 requests side by side, from fibers and from OS threads at once (tests/test_ensemble_cpu.py).
+// Request i -- planes [n][43*361] and the other arrays as for sayuri_pipe_eval, packable -- is sent as kind[i]:
+//   0 ForwardEnsemble from a fiber, 1 ForwardEnsemble from an OS thread of its own, 2 ForwardPacked from a fiber,
+//   3 ForwardPacked from a thread, 4 Forward (fp32 planes) from a thread.
+// The fibers run on one FiberPool over `fiber_threads` threads while the thread callers run.  out [n][8][2*361 + 9] in
+// sayuri_pipe_eval's packing, got[i] = results filled for request i (8, or 1).  Returns 0, -1 with the first error's text.
+extern "C" int sayuri_pipe_ensemble_mix(void* hp, int n, const float* planes, const int* board_sizes, const float* komi,
+                                        const int* offsets, const int* kind, int fiber_threads, float* out, int* got) {
+    auto* h = static_cast<PipeHandle*>(hp);
+    if (!h || n <= 0 || !planes || !board_sizes || !kind || !out || !got || fiber_threads <= 0) return -1;
+    const int PL = kInputChannels * kNumIntersections, OL = 2 * kNumIntersections + 9;
+    const int C = h->weights->input_channels, nbin = PackedPlanes::BinaryPlanes(C);
+    std::vector<std::vector<OutputResult>> outs(static_cast<size_t>(n), std::vector<OutputResult>(8));
+    std::vector<std::string> errs(static_cast<size_t>(n));
+    auto one = [&](int i) {
+        try {
+            const int bs = board_sizes[i], cells = bs * bs;
+            const float* src = planes + static_cast<size_t>(i) * PL;
+            if (kind[i] == 4) {
+                auto in = std::make_unique<InputData>();
+                in->board_size = bs;
+                in->komi = komi ? komi[i] : 7.5f;
+                in->offset = static_cast<PolicyBufferOffset>(offsets ? offsets[i] : 0);
+                std::memcpy(in->planes.data(), src, sizeof(float) * PL);
+                outs[i][0] = h->pipe->Forward(*in);
+                got[i] = 1;
+                return;
+            }
+            PackedPlanes pk;
+            pk.Clear(nbin);
+            pk.board_size = bs;
+            pk.komi = komi ? komi[i] : 7.5f;
+            pk.offset = offsets ? offsets[i] : 0;
+            for (int c = 0; c < C; ++c) {
+                const float* pl = src + static_cast<size_t>(c) * cells;
+                if (c >= nbin) { pk.scalars[c - nbin] = pl[0]; continue; }
+                for (int k = 0; k < cells; ++k)
+                    if (pl[k] != 0.f) pk.Set(c, k);
+            }
+            if (kind[i] <= 1) {
+                got[i] = h->pipe->ForwardEnsemble(pk, outs[i].data()) ? 8 : 1;
+            } else {
+                outs[i][0] = h->pipe->ForwardPacked(pk);
+                got[i] = 1;
+            }
+        } catch (const std::exception& e) {
+            errs[i] = e.what();
+            got[i] = 0;
+        }
+    };
+    sayuri_fiber::FiberPool pool;
+    std::vector<std::thread> th;
+    for (int i = 0; i < n; ++i) {
+        if (kind[i] == 0 || kind[i] == 2) pool.Add([&one, i] { one(i); });
+        else th.emplace_back([&one, i] { one(i); });
+    }
+    if (pool.size() > 0) pool.Run(fiber_threads);
+    for (auto& t : th) t.join();
+    for (int i = 0; i < n; ++i) {
+        if (!errs[i].empty()) { g_err = errs[i]; return -1; }
+        for (int s = 0; s < got[i]; ++s) {
+            float* o = out + (static_cast<size_t>(i) * 8 + s) * OL;
+            const OutputResult& r = outs[i][s];
+            std::memcpy(o, r.probabilities.data(), sizeof(float) * kNumIntersections);
+            std::memcpy(o + kNumIntersections, r.ownership.data(), sizeof(float) * kNumIntersections);
+            float* t = o + 2 * kNumIntersections;
+            t[0] = r.pass_probability; t[1] = r.wdl[0]; t[2] = r.wdl[1]; t[3] = r.wdl[2];
+            t[4] = r.stm_winrate; t[5] = r.final_score; t[6] = r.q_error; t[7] = r.score_error;
+            t[8] = static_cast<float>(static_cast<int>(r.offset));
+        }
+    }
+    return 0;
 }
 
 #include <atomic>

@@ -71,17 +71,21 @@ int BlockTypeCode(BlockBasic& b) {  // the reference's Is*Block() are non-const
 // library has none (an older build, or the serial stand-in of the host tests).  Looked up by name, and only when a flag is set: a
 // device library without the entry point keeps serving every pipe that asks for nothing new.
 typedef sayuri_hip_ctx* (*CreateExFn)(int, const sayuri_hip_netdesc*, int, int, int, unsigned);
-CreateExFn FindCreateEx() {
+void* FindInDeviceLibrary(const char* name) {
     Dl_info info;
     if (!dladdr(reinterpret_cast<void*>(&sayuri_hip_create), &info) || !info.dli_fname) return nullptr;
     void* lib = dlopen(info.dli_fname, RTLD_NOW | RTLD_NOLOAD);
     if (!lib) return nullptr;
-    void* sym = dlsym(lib, "sayuri_hip_create_ex");
+    void* sym = dlsym(lib, name);
     Dl_info where;  // (a handle's lookup also searches the library's dependencies: the entry point must be the library's own)
     if (sym && (!dladdr(sym, &where) || !where.dli_fname || std::strcmp(where.dli_fname, info.dli_fname) != 0)) sym = nullptr;
     dlclose(lib);  // drops the extra reference only: the library stays loaded
-    return reinterpret_cast<CreateExFn>(sym);
+    return sym;
 }
+CreateExFn FindCreateEx() { return reinterpret_cast<CreateExFn>(FindInDeviceLibrary("sayuri_hip_create_ex")); }
+// sayuri_hip_submit_packed_symm, looked up the same way (ensemble requests): a library without it serves everything else
+typedef int (*SubmitSymmFn)(sayuri_hip_ctx*, int, const unsigned*, int, int, const int*, const int*, const int*, float*, float*, float*,
+                            float*, int*);
 
 sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bool fp16, unsigned hip_flags) {
     std::vector<sayuri_hip_blockdesc> blocks(w.residual_blocks);
@@ -225,24 +229,33 @@ void HipForwardPipe::BuildGraphs() {
 
     const size_t B2 = static_cast<size_t>(board_size_) * board_size_;
     DNNWeights& w = *weights_;
+    // Ensemble requests: the contexts and the output / fp32 staging take the 7 extra samples of each of the E requests a batch
+    // can expand; with E = 0 (or a device library without the entry point) every size below is what it was.
+    submit_symm_ = cfg_.ensemble_slots > 0 ? FindInDeviceLibrary("sayuri_hip_submit_packed_symm") : nullptr;
+    const size_t dev_batch = static_cast<size_t>(AcceptsEnsemble() ? DeviceBatch() : max_batch_);
     for (int dev : devices) {
         auto g = std::make_unique<Graph>();
         g->device = dev;
-        g->ctx = BuildCtx(dev, w, max_batch_, board_size_, cfg_.fp16, cfg_.hip_flags);
+        g->ctx = BuildCtx(dev, w, static_cast<int>(dev_batch), board_size_, cfg_.fp16, cfg_.hip_flags);
         auto pinned = [&](size_t count) {
             float* p = static_cast<float*>(sayuri_hip_host_alloc(sizeof(float) * count));
             if (!p) ThrowHip("sayuri_hip_host_alloc");
             return p;
         };
         for (Staging& s : g->st) {
-            s.planes = pinned(static_cast<size_t>(max_batch_) * w.input_channels * B2);
+            s.planes = pinned(dev_batch * w.input_channels * B2);
             s.packed = reinterpret_cast<std::uint32_t*>(pinned(static_cast<size_t>(max_batch_) * PackedPlanes::RecordWords(BinaryPlanes())));
             s.is_packed.assign(max_batch_, 0);
-            s.prob = pinned(static_cast<size_t>(max_batch_) * w.probabilities_channels * B2);
-            s.pass = pinned(static_cast<size_t>(max_batch_) * w.pass_probability_outputs);
-            s.misc = pinned(static_cast<size_t>(max_batch_) * w.value_misc_outputs);
-            s.own = pinned(static_cast<size_t>(max_batch_) * B2);
-            s.bsz.assign(max_batch_, board_size_);
+            s.is_ens.assign(max_batch_, 0);
+            s.ens_base.assign(max_batch_, -1);
+            s.fin_ens_base.assign(max_batch_, -1);
+            s.dev_src.assign(dev_batch, 0);
+            s.dev_symm.assign(dev_batch, 0);
+            s.prob = pinned(dev_batch * w.probabilities_channels * B2);
+            s.pass = pinned(dev_batch * w.pass_probability_outputs);
+            s.misc = pinned(dev_batch * w.value_misc_outputs);
+            s.own = pinned(dev_batch * B2);
+            s.bsz.assign(dev_batch, board_size_);
             s.reqs.resize(max_batch_);
             s.fin_reqs.resize(max_batch_);
             s.fin_list.resize(max_batch_);
@@ -332,18 +345,19 @@ void HipForwardPipe::StagePacked(Staging* st, int slot, const PackedPlanes& in) 
     in.Store(st->packed + static_cast<size_t>(slot) * PackedPlanes::RecordWords(in.binary_planes));
 }
 
-// A packed slot of a batch that also holds fp32 requests: expand it into the fp32 staging (NN grid), pump thread.
-void HipForwardPipe::ExpandPacked(Staging* st, int slot) {
+// A packed slot of a batch that also holds fp32 requests: expand it into the fp32 staging (NN grid), pump thread.  An ensemble
+// slot's symmetries 1..7 go to their device samples the same way, each cell taken through PackedPlanes::SymmetryIndex.
+void HipForwardPipe::ExpandPacked(Staging* st, int slot, int dst_slot, int symmetry) {
     const int B = board_size_, bs = st->bsz[slot], C = weights_->input_channels, nbin = BinaryPlanes();
     const std::uint32_t* rec = st->packed + static_cast<size_t>(slot) * PackedPlanes::RecordWords(nbin);
-    float* dst = st->planes + static_cast<size_t>(slot) * C * B * B;
+    float* dst = st->planes + static_cast<size_t>(dst_slot) * C * B * B;
     std::memset(dst, 0, sizeof(float) * C * B * B);
     for (int c = 0; c < C; ++c) {
         float scalar = 0.f;
         if (c >= nbin) std::memcpy(&scalar, rec + nbin * PackedPlanes::kWords + (c - nbin), sizeof scalar);
         for (int y = 0; y < bs; ++y)
             for (int x = 0; x < bs; ++x) {
-                const int cell = y * bs + x;
+                const int cell = symmetry ? PackedPlanes::SymmetryIndex(bs, symmetry, y * bs + x) : y * bs + x;
                 dst[(static_cast<size_t>(c) * B + y) * B + x] =
                     c < nbin ? static_cast<float>((rec[c * PackedPlanes::kWords + (cell >> 5)] >> (cell & 31)) & 1u) : scalar;
             }
@@ -396,12 +410,39 @@ void HipForwardPipe::FillOutput(const Staging* g, int slot, const Echo& in, bool
 
 void HipForwardPipe::SubmitBatch(Graph* g, Staging* s, int n) {
     const auto t0 = Clock::now();
-    int npacked = 0;
+    int npacked = 0, nens = 0;
     for (int i = 0; i < n; ++i) npacked += s->is_packed[i];
+    // The device batch: the set's slots as they are, then symmetries 1..7 of every ensemble slot behind them.
+    for (int i = 0; i < n; ++i) {
+        s->ens_base[i] = -1;
+        if (!s->is_ens[i]) continue;
+        const int base = s->ens_base[i] = n + 7 * nens++;
+        for (int k = 0; k < 7; ++k) {
+            s->dev_src[base + k] = i;
+            s->dev_symm[base + k] = k + 1;
+            s->bsz[base + k] = s->bsz[i];
+        }
+    }
+    s->dev_n = n + 7 * nens;
     if (npacked > 0 && npacked < n)  // a mixed batch travels as fp32 planes
-        for (int i = 0; i < n; ++i)
-            if (s->is_packed[i]) ExpandPacked(s, i);
+        for (int i = 0; i < n; ++i) {
+            if (!s->is_packed[i]) continue;
+            ExpandPacked(s, i, i, 0);
+            for (int k = 0; k < 7 && s->ens_base[i] >= 0; ++k) ExpandPacked(s, i, s->ens_base[i] + k, k + 1);
+        }
     std::lock_guard<std::mutex> dev(g->dev_mu);
+    if (nens > 0) {
+        if (npacked == n) {
+            for (int i = 0; i < n; ++i) { s->dev_src[i] = i; s->dev_symm[i] = 0; }
+            if (reinterpret_cast<SubmitSymmFn>(submit_symm_)(g->ctx, s->dev_n, s->packed, n, BinaryPlanes(), s->bsz.data(), s->dev_src.data(),
+                                                             s->dev_symm.data(), s->prob, s->pass, s->misc, s->own, &s->ticket))
+                ThrowHip("sayuri_hip_submit_packed_symm");
+        } else if (sayuri_hip_submit(g->ctx, s->dev_n, s->planes, s->bsz.data(), s->prob, s->pass, s->misc, s->own, &s->ticket)) {
+            ThrowHip("sayuri_hip_submit");
+        }
+        pump_stat_[kSubmitCall] += Ns(Clock::now() - t0);
+        return;
+    }
     if (npacked == n ? sayuri_hip_submit_packed(g->ctx, n, s->packed, BinaryPlanes(), s->bsz.data(), s->prob, s->pass, s->misc, s->own, &s->ticket)
                      : sayuri_hip_submit(g->ctx, n, s->planes, s->bsz.data(), s->prob, s->pass, s->misc, s->own, &s->ticket))
         ThrowHip(npacked == n ? "sayuri_hip_submit_packed" : "sayuri_hip_submit");
@@ -423,6 +464,7 @@ void HipForwardPipe::FinishBatch(Graph* g, Staging* s, int n) {
     for (int i = 0; i < n; ++i) {
         const Request& r = s->reqs[i];
         s->fin_reqs[i] = r;
+        s->fin_ens_base[i] = s->ens_base[i];
         if (r.fiber) {
             ++fibers;  // flagged below, once fin_status is in place
         } else if (r.self_serve) {
@@ -435,7 +477,7 @@ void HipForwardPipe::FinishBatch(Graph* g, Staging* s, int n) {
         }
     }
     batches_.fetch_add(1, std::memory_order_relaxed);
-    evals_.fetch_add(static_cast<size_t>(n), std::memory_order_relaxed);
+    evals_.fetch_add(static_cast<size_t>(std::max(n, s->dev_n)), std::memory_order_relaxed);
     s->fin_count = count;
     s->fin_fibers = fibers;
     s->wakes_done.store(0, std::memory_order_relaxed);
@@ -468,6 +510,8 @@ void HipForwardPipe::AnnounceEpoch(Graph* g) {
 
 void HipForwardPipe::Reopen(Graph* g, Staging* s) {
     s->ready.store(0, std::memory_order_relaxed);
+    s->ens_taken.store(0, std::memory_order_relaxed);
+    s->dev_n = 0;
     s->reserved.store(0, std::memory_order_release);  // re-open for callers
     AnnounceEpoch(g);
 }
@@ -631,7 +675,7 @@ void HipForwardPipe::PumpLoop(Graph* g) {
 }
 
 HipForwardPipe::Ticket HipForwardPipe::Reserve(const InputData* input, const PackedPlanes* packed, OutputResult* out,
-                                               std::atomic<int>* done, bool self_serve, bool fiber) {
+                                               std::atomic<int>* done, bool self_serve, bool fiber, bool ensemble) {
     if (graphs_.empty()) throw std::runtime_error("HipForwardPipe is not constructed");
     const Echo echo = EchoOf(input, packed);
     if (echo.board_size < 2 || echo.board_size > board_size_)
@@ -659,6 +703,8 @@ HipForwardPipe::Ticket HipForwardPipe::Reserve(const InputData* input, const Pac
                 if (input) StageInput(&s, slot, *input, false);
                 else StagePacked(&s, slot, *packed);
                 s.is_packed[slot] = input ? 0 : 1;
+                // an ensemble request expands while the set has capacity left; past it the slot is a plain identity request
+                s.is_ens[slot] = ensemble && s.ens_taken.fetch_add(1, std::memory_order_relaxed) < cfg_.ensemble_slots ? 1 : 0;
                 s.reqs[slot] = Request{echo, out, done, self_serve, fiber};
                 s.ready.fetch_add(1, std::memory_order_release);
                 if (r == 0 || r + 1 >= want) g->cv.notify_one();
@@ -683,9 +729,24 @@ void HipForwardPipe::Submit(const InputData& input, OutputResult* out, std::atom
     Reserve(&input, nullptr, out, done, false);
 }
 
-OutputResult HipForwardPipe::Forward(const InputData& input) { return ForwardAny(&input, nullptr); }
+OutputResult HipForwardPipe::Forward(const InputData& input) {
+    OutputResult out;
+    ForwardAny(&input, nullptr, &out);
+    return out;
+}
 
-OutputResult HipForwardPipe::ForwardPacked(const PackedPlanes& input) { return ForwardAny(nullptr, &input); }
+OutputResult HipForwardPipe::ForwardPacked(const PackedPlanes& input) {
+    OutputResult out;
+    ForwardAny(nullptr, &input, &out);
+    return out;
+}
+
+bool HipForwardPipe::ForwardEnsemble(const PackedPlanes& identity, OutputResult out[8]) {
+    if (!AcceptsEnsemble()) throw std::runtime_error("HipForwardPipe: ensemble requests are off (ensemble_slots = 0, or a device library without sayuri_hip_submit_packed_symm)");
+    const bool all = ForwardAny(nullptr, &identity, &out[0], out);
+    if (!all) ens_fallbacks_.fetch_add(1, std::memory_order_relaxed);
+    return all;
+}
 
 HipForwardPipe::Echo HipForwardPipe::EchoOf(const InputData* input, const PackedPlanes* packed) {
     return input ? Echo{input->board_size, input->offset, input->komi}
@@ -693,29 +754,34 @@ HipForwardPipe::Echo HipForwardPipe::EchoOf(const InputData* input, const Packed
 }
 
 // A Forward() caller copies its own result out of its set's pinned outputs, and says so: the set's next batch waits for that.
-void HipForwardPipe::TakeResult(Staging* s, int slot, const Echo& echo, int status, OutputResult* out) const {
-    if (status > 0) FillOutput(s, slot, echo, true, out);
+// An ensemble request's symmetries 1..7 lie at the device samples FinishBatch's snapshot names; true when they were taken.
+bool HipForwardPipe::TakeResult(Staging* s, int slot, const Echo& echo, int status, OutputResult* out, OutputResult* ens_out) const {
+    const int base = ens_out ? s->fin_ens_base[slot] : -1;
+    if (status > 0) {
+        FillOutput(s, slot, echo, true, out);
+        for (int k = 0; k < 7 && base >= 0; ++k) FillOutput(s, base + k, echo, true, &ens_out[k + 1]);
+    }
     s->consumed.fetch_add(1, std::memory_order_release);
     if (status < 0) ThrowBatchFailed();
+    return base >= 0;
 }
 
-OutputResult HipForwardPipe::ForwardAny(const InputData* in, const PackedPlanes* pk) {
-    OutputResult out;
+bool HipForwardPipe::ForwardAny(const InputData* in, const PackedPlanes* pk, OutputResult* outp, OutputResult* ens_out) {
+    OutputResult& out = *outp;
     std::atomic<int> done{0};
     const Echo echo = EchoOf(in, pk);
     if (sayuri_fiber::InFiber()) {
         // M:N game scheduling (fiber.h): hand the request over and run this thread's other games until the batch is back
-        const Ticket t = Reserve(in, pk, nullptr, &done, false, true);
+        const Ticket t = Reserve(in, pk, nullptr, &done, false, true, ens_out != nullptr);
         sayuri_fiber::WaitWhileEqual(&done, 0);
         if (trace_.on) {
             const long long now = Trace::now_ns();
             Trace::Count(trace_.resume[Trace::bin250us(now - trace_.last_done_ns.load(std::memory_order_relaxed))]);
             if (long long* st = sayuri_fiber::FiberStamp()) *st = now;
         }
-        TakeResult(t.s, t.slot, echo, done.load(std::memory_order_acquire), &out);
-        return out;
+        return TakeResult(t.s, t.slot, echo, done.load(std::memory_order_acquire), &out, ens_out);
     }
-    const Ticket t = Reserve(in, pk, nullptr, &done, true);
+    const Ticket t = Reserve(in, pk, nullptr, &done, true, false, ens_out != nullptr);
     int st;
     while ((st = done.load(std::memory_order_acquire)) == 0) FutexWait(&done, 0);
     if (st < 0) ThrowBatchFailed();  // the batch was never submitted: no tree, nothing to take
@@ -728,8 +794,7 @@ OutputResult HipForwardPipe::ForwardAny(const InputData* in, const PackedPlanes*
         FutexWakeAll(child);
     }
     s.wakes_done.fetch_add(1, std::memory_order_release);
-    TakeResult(&s, t.slot, echo, s.fin_status.load(std::memory_order_relaxed), &out);
-    return out;
+    return TakeResult(&s, t.slot, echo, s.fin_status.load(std::memory_order_relaxed), &out, ens_out);
 }
 
 std::vector<OutputResult> HipForwardPipe::BatchForward(int gpu, const std::vector<InputData>& inputs) {

@@ -55,6 +55,8 @@ struct HipPipeConfig {
     int default_boardsize{kBoardSize};
     int fixed_nn_boardsize{0};
     unsigned hip_flags{0};       // sayuri_hip_create_ex flags of every GPU's context (SAYURI_HIP_LATENCY); 0 = sayuri_hip_create
+    int ensemble_slots{0};       // E: ensemble requests (ForwardEnsemble) a batch can expand on the device; every context gets
+                                 // batch_size + 7 * E device samples.  0 = off: the pipe and its contexts are as without it
 };
 
 // What the pump thread keeps count of, in the order pump_times() reports it: time spent ...
@@ -89,6 +91,14 @@ public:
     // the packed ones into the fp32 staging first.
     OutputResult ForwardPacked(const PackedPlanes& input) SAYURI_EXT_OVERRIDE;
     bool AcceptsPacked() const SAYURI_EXT_OVERRIDE { return true; }
+
+    // The eight board symmetries of one position as ONE request (one slot of the batch, one record over PCIe): the device
+    // expands the record under symmetries 1..7 into extra samples behind the batch's own (sayuri_hip_submit_packed_symm).
+    // A batch expands at most ensemble_slots requests; one that comes after them is served as a plain identity request --
+    // false, out[0] filled, the caller evaluates symmetries 1..7 through ForwardPacked (counted in num_ensemble_fallbacks).
+    bool AcceptsEnsemble() const SAYURI_EXT_OVERRIDE { return cfg_.ensemble_slots > 0 && submit_symm_ != nullptr; }
+    bool ForwardEnsemble(const PackedPlanes& identity, OutputResult out[8]) SAYURI_EXT_OVERRIDE;
+    size_t num_ensemble_fallbacks() const { return ens_fallbacks_.load(std::memory_order_relaxed); }
 
     // batch_forward_pipe.h:27-28.  `inputs` are already re-padded into the NN grid.
     std::vector<OutputResult> BatchForward(int gpu, const std::vector<InputData>& inputs);
@@ -133,6 +143,12 @@ private:
         float* planes{nullptr};
         std::uint32_t* packed{nullptr};      // packed records of the slots filled through ForwardPacked (pinned)
         std::vector<std::uint8_t> is_packed;  // per slot: its planes are in `packed`, not in `planes`
+        std::vector<std::uint8_t> is_ens;     // per slot: an ensemble request this batch expands (ForwardEnsemble)
+        std::atomic<int> ens_taken{0};        // ensemble requests of the set, counted AFTER the slot is taken: the first E expand
+        // pump-private, SubmitBatch: the batch's device samples [0, n) are its slots; expanded slot i has symmetries 1..7 at
+        // ens_base[i] .. ens_base[i] + 6, behind n.  fin_ens_base is FinishBatch's snapshot of it (-1: not expanded)
+        std::vector<int> ens_base, fin_ens_base, dev_src, dev_symm;
+        int dev_n{0};                         // device samples of the submitted batch: n + 7 * expanded slots
         float *prob{nullptr}, *pass{nullptr}, *misc{nullptr}, *own{nullptr};
         std::vector<int> bsz;
         std::vector<Request> reqs;
@@ -195,9 +211,11 @@ private:
     static Echo EchoOf(const InputData* input, const PackedPlanes* packed);
     // exactly one of input / packed is non-null
     Ticket Reserve(const InputData* input, const PackedPlanes* packed, OutputResult* out, std::atomic<int>* done, bool self_serve,
-                   bool fiber = false);
-    OutputResult ForwardAny(const InputData* input, const PackedPlanes* packed);
-    void TakeResult(Staging* s, int slot, const Echo& echo, int status, OutputResult* out) const;
+                   bool fiber = false, bool ensemble = false);
+    // ens_out: null, or the eight results of an ensemble request (out = ens_out[0]); returns whether all eight were filled
+    bool ForwardAny(const InputData* input, const PackedPlanes* packed, OutputResult* out, OutputResult* ens_out = nullptr);
+    bool TakeResult(Staging* s, int slot, const Echo& echo, int status, OutputResult* out, OutputResult* ens_out = nullptr) const;
+    int DeviceBatch() const { return max_batch_ + 7 * std::max(cfg_.ensemble_slots, 0); }
     int BinaryPlanes() const;
     // forwarding size, read live: Construct() may lower it while the pump runs (no rebuild)
     unsigned WantNow() const { return static_cast<unsigned>(std::min(forward_size_.load(std::memory_order_acquire), max_batch_)); }
@@ -216,7 +234,7 @@ private:
     void FinishBatch(Graph* g, Staging* s, int n);
     void StageInput(Staging* s, int slot, const InputData& in, bool already_padded);
     void StagePacked(Staging* s, int slot, const PackedPlanes& in);
-    void ExpandPacked(Staging* s, int slot);
+    void ExpandPacked(Staging* s, int slot, int dst_slot, int symmetry);
     void FillOutput(const Staging* s, int slot, const Echo& in, bool unpad, OutputResult* out) const;
 
     HipPipeConfig cfg_;
@@ -226,7 +244,8 @@ private:
     std::vector<std::unique_ptr<Graph>> graphs_;
     std::atomic<bool> running_{false};
     std::atomic<unsigned> next_graph_{0};
-    std::atomic<size_t> batches_{0}, evals_{0};
+    std::atomic<size_t> batches_{0}, evals_{0}, ens_fallbacks_{0};
+    void* submit_symm_{nullptr};  // sayuri_hip_submit_packed_symm of the device library in use, null when it has none
     mutable std::atomic<long long> pump_stat_[kPumpCounters] = {};  // nanoseconds, but kPartialBatches: a count
     struct PumpTimer;  // adds its own lifetime to one of them
     std::atomic<int> epoch_parked_{0};  // fibers suspended in Reserve() until a staging set re-opens

@@ -44,6 +44,29 @@ struct PackedPlanes {
         std::memcpy(record, bits, sizeof(std::uint32_t) * kWords * static_cast<size_t>(binary_planes));
         std::memcpy(record + binary_planes * kWords, scalars, sizeof(scalars));
     }
+    // Source cell of output cell d = y*bs + x under board symmetry s (0..7): SymmetryTables::Index (csrc/engine/go_base.cc;
+    // reference src/game/symmetry.cc:97-123), computed -- this header stands alone: s & 4 swaps x and y, s & 2 mirrors x,
+    // s & 1 mirrors y.
+    static int SymmetryIndex(int bs, int s, int d) {
+        int ty = d / bs, tx = d - ty * bs;
+        if (s & 4) { const int t = tx; tx = ty; ty = t; }
+        if (s & 2) tx = bs - 1 - tx;
+        if (s & 1) ty = bs - 1 - ty;
+        return ty * bs + tx;
+    }
+    // *out = these planes as the encoder builds them for symmetry s when *this is the identity's (Encoder::Packed takes the
+    // identity planes through the symmetry map): cell d of every bit plane shows cell SymmetryIndex(d), the rest is copied.
+    void Symmetry(int s, PackedPlanes* out) const {
+        out->komi = komi; out->board_size = board_size; out->side_to_move = side_to_move; out->offset = offset;
+        out->Clear(binary_planes);
+        std::memcpy(out->scalars, scalars, sizeof(scalars));
+        const int n = board_size * board_size;
+        for (int d = 0; d < n; ++d) {
+            const int q = SymmetryIndex(board_size, s, d);
+            for (int c = 0; c < binary_planes; ++c)
+                if (Get(c, q)) out->Set(c, d);
+        }
+    }
     // fp32 planes [channels][board_size^2] -- what InputData::planes would hold
     void Expand(int channels, float* planes) const {
         const int n = board_size * board_size;

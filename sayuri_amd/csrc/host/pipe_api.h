@@ -97,6 +97,12 @@ public:
     // packed_planes.h says so, and the engine's encoder then never materialises the 43 fp32 planes.
     virtual bool AcceptsPacked() const { return false; }
     virtual OutputResult ForwardPacked(const PackedPlanes&) { throw std::runtime_error("this pipe does not take packed planes"); }
+    // Extension: the eight board symmetries of ONE position in one request (reference Network::kAverage).  `identity` is the
+    // identity symmetry's planes; out[s] receives the raw result of the planes under symmetry s, as ForwardPacked would give
+    // it for Encoder::Packed(state, s).  false: only out[0] was filled (the pipe had no room to expand this request) and the
+    // caller evaluates the other seven one by one.
+    virtual bool AcceptsEnsemble() const { return false; }
+    virtual bool ForwardEnsemble(const PackedPlanes&, OutputResult*) { throw std::runtime_error("this pipe does not take ensemble requests"); }
     std::string GetName() const;
     int GetVersion() const;
     std::shared_ptr<DNNWeights> weights_{nullptr};

@@ -67,11 +67,16 @@ class HipForwardPipe:
     """One process, one pipe; `device` = -1 uses every visible GPU (one pump thread each)."""
 
     def __init__(self, weights_path: str, board_size: int = MAX_BOARD, batch_size: int = 256, fp16: bool = True,
-                 device: int = 0, waittime_ms: int = 2, latency: bool = False):
+                 device: int = 0, waittime_ms: int = 2, latency: bool = False, ensemble: int = 0):
         """latency: a latency context per GPU (include/sayuri_hip.h, SAYURI_HIP_LATENCY) -- every 3x3 tower convolution cut
-        into many small workgroups, for the batches of 1 to 16 positions of a playing or analysing engine.  fp16 only."""
+        into many small workgroups, for the batches of 1 to 16 positions of a playing or analysing engine.  fp16 only.
+        ensemble: E > 0 lets every batch expand up to E ensemble requests (ForwardEnsemble; Network kAverage) on the device:
+        the contexts take batch_size + 7 * E samples.  0 = off, the pipe as without the argument."""
         lib = _lib.host()
-        if latency:
+        if ensemble:
+            self._h = lib.sayuri_pipe_create_ens(weights_path.encode(), board_size, batch_size, int(fp16), device,
+                                                 waittime_ms, HIP_LATENCY if latency else 0, int(ensemble))
+        elif latency:
             self._h = lib.sayuri_pipe_create_ex(weights_path.encode(), board_size, batch_size, int(fp16), device,
                                                 waittime_ms, HIP_LATENCY)
         else:
@@ -83,6 +88,7 @@ class HipForwardPipe:
         self.batch_size = batch_size
         self.fp16 = fp16
         self.latency = latency
+        self.ensemble = int(ensemble)
 
     # -- NetworkForwardPipe surface
     def Valid(self) -> bool:
@@ -168,6 +174,49 @@ class HipForwardPipe:
         """n concurrent blocking Forward() calls through the batching queue."""
         return self._eval(1, planes, board_sizes, komi, offsets)
 
+    def AcceptsEnsemble(self) -> bool:
+        return bool(_lib.host().sayuri_pipe_accepts_ensemble(self._h))
+
+    def ensemble_fallbacks(self) -> int:
+        """Ensemble requests that found their batch's capacity used up and were served as a plain identity request."""
+        return int(_lib.host().sayuri_pipe_ensemble_fallbacks(self._h))
+
+    def ForwardEnsemble(self, planes, board_size: int, komi: float = 7.5, offset: int = 0):
+        """One position's identity planes (packable, as for ForwardPacked) -> (all, results): results[s] is the raw result of
+        the planes under board symmetry s in Forward()'s packing; all is False when only results[0] was evaluated."""
+        flat = np.zeros(PLANES_LEN, np.float32)
+        p = np.ascontiguousarray(planes, np.float32).ravel()
+        flat[:p.size] = p
+        out = np.zeros((8, OUT_LEN), np.float32)
+        rc = _lib.host().sayuri_pipe_forward_ensemble(self._h, _fp(flat), board_size, komi, offset, _fp(out))
+        if rc < 0:
+            raise RuntimeError(_lib.host().sayuri_host_last_error().decode())
+        s = board_size * board_size
+        return rc == 8, [np.concatenate([out[i, :s], out[i, 361:361 + s], out[i, 722:]]) for i in range(8 if rc == 8 else 1)]
+
+    def ensemble_mix(self, planes, board_sizes, kinds, komi=None, offsets=None, fiber_threads: int = 2):
+        """Test tap (sayuri_pipe_ensemble_mix): the requests at once, request i as kinds[i] -- 0 / 1 ForwardEnsemble from a
+        fiber / an OS thread, 2 / 3 ForwardPacked from a fiber / a thread, 4 Forward from a thread.  -> per request the list
+        of its results (eight, or one) in Forward()'s packing."""
+        n = len(planes)
+        buf = np.zeros((n, PLANES_LEN), np.float32)
+        for i, p in enumerate(planes):
+            flat = np.ascontiguousarray(p, np.float32).ravel()
+            buf[i, :flat.size] = flat
+        bsz = np.asarray(board_sizes, np.int32)
+        km = np.asarray(komi if komi is not None else [7.5] * n, np.float32)
+        off = np.asarray(offsets if offsets is not None else [0] * n, np.int32)
+        kd = np.asarray(kinds, np.int32)
+        out = np.zeros((n, 8, OUT_LEN), np.float32)
+        got = np.zeros(n, np.int32)
+        if _lib.host().sayuri_pipe_ensemble_mix(self._h, n, _fp(buf), _ip(bsz), _fp(km), _ip(off), _ip(kd), fiber_threads, _fp(out), _ip(got)):
+            raise RuntimeError(_lib.host().sayuri_host_last_error().decode())
+        res = []
+        for i in range(n):
+            s = int(bsz[i]) ** 2
+            res.append([np.concatenate([out[i, k, :s], out[i, k, 361:361 + s], out[i, k, 722:]]) for k in range(int(got[i]))])
+        return res
+
     def ForwardPacked(self, planes, board_sizes, komi=None, offsets=None, mixed: bool = False):
         """The same through ForwardPacked() (csrc/host/packed_planes.h): the planes are packed into bit planes + scalars on
         the way in (they must be packable: 0/1 binary planes, constant scalar planes).  mixed: odd requests packed, even
@@ -206,5 +255,46 @@ def hip_forward_packed_raw(ctx: int, records: np.ndarray, binary: int, board_siz
     misc = np.zeros((n, misc_outs), np.float32)
     own = np.zeros((n, board * board), np.float32)
     if lib.sayuri_hip_forward_packed(ctx, n, records.ctypes.data, binary, _ip(bsz), _fp(prob), _fp(pas), _fp(misc), _fp(own)):
+        raise RuntimeError(lib.sayuri_hip_last_error().decode())
+    return prob, pas, misc, own
+
+
+def packed_symmetry(record: np.ndarray, binary: int, board_size: int, symmetry: int) -> np.ndarray:
+    """PackedPlanes::Symmetry (csrc/host/packed_planes.h): the record the encoder builds for `symmetry` from the identity's."""
+    record = np.ascontiguousarray(record, np.uint32)
+    out = np.zeros_like(record)
+    if _lib.host().sayuri_packed_symmetry(record.ctypes.data, binary, board_size, symmetry, out.ctypes.data):
+        raise ValueError("packed_symmetry: bad arguments")
+    return out
+
+
+_SYMM_ARGS = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _lib.c_int_p, _lib.c_int_p, _lib.c_int_p,
+              _lib.c_float_p, _lib.c_float_p, _lib.c_float_p, _lib.c_float_p]
+
+
+def hip_forward_packed_symm_raw(ctx: int, records, binary: int, board_sizes, src, symm, board: int, prob_ch: int = 5,
+                                pass_outs: int = 5, misc_outs: int = 15, n_records: Optional[int] = None):
+    """sayuri_hip_forward_packed_symm: device sample i = record src[i] (None: the identity map) under board symmetry symm[i]
+    -> prob, pass, misc, own per device sample.  records: uint32 [n_records][binary*12 + 8], or the address of such an array
+    (memory from sayuri_hip_host_alloc) with n_records given."""
+    lib = _lib.hip()
+    lib.sayuri_hip_forward_packed_symm.argtypes = _SYMM_ARGS
+    if isinstance(records, np.ndarray):
+        records = np.ascontiguousarray(records, np.uint32)
+        assert records.shape[1] == binary * 12 + 8
+        n_records = records.shape[0] if n_records is None else n_records
+        addr = records.ctypes.data
+    else:
+        addr = int(records)
+    sym = np.ascontiguousarray(symm, np.int32)
+    n = sym.shape[0]
+    bsz = np.ascontiguousarray(board_sizes, np.int32)
+    sr = None if src is None else np.ascontiguousarray(src, np.int32)
+    prob = np.zeros((n, prob_ch, board * board), np.float32)
+    pas = np.zeros((n, pass_outs), np.float32)
+    misc = np.zeros((n, misc_outs), np.float32)
+    own = np.zeros((n, board * board), np.float32)
+    if lib.sayuri_hip_forward_packed_symm(ctx, n, addr, n_records, binary, _ip(bsz), None if sr is None else _ip(sr), _ip(sym),
+                                          _fp(prob), _fp(pas), _fp(misc), _fp(own)):
         raise RuntimeError(lib.sayuri_hip_last_error().decode())
     return prob, pas, misc, own

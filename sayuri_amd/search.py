@@ -36,6 +36,7 @@ def lib() -> ctypes.CDLL:
         h.sayuri_engine_net_queries.restype = ctypes.c_ulong
         h.sayuri_engine_net_queries.argtypes = [vp]
         h.sayuri_engine_net_output.argtypes = [vp, vp, ci, ci, cf, ci, u64, vp]
+        h.sayuri_engine_net_set_device_ensemble.argtypes = [vp, ci]
         h.sayuri_engine_search_new.restype = vp
         h.sayuri_engine_search_new.argtypes = [vp, vp, ctypes.c_char_p]
         h.sayuri_engine_search_free.argtypes = [vp]
@@ -96,6 +97,11 @@ class Network:
 
     def queries(self) -> int:
         return int(lib().sayuri_engine_net_queries(self._h))
+
+    def set_device_ensemble(self, on: bool):
+        """NetworkOptions::device_ensemble (also the option `device_ensemble`): kAverage as one ensemble request of a pipe
+        created with ensemble=E, or as eight evaluations in a row.  The result is the same, bit for bit."""
+        lib().sayuri_engine_net_set_device_ensemble(self._h, int(on))
 
     def output(self, game: Game, ensemble: int = 0, symmetry: int = 0, temperature: float = 1.0, use_cache: bool = False,
                seed: int = 0) -> np.ndarray:
