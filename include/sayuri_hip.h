@@ -278,6 +278,9 @@ int sayuri_hip_test_head_tail(int device, int use_fp16, int n, const int* board_
 int sayuri_hip_test_conv_se(int device, int n, const int* board_sizes, int max_board, int channels, int se_size, int act,
                             int via_tower, const float* x, const float* w, const float* bias, const float* res, const float* w1,
                             const float* b1, const float* w2, const float* b2, float* y);
+/* Form of the SE stage the calling thread's last sayuri_hip_test_conv_se launched (either kernel): 0 it launched nothing,
+ * 1 both FC images staged into LDS as fp16 (make_se_images fits), 2 the FCs read their fp32 weights from L2. */
+int sayuri_hip_test_last_se_form(void);
 /* sayuri_hip_test_conv_se's layer when its channels are split over 2..4 workgroups of 128 per board tile, which exchange their
  * partial squeeze sums inside the launch (conv_board_sx_kernel, conv_board_sx.h; the 40b x 384 network): same tensors, same
  * y = act(sigmoid(gamma) * conv(x) + beta + res).  The images, the board plan and the launch are the engine's own host code;

@@ -23,7 +23,7 @@ HIP_SYMBOLS = [
     "sayuri_hip_forward_packed", "sayuri_hip_submit_packed", "sayuri_hip_forward_packed_symm", "sayuri_hip_submit_packed_symm", "sayuri_hip_profile_run", "sayuri_hip_mark_kernel", "sayuri_hip_timed_stat", "sayuri_hip_host_alloc", "sayuri_hip_host_free", "sayuri_hip_device_bytes", "sayuri_hip_last_chains", "sayuri_hip_tower_state",
     "sayuri_hip_destroy", "sayuri_hip_last_error", "sayuri_hip_test_conv", "sayuri_hip_test_last_conv_kind",
     "sayuri_hip_test_se_unit", "sayuri_hip_test_head_tail", "sayuri_hip_test_conv_se", "sayuri_hip_test_head_board",
-    "sayuri_hip_test_conv_sx", "sayuri_hip_test_last_sx_kts",
+    "sayuri_hip_test_conv_sx", "sayuri_hip_test_last_sx_kts", "sayuri_hip_test_last_se_form",
 ]
 
 _hip = None

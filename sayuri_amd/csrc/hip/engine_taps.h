@@ -299,10 +299,12 @@ static int test_head_tail_impl(int device, int n, const int* board_sizes, int ma
 // The convolution with the SE unit inside it (conv_board_se_kernel, or the same stage inside the persistent tower kernel
 // when via_tower != 0): C -> C 3x3 convolution + bias, then the unit's pool -> FC -> FC -> act(sigmoid(g) x + b + res).
 // Returns 1 when the fused kernel does not apply to this batch (several samples per tile, channel tile not 128 / 256).
+static thread_local int g_test_se_form = 0;  // form of the SE stage the last sayuri_hip_test_conv_se launched: 0 nothing, 1 staged images, 2 FCs from L2
 static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_board, int C, int se, int act, int via_tower,
                              const float* x, const float* w, const float* bias, const float* res, const float* w1, const float* b1,
                              const float* w2, const float* b2, float* y) {
     typedef f16 T;
+    g_test_se_form = 0;
     HIP_OK(hipSetDevice(device));
     enable_big_lds_glds();
     TestArena A;
@@ -350,6 +352,7 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     if (!p.w || !p.bias || !sp.squeeze.wt || !sp.squeeze.b || !sp.excite.wt || !sp.excite.b || (staged && (!sp.w1h || !sp.w2h)))
         return fail("test_conv_se: hipMalloc failed");
     hipModule_t mod = nullptr;
+    g_test_se_form = sp.w1h ? 1 : 2;  // what both kernels branch on (board_se_pool / board_se_fc, the seam's image staging)
     if (via_tower) {
         hipFunction_t fn[2] = {nullptr, nullptr};
         if (load_tower_module(&mod, fn)) return -1;
@@ -489,6 +492,8 @@ extern "C" int sayuri_hip_test_conv_sx(int device, int n, const int* board_sizes
     if (!board_sizes || !x || !w || !w1 || !b1 || !w2 || !b2 || !y || n <= 0) return fail("test_conv_sx: bad argument");
     return test_conv_sx_impl(device, n, board_sizes, max_board, channels, se_size, act, x, w, bias, res, w1, b1, w2, b2, y);
 }
+
+extern "C" int sayuri_hip_test_last_se_form(void) { return sayuri::g_test_se_form; }
 
 extern "C" int sayuri_hip_test_last_sx_kts(void) { return sayuri::g_test_sx_kts; }
 
