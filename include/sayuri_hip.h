@@ -281,6 +281,22 @@ int sayuri_hip_test_conv_se(int device, int n, const int* board_sizes, int max_b
 /* Form of the SE stage the calling thread's last sayuri_hip_test_conv_se launched (either kernel): 0 it launched nothing,
  * 1 both FC images staged into LDS as fp16 (make_se_images fits), 2 the FCs read their fp32 weights from L2. */
 int sayuri_hip_test_last_se_form(void);
+/* A RUN of nlayers = 1..8 board convolutions as ONE launch of the persistent tower kernel (conv_tower.h), every layer built and
+ * the run linked by the engine's own host code: layer 0 is cin0 -> channels, every later layer channels -> channels, channels =
+ * 128 or 256 (the two widths of the kernel).  act [nlayers]; res_from [nlayers]: -1 no residual, 0 the run's input (cin0 ==
+ * channels), k the output of layer k - 1; w = [channels][cin0][3][3], then [channels][channels][3][3] per later layer; bias
+ * [nlayers][channels].  se_layer >= 0: that layer carries the SE unit (se_size, w1, b1, w2, b2 as in sayuri_hip_test_conv_se,
+ * which also states when the stage applies; sayuri_hip_test_last_se_form reports its form), < 0: none.  chain = 1: the weight
+ * hand-over between layers where the engine's rule allows it, 0: none.  x [n][cin0][bs*bs]; y [nlayers][n][channels][bs*bs]
+ * receives EVERY layer's output (each layer writes a buffer of its own, pre-set to NaN).  Returns 1 when the batch has no
+ * board plan, -1 on bad arguments.
+ * sayuri_hip_test_last_tower_run: out = {layers, layers that took the generated epilogue (row order), hand-over links} of the
+ * calling thread's last sayuri_hip_test_tower_run launch (zeros: that call launched nothing). */
+int sayuri_hip_test_tower_run(int device, int n, const int* board_sizes, int max_board, int channels, int cin0, int nlayers,
+                              const int* act, const int* res_from, const float* w, const float* bias, int se_layer, int se_size,
+                              const float* w1, const float* b1, const float* w2, const float* b2, int chain, const float* x,
+                              float* y);
+int sayuri_hip_test_last_tower_run(int out[3]);
 /* sayuri_hip_test_conv_se's layer when its channels are split over 2..4 workgroups of 128 per board tile, which exchange their
  * partial squeeze sums inside the launch (conv_board_sx_kernel, conv_board_sx.h; the 40b x 384 network): same tensors, same
  * y = act(sigmoid(gamma) * conv(x) + beta + res).  The images, the board plan and the launch are the engine's own host code;

@@ -24,6 +24,7 @@ HIP_SYMBOLS = [
     "sayuri_hip_destroy", "sayuri_hip_last_error", "sayuri_hip_test_conv", "sayuri_hip_test_last_conv_kind",
     "sayuri_hip_test_se_unit", "sayuri_hip_test_head_tail", "sayuri_hip_test_conv_se", "sayuri_hip_test_head_board",
     "sayuri_hip_test_conv_sx", "sayuri_hip_test_last_sx_kts", "sayuri_hip_test_last_se_form",
+    "sayuri_hip_test_tower_run", "sayuri_hip_test_last_tower_run",
 ]
 
 _hip = None
@@ -84,6 +85,9 @@ def hip() -> ctypes.CDLL:
             lib.sayuri_hip_test_conv.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]
+            lib.sayuri_hip_test_tower_run.argtypes = ([ctypes.c_int, ctypes.c_int, c_int_p] + [ctypes.c_int] * 4 + [c_int_p, c_int_p, c_float_p, c_float_p,
+                                                      ctypes.c_int, ctypes.c_int] + [c_float_p] * 4 + [ctypes.c_int, c_float_p, c_float_p])
+            lib.sayuri_hip_test_last_tower_run.argtypes = [c_int_p]
         _hip = lib
     return _hip
 

@@ -1594,17 +1594,7 @@ private:
     int tower_append(Fwd& f, int kot, const BoardSeParams& sp, bool has_se, double flops, double bytes) {
         if (!f.run.empty() && (f.run_kot != kot || (int)f.run.size() + f.table_used >= kTowerCap) && tower_flush(f)) return -1;
         if (f.run.empty()) { f.run_kot = kot; f.run_flops = f.run_bytes = 0; }
-        TowerLayer t;
-        std::memset(&t, 0, sizeof(t));
-        t.sp = sp;
-        t.has_se = has_se ? 1 : 0;
-        // what the bodies never read (tile = workgroup id, the launch's grid is the batch): left out of the table, so that
-        // a batch of 250 positions finds the table of a batch of 256 in place and nothing is uploaded
-        ConvParams& c = t.sp.b.c;
-        c.num_pix_tiles = 0;
-        c.g.n_samples = 0;
-        c.g.total_pix = 0;
-        f.run.push_back(t);
+        f.run.push_back(tower_element(sp, has_se));
         f.run_flops += flops;
         f.run_bytes += bytes;
         return 0;
@@ -1626,20 +1616,7 @@ private:
         if (flags_.tower_noepi_after >= 0 && tower_launches_++ >= flags_.tower_noepi_after)
             for (auto& t : run)
                 if (t.sp.b.row_order == 1 && !t.has_se) t.sp.b.row_order = 3;  // MEASURING: no epilogue (tower_seam.py epi_hook)
-        for (int i = 0; i < n; ++i) {
-            run[i].self = ts.dev + first + i;
-            run[i].last = i + 1 == n ? 1 : 0;
-        }
-        // weight hand-over (conv_board.h, CHAIN main loop): a plain layer without residual leaves the LDS alone after its K
-        // loop, so its last K group can bring in the next layer's first weight group.  Needs the same weight geometry on
-        // both sides (the piece addresses are computed with this layer's strides) and an even number of 32-channel chunks
-        // (the last group then sits in ring slot 1 and slot 0 is free).
-        for (int i = 0; i + 1 < n && flags_.tower_chain; ++i) {
-            const ConvParams &a = run[i].sp.b.c, &b = run[i + 1].sp.b.c;
-            if (run[i].has_se || a.res || a.cin_s != b.cin_s || a.ko_pad != b.ko_pad || (a.cin_s / kChunk) % 2) continue;
-            run[i].sp.b.w_next = b.w;
-            run[i + 1].sp.b.w_ready = 1;
-        }
+        (void)tower_link(run, ts.dev + first, flags_.tower_chain);  // self, last, the weight hand-over (engine_plan.h)
         if (std::memcmp(run.data(), ts.cache.data() + first, sizeof(TowerLayer) * n) != 0) {
             const int st = ts.next_stage;
             ts.next_stage ^= 1;

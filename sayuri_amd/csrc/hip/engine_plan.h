@@ -460,6 +460,41 @@ static bool board_row_order_ok(const BoardParams& bp, int kot, bool gen_epi) {
     return gen_epi && !bp.dbg && board_uses_row_order(kot) && bp.arith && (p.act == kMish || p.act == kReLU || p.act == kIdentity) &&
            p.cout_s == kot && p.ko_pad == kot;
 }
+// A board convolution as an element of the persistent launch's table (conv_tower.h); tower_link fills self / last.  What the
+// bodies never read (tile = workgroup id, the launch's grid is the batch) is left out of the table, so that a batch of 250
+// positions finds the table of a batch of 256 in place and nothing is uploaded (Engine::tower_flush compares bytewise).
+static TowerLayer tower_element(const BoardSeParams& sp, bool has_se) {
+    TowerLayer t;
+    std::memset(&t, 0, sizeof(t));
+    t.sp = sp;
+    t.has_se = has_se ? 1 : 0;
+    ConvParams& c = t.sp.b.c;
+    c.num_pix_tiles = 0;
+    c.g.n_samples = 0;
+    c.g.total_pix = 0;
+    return t;
+}
+// Links the elements of one run, which will sit at dev_base[0 .. run.size()) on the device: every element's own address, the
+// end of the run, and -- `chain` (SAYURI_TOWER_CHAIN) -- the weight hand-over (conv_board.h, CHAIN main loop): a plain layer
+// without residual leaves the LDS alone after its K loop, so its last K group can bring in the next layer's first weight group.
+// Needs the same weight geometry on both sides (the piece addresses are computed with this layer's strides) and an even number
+// of 32-channel chunks (the last group then sits in ring slot 1 and slot 0 is free).  Returns the number of hand-overs.
+static int tower_link(std::vector<TowerLayer>& run, const TowerLayer* dev_base, bool chain) {
+    const int n = (int)run.size();
+    for (int i = 0; i < n; ++i) {
+        run[i].self = dev_base + i;
+        run[i].last = i + 1 == n ? 1 : 0;
+    }
+    int links = 0;
+    for (int i = 0; i + 1 < n && chain; ++i) {
+        const ConvParams &a = run[i].sp.b.c, &b = run[i + 1].sp.b.c;
+        if (run[i].has_se || a.res || a.cin_s != b.cin_s || a.ko_pad != b.ko_pad || (a.cin_s / kChunk) % 2) continue;
+        run[i].sp.b.w_next = b.w;
+        run[i + 1].sp.b.w_ready = 1;
+        ++links;
+    }
+    return links;
+}
 // The across-sample kernel's part of a launch of `e` over `ntiles` pixel tiles (conv_params has filled gp.c); returns the grid.
 static int glds_params(GldsParams& gp, const GldsEntry& e, const int* tab_src, const int2* tab_pix, const float* zeros, int ntiles) {
     gp.tab_src = tab_src; gp.tab_pix = tab_pix; gp.zeros = zeros;

@@ -1,7 +1,8 @@
 // engine_taps.h -- layer-level test taps of the C-ABI (sayuri_hip_test_*): one kernel family at a time on host tensors, for the
 // parity tests (tests/test_gpu_layers.py, test_gpu_smallops.py).  Not used by the pipe.  A tap converts the layouts on the host,
-// in and out, and launches ONE layer; the device images, the routing of a convolution to its kernel family and the launch
-// parameters are the engine's own code (engine_plan.h), so the tests check the host code the engine runs.
+// in and out, and launches ONE layer -- sayuri_hip_test_tower_run one RUN of layers, as one persistent launch; the device images,
+// the routing of a convolution to its kernel family, the launch parameters and the linking of a run are the engine's own code
+// (engine_plan.h), so the tests check the host code the engine runs.
 #pragma once
 #include "engine_graph.h"
 
@@ -374,6 +375,123 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     return nhwc_to_nchw(tg, dy, C, cs, y);
 }
 
+// A RUN of 1..8 board convolutions as ONE launch of the persistent tower kernel (conv_tower.h): layer 0 is cin0 -> C, every later
+// layer C -> C, C = the channel tile (128 / 256); at most one layer carries the SE unit.  Each layer's parameters are built the
+// way Engine::conv / conv_se / board_launch build them (board_plan, board_params, conv_params, the row order wherever
+// board_row_order_ok allows it), the table is tower_element + tower_link's, the launch is Engine::tower_flush's.  Every layer
+// writes a buffer of its own that starts as fp16 NaN, and reads the previous layer's; y receives all of them.
+// res_from[l]: -1 no residual, 0 the run's input, k the output of layer k - 1.  Returns 1 when the batch has no board plan.
+static thread_local int g_test_tower_run[3] = {0, 0, 0};  // the last run launched: layers, layers in row order, hand-over links
+struct TestSeUnit { int layer, se; const float *w1, *b1, *w2, *b2; };
+static int test_tower_run_impl(int device, int n, const int* board_sizes, int max_board, int C, int cin0, int nlayers, const int* act,
+                               const int* res_from, const float* w, const float* bias, const TestSeUnit& se, int chain, const float* x, float* y) {
+    typedef f16 T;
+    g_test_tower_run[0] = g_test_tower_run[1] = g_test_tower_run[2] = 0;
+    g_test_se_form = 0;
+    if (C != 128 && C != 256) return fail("test_tower_run: the run's channels are a channel tile of the tower kernel, 128 or 256");
+    if (nlayers < 1 || nlayers > 8) return fail("test_tower_run: 1 to 8 layers");
+    if (cin0 < 1 || cin0 > 512) return fail("test_tower_run: bad input channel count");
+    if (se.layer >= nlayers) return fail("test_tower_run: the SE layer is not a layer of the run");
+    for (int l = 0; l < nlayers; ++l) {
+        if (act[l] < 0 || act[l] > 7) return fail("test_tower_run: bad activation");
+        if (res_from[l] < -1 || res_from[l] > l) return fail("test_tower_run: a layer's residual is the run's input or an earlier layer's output");
+        if (res_from[l] == 0 && cin0 != C) return fail("test_tower_run: the run's input has " + std::to_string(cin0) + " channels, a residual has " + std::to_string(C));
+    }
+    HIP_OK(hipSetDevice(device));
+    TestArena A;
+    TestGeom tg;
+    if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
+    const EngineFlags flags = EngineFlags::from_env();
+    const int cin0_s = round_up(cin0, 32);
+    int wmt, ko_pad;
+    conv_tile(C, true, &wmt, &ko_pad);
+    const BoardPlan plan = board_plan(tg.hg, ConvOverride{});
+    const BoardEntry* be = nullptr;
+    if (plan.ok)
+        for (const auto& e : kBoardEntries)
+            if (e.kot == ko_pad && e.lds(plan.npos) <= kMaxLds) be = &e;
+    if (!be) return 1;
+    // the SE layer: the rule of sayuri_hip_test_conv_se (one sample per tile; the images staged, or FC widths the L2 form takes)
+    const bool has_unit = se.layer >= 0;
+    std::vector<f16> img1;
+    std::vector<unsigned char> img2;
+    int w1_bytes = 0, w2_bytes = 0;
+    bool staged = false;
+    if (has_unit) {
+        if (!se.w1 || !se.b1 || !se.w2 || !se.b2) return fail("test_tower_run: the SE layer's weights are missing");
+        if (!be->fn_se || !plan.single) return fail("test_tower_run: the SE stage needs one sample per tile");
+        staged = make_se_images(C, se.se, max_board, se.w1, se.b1, se.w2, se.b2, &img1, &img2, &w1_bytes, &w2_bytes);
+        if (!staged && (se.se <= 0 || se.se % 4 || se.se > 512 || (2 * C) % 4 || 512 % (se.se / 4) || 512 % (2 * C / 4)))
+            return fail("test_tower_run: no form of the SE stage takes this SE width");
+    }
+    const size_t act_bytes = (size_t)n * tg.slot * C * sizeof(T);
+    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, cin0, cin0_s));
+    TestBoardTabs tabs;
+    if (!dx || !make_board_tabs(A, tg, plan, &tabs)) return fail("test_tower_run: hipMalloc failed");
+    T* out[8];
+    for (int l = 0; l < nlayers; ++l) {
+        // a buffer of its own behind the zero prefix; fp16 NaN (0xffff) wherever no layer wrote
+        unsigned char* raw = (unsigned char*)A.alloc(act_bytes + kZeroPrefix);
+        if (!raw) return fail("test_tower_run: hipMalloc failed");
+        out[l] = (T*)(raw + kZeroPrefix);
+        HIP_OK(hipMemset(out[l], 0xff, act_bytes));
+    }
+    std::vector<TowerLayer> run;
+    size_t w_off = 0;
+    int row_ordered = 0;
+    for (int l = 0; l < nlayers; ++l) {
+        const int cin = l ? C : cin0, cin_s = l ? C : cin0_s;
+        const bool unit = l == se.layer;
+        BoardSeParams sp;
+        std::memset(&sp, 0, sizeof(sp));
+        BoardParams& bp = sp.b;
+        board_params(bp, plan, tabs.src, tabs.pix, tabs.cols, flags.arith);
+        ConvParams& p = bp.c;
+        const T* res = res_from[l] < 0 ? nullptr : res_from[l] == 0 ? dx : out[res_from[l] - 1];
+        conv_params(p, l ? out[l - 1] : dx, nullptr, nullptr, res, out[l], tg.g, cin_s, C, ko_pad, 9, act[l]);
+        p.npos = 0; p.num_pix_tiles = plan.ntiles;
+        bp.row_order = board_row_order_ok(bp, be->kot, flags.tower_gen_epi) ? 1 : 0;  // Engine::board_launch
+        row_ordered += bp.row_order;
+        const std::vector<T> img = conv_image<T>(w + w_off, cin, C, 9, ko_pad);
+        const std::vector<float> hb = padded_bias(bias + (size_t)l * C, C, ko_pad);
+        w_off += (size_t)C * cin * 9;
+        p.w = A.upload(bp.row_order ? board_row_order(img, ko_pad) : img);
+        p.bias = A.upload(bp.row_order ? board_row_order(hb, ko_pad, 1) : hb);
+        if (!p.w || !p.bias) return fail("test_tower_run: hipMalloc failed");
+        if (unit) {
+            sp.squeeze = FcDev{A.upload(fc_transposed(se.w1, 3 * C, se.se)), A.upload(std::vector<float>(se.b1, se.b1 + se.se)), 3 * C, se.se};
+            sp.excite = FcDev{A.upload(fc_transposed(se.w2, se.se, 2 * C)), A.upload(std::vector<float>(se.b2, se.b2 + 2 * C)), se.se, 2 * C};
+            sp.C = C;
+            sp.w1h = staged ? A.upload(img1) : nullptr;
+            sp.w2h = staged ? A.upload(img2) : nullptr;
+            sp.w1_bytes = w1_bytes; sp.w2_bytes = w2_bytes;
+            if (!sp.squeeze.wt || !sp.squeeze.b || !sp.excite.wt || !sp.excite.b || (staged && (!sp.w1h || !sp.w2h)))
+                return fail("test_tower_run: hipMalloc failed");
+        }
+        run.push_back(tower_element(sp, unit));
+    }
+    TowerLayer* dt = (TowerLayer*)A.alloc(sizeof(TowerLayer) * nlayers);
+    if (!dt) return fail("test_tower_run: hipMalloc failed");
+    const int links = tower_link(run, dt, chain != 0);
+    HIP_OK(hipMemcpy(dt, run.data(), sizeof(TowerLayer) * nlayers, hipMemcpyHostToDevice));
+    hipModule_t mod = nullptr;
+    hipFunction_t fn[2] = {nullptr, nullptr};
+    if (load_tower_module(&mod, fn)) return -1;
+    if (has_unit) g_test_se_form = staged ? 1 : 2;
+    g_test_tower_run[0] = nlayers; g_test_tower_run[1] = row_ordered; g_test_tower_run[2] = links;
+    const TowerLayer* arg = dt;
+    void* params[] = {(void*)&arg};
+    hipError_t rc = hipModuleLaunchKernel(fn[be->kot == 256 ? 0 : 1], plan.ntiles, 1, 1, 512, 1, 1, 0, nullptr, params, nullptr);
+    if (rc == hipSuccess) rc = hipGetLastError();
+    if (rc == hipSuccess) rc = hipDeviceSynchronize();
+    (void)hipModuleUnload(mod);
+    if (rc != hipSuccess) return fail(std::string("test_tower_run: ") + hipGetErrorString(rc));
+    const size_t per_layer = (size_t)C * tg.hg.total;
+    for (int l = 0; l < nlayers; ++l)
+        if (nhwc_to_nchw(tg, out[l], C, C, y + l * per_layer)) return -1;
+    return 0;
+}
+
 // The same layer when its channels are split over kts = 2..4 workgroups of 128 (conv_board_sx_kernel, conv_board_sx.h): the
 // images of make_sx_images, the launch of Engine::conv_sx (sx_board_entry / sx_params / sx_grid) over every tile of the batch,
 // on a zeroed exchange buffer with a fixed tag.  Returns 1 when the form does not apply: the channels are not 2..4 whole tiles
@@ -494,6 +612,21 @@ extern "C" int sayuri_hip_test_conv_sx(int device, int n, const int* board_sizes
 }
 
 extern "C" int sayuri_hip_test_last_se_form(void) { return sayuri::g_test_se_form; }
+
+extern "C" int sayuri_hip_test_tower_run(int device, int n, const int* board_sizes, int max_board, int channels, int cin0, int nlayers,
+                                         const int* act, const int* res_from, const float* w, const float* bias, int se_layer, int se_size,
+                                         const float* w1, const float* b1, const float* w2, const float* b2, int chain, const float* x,
+                                         float* y) {
+    if (!board_sizes || !act || !res_from || !w || !bias || !x || !y || n <= 0 || (chain != 0 && chain != 1))
+        return fail("test_tower_run: bad argument");
+    return test_tower_run_impl(device, n, board_sizes, max_board, channels, cin0, nlayers, act, res_from, w, bias,
+                               TestSeUnit{se_layer < 0 ? -1 : se_layer, se_size, w1, b1, w2, b2}, chain, x, y);
+}
+extern "C" int sayuri_hip_test_last_tower_run(int out[3]) {
+    if (!out) return fail("test_last_tower_run: bad argument");
+    std::copy(sayuri::g_test_tower_run, sayuri::g_test_tower_run + 3, out);
+    return 0;
+}
 
 extern "C" int sayuri_hip_test_last_sx_kts(void) { return sayuri::g_test_sx_kts; }
 

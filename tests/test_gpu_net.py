@@ -418,6 +418,76 @@ def test_persistent_tower_and_its_weight_hand_over_change_nothing(tmp_weights_di
         assert np.abs(outs["layers"][0]).max() > 0
 
 
+TOWER_NETS = {
+    # networks no fixture has: the 128-channel tile as a whole tower (conv_tower_kernel<2>, tower_se_fc_kernel<2>), ReLU towers
+    # (the generated ReLU epilogue), a tower without SE units
+    "4b128-se-mish": lambda: W.NetSpec.residual(4, 128, 32, se_every=2),
+    "4b128-se-relu": lambda: W.NetSpec.residual(4, 128, 32, se_every=2, activation="relu"),
+    "3b256-relu": lambda: W.NetSpec.residual(3, 256, 32, se_every=0, activation="relu"),
+}
+TOWER_BATCHES = ([19] * 5, [19], [9])  # 9x9 on the 19 grid
+# ... and, for the 256-channel network only, the smallest batch whose boards take the 256-channel tile (below it a layer runs as
+# two 128-channel workgroups per board and joins no run: pick_board, engine_plan.h)
+TOWER_BATCH_256 = [19] * 129
+
+
+@pytest.mark.parametrize("name", list(TOWER_NETS))
+def test_persistent_tower_on_networks_of_both_widths(name, tmp_weights_dir, monkeypatch):
+    """test_persistent_tower_and_its_weight_hand_over_change_nothing on synthetic networks of the widths and activations the
+    fixtures lack: one launch per convolution (SAYURI_TOWER=0), the run without the weight hand-over (SAYURI_TOWER_CHAIN=0) and
+    the default give identical bits on every batch; the default is within fp16_tol of the CPU oracle on two positions of a
+    batch; the tower code object is loaded, and wherever a board's channel tile covers the layer the forward really contains a
+    tower_run launch."""
+    import os
+
+    from sayuri_amd import _lib
+    spec = TOWER_NETS[name]()
+    path = os.path.join(tmp_weights_dir, f"tower_{name}.bin")
+    W.write_weights(path, spec, seed=21)
+    oracle = PortNet(path)
+    lib = _lib.hip()
+    batches = [list(b) for b in TOWER_BATCHES] + ([TOWER_BATCH_256] if spec.channels == 256 else [])
+    planes = [W.synthetic_planes(len(bsz), bsz, seed=60 + k) for k, bsz in enumerate(batches)]
+    outs = {}
+    for mode, env in (("layers", {"SAYURI_TOWER": "0"}), ("run", {"SAYURI_TOWER_CHAIN": "0"}), ("run+handover", {})):
+        for k in ("SAYURI_TOWER", "SAYURI_TOWER_CHAIN"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        pipe = HipForwardPipe(path, board_size=19, batch_size=max(len(b) for b in batches), fp16=True)
+        try:
+            ctx = pipe.ctx(0)
+            assert lib.sayuri_hip_tower_state(ctx) == (0 if mode == "layers" else 1), mode
+            outs[mode] = []
+            for bsz, p in zip(batches, planes):
+                outs[mode].append(pipe.BatchForward(p, bsz))
+                # did this batch's forward contain a persistent launch?
+                stat, ms = _lib.KernelStat(), ctypes.c_float(0)
+                lib.sayuri_hip_mark_kernel(ctx, b"tower_run")
+                assert lib.sayuri_hip_time_runs(ctx, 1, ctypes.byref(ms)) == 0, lib.sayuri_hip_last_error().decode()
+                lib.sayuri_hip_timed_stat(ctx, ctypes.byref(stat))
+                lib.sayuri_hip_mark_kernel(ctx, b"")
+                covered = spec.channels == 128 or len(bsz) >= len(TOWER_BATCH_256)
+                if mode == "layers":
+                    assert stat.launches == 0, (name, bsz[:3], len(bsz), "SAYURI_TOWER=0 launched a run")
+                elif covered:
+                    assert stat.launches >= 1, (name, mode, bsz[:3], len(bsz), "the forward did not take the persistent launch")
+        finally:
+            pipe.Destroy()
+    for k, bsz in enumerate(batches):
+        for other in ("run", "run+handover"):
+            for a, b in zip(outs["layers"][k], outs[other][k]):
+                assert np.array_equal(a, b), (name, bsz[:3], len(bsz), other)
+        for i in sorted({0, len(bsz) - 1}):
+            exp = oracle.forward(planes[k][i], bsz[i])
+            got = outs["run+handover"][k][i]
+            assert np.isfinite(got).all()
+            err = float(np.abs(got - exp).max())
+            print(f"tower net {name} batch {len(bsz)} x {bsz[0]}x{bsz[0]} sample {i}: error {err / fp16_tol(exp):.2f} x tol")
+            assert err <= fp16_tol(exp), (name, bsz[:3], len(bsz), i, err)
+            assert np.abs(got).max() > 0
+
+
 @pytest.mark.parametrize("fp16", [False, True], ids=["fp32", "fp16"])
 def test_40b384_golden_parity(fp16, tmp_weights_dir):
     """BASELINE.json configs[4] network (40 blocks x 384 filters) on 19 / 13 / 9 boards against the reference's own
