@@ -16,16 +16,77 @@ class KernelStat(ctypes.Structure):
                 ("flops", ctypes.c_double), ("bytes", ctypes.c_double)]
 
 
-# every symbol include/sayuri_hip.h declares
-HIP_SYMBOLS = [
-    "sayuri_hip_device_count", "sayuri_hip_create", "sayuri_hip_create_ex", "sayuri_hip_latency_state", "sayuri_hip_test_conv_split", "sayuri_hip_load_tensor", "sayuri_hip_forward",
-    "sayuri_hip_submit", "sayuri_hip_wait", "sayuri_hip_query", "sayuri_hip_upload", "sayuri_hip_run", "sayuri_hip_sync", "sayuri_hip_download", "sayuri_hip_time_runs",
-    "sayuri_hip_forward_packed", "sayuri_hip_submit_packed", "sayuri_hip_forward_packed_symm", "sayuri_hip_submit_packed_symm", "sayuri_hip_profile_run", "sayuri_hip_mark_kernel", "sayuri_hip_timed_stat", "sayuri_hip_host_alloc", "sayuri_hip_host_free", "sayuri_hip_device_bytes", "sayuri_hip_last_chains", "sayuri_hip_tower_state",
-    "sayuri_hip_destroy", "sayuri_hip_last_error", "sayuri_hip_test_conv", "sayuri_hip_test_last_conv_kind",
-    "sayuri_hip_test_se_unit", "sayuri_hip_test_head_tail", "sayuri_hip_test_conv_se", "sayuri_hip_test_head_board",
-    "sayuri_hip_test_conv_sx", "sayuri_hip_test_last_sx_kts", "sayuri_hip_test_last_se_form",
-    "sayuri_hip_test_tower_run", "sayuri_hip_test_last_tower_run",
-]
+class BlockDesc(ctypes.Structure):
+    """sayuri_hip_blockdesc"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("type", "apply_se", "se_size", "bottleneck_channels", "feedforward_channels", "dw_filter")]
+
+
+class NetDesc(ctypes.Structure):
+    """sayuri_hip_netdesc"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("version", "input_channels", "residual_channels", "residual_blocks", "policy_head_channels",
+                                              "value_head_channels", "probabilities_channels", "pass_probability_outputs",
+                                              "ownership_channels", "value_misc_outputs", "default_act", "policy_head_type",
+                                              "policy_dw_filter")] + [("blocks", ctypes.POINTER(BlockDesc))]
+
+
+def fp(a):
+    return a.ctypes.data_as(c_float_p)
+
+
+def ip(a):
+    return a.ctypes.data_as(c_int_p)
+
+
+# The C-ABI of include/sayuri_hip.h: name -> (restype, argtypes) of every function it declares, applied by hip() to what the
+# loaded library exports.  A context (sayuri_hip_ctx*) and packed records are c_void_p: a Python int or an address goes in whole.
+_I, _U, _Z, _V, _F, _IP = ctypes.c_int, ctypes.c_uint, ctypes.c_size_t, ctypes.c_void_p, c_float_p, c_int_p
+_OUT = [_F] * 4  # prob, pass, misc, own
+_STAT = ctypes.POINTER(KernelStat)
+_W12 = ctypes.POINTER(c_float_p)  # weights12 of the head taps
+HIP_ABI = {
+    "sayuri_hip_device_count": (_I, []),
+    "sayuri_hip_create": (_V, [_I, _V, _I, _I, _I]),
+    "sayuri_hip_create_ex": (_V, [_I, _V, _I, _I, _I, _U]),
+    "sayuri_hip_load_tensor": (_I, [_V, _I, _I, _F, _Z]),
+    "sayuri_hip_forward": (_I, [_V, _I, _F, _IP] + _OUT),
+    "sayuri_hip_upload": (_I, [_V, _I, _F, _IP]),
+    "sayuri_hip_run": (_I, [_V]),
+    "sayuri_hip_sync": (_I, [_V]),
+    "sayuri_hip_download": (_I, [_V] + _OUT),
+    "sayuri_hip_submit": (_I, [_V, _I, _F, _IP] + _OUT + [_IP]),
+    "sayuri_hip_forward_packed": (_I, [_V, _I, _V, _I, _IP] + _OUT),
+    "sayuri_hip_submit_packed": (_I, [_V, _I, _V, _I, _IP] + _OUT + [_IP]),
+    "sayuri_hip_forward_packed_symm": (_I, [_V, _I, _V, _I, _I, _IP, _IP, _IP] + _OUT),
+    "sayuri_hip_submit_packed_symm": (_I, [_V, _I, _V, _I, _I, _IP, _IP, _IP] + _OUT + [_IP]),
+    "sayuri_hip_wait": (_I, [_V, _I]),
+    "sayuri_hip_query": (_I, [_V, _I]),
+    "sayuri_hip_time_runs": (_I, [_V, _I, _F]),
+    "sayuri_hip_profile_run": (_I, [_V, _STAT, _I]),
+    "sayuri_hip_mark_kernel": (_I, [_V, ctypes.c_char_p]),
+    "sayuri_hip_timed_stat": (_I, [_V, _STAT]),
+    "sayuri_hip_host_alloc": (_V, [_Z]),
+    "sayuri_hip_host_free": (None, [_V]),
+    "sayuri_hip_device_bytes": (_Z, [_V]),
+    "sayuri_hip_last_chains": (_I, [_V]),
+    "sayuri_hip_tower_state": (_I, [_V]),
+    "sayuri_hip_latency_state": (_I, [_V]),
+    "sayuri_hip_destroy": (None, [_V]),
+    "sayuri_hip_last_error": (ctypes.c_char_p, []),
+    # the layer taps: device, (use_fp16,) n, board_sizes, max_board, shape ..., tensors
+    "sayuri_hip_test_conv": (_I, [_I] * 3 + [_IP] + [_I] * 7 + [_F] * 5),
+    "sayuri_hip_test_conv_split": (_I, [_I] * 2 + [_IP] + [_I] * 4 + [_F] * 5 + [_I] * 2),
+    "sayuri_hip_test_last_conv_kind": (_I, []),
+    "sayuri_hip_test_se_unit": (_I, [_I] * 3 + [_IP] + [_I] * 4 + [_F] * 8),
+    "sayuri_hip_test_head_tail": (_I, [_I] * 3 + [_IP] + [_I] * 7 + [_F, _F, _W12] + _OUT),
+    "sayuri_hip_test_conv_se": (_I, [_I] * 2 + [_IP] + [_I] * 5 + [_F] * 9),
+    "sayuri_hip_test_last_se_form": (_I, []),
+    "sayuri_hip_test_tower_run": (_I, [_I] * 2 + [_IP] + [_I] * 4 + [_IP, _IP, _F, _F, _I, _I] + [_F] * 4 + [_I, _F, _F]),
+    "sayuri_hip_test_last_tower_run": (_I, [_IP]),
+    "sayuri_hip_test_conv_sx": (_I, [_I] * 2 + [_IP] + [_I] * 4 + [_F] * 9),
+    "sayuri_hip_test_last_sx_kts": (_I, []),
+    "sayuri_hip_test_head_board": (_I, [_I] * 2 + [_IP] + [_I] * 8 + [_F] * 5 + [_W12] + _OUT),
+}
+HIP_SYMBOLS = list(HIP_ABI)
 
 _hip = None
 _host = None
@@ -52,42 +113,11 @@ def hip() -> ctypes.CDLL:
                   file=sys.stderr)
             path = fake
         lib = ctypes.CDLL(_require(path), mode=ctypes.RTLD_GLOBAL)
-        lib.sayuri_hip_last_error.restype = ctypes.c_char_p
-        lib.sayuri_hip_device_count.restype = ctypes.c_int
-        lib.sayuri_hip_upload.argtypes = [ctypes.c_void_p, ctypes.c_int, c_float_p, c_int_p]
-        lib.sayuri_hip_run.argtypes = [ctypes.c_void_p]
-        lib.sayuri_hip_sync.argtypes = [ctypes.c_void_p]
-        lib.sayuri_hip_download.argtypes = [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p]
-        lib.sayuri_hip_forward.argtypes = [ctypes.c_void_p, ctypes.c_int, c_float_p, c_int_p, c_float_p,
-                                           c_float_p, c_float_p, c_float_p]
-        lib.sayuri_hip_time_runs.argtypes = [ctypes.c_void_p, ctypes.c_int, c_float_p]
-        lib.sayuri_hip_profile_run.argtypes = [ctypes.c_void_p, ctypes.POINTER(KernelStat), ctypes.c_int]
-        lib.sayuri_hip_mark_kernel.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-        lib.sayuri_hip_timed_stat.argtypes = [ctypes.c_void_p, ctypes.POINTER(KernelStat)]
-        lib.sayuri_hip_device_bytes.restype = ctypes.c_size_t
-        lib.sayuri_hip_device_bytes.argtypes = [ctypes.c_void_p]
-        lib.sayuri_hip_last_chains.restype = ctypes.c_int
-        lib.sayuri_hip_last_chains.argtypes = [ctypes.c_void_p]
-        lib.sayuri_hip_tower_state.restype = ctypes.c_int
-        lib.sayuri_hip_tower_state.argtypes = [ctypes.c_void_p]
-        # entry points a device library may lack (the stand-in knows the ABI it was written against): declared where present
-        if hasattr(lib, "sayuri_hip_latency_state"):
-            lib.sayuri_hip_latency_state.restype = ctypes.c_int
-            lib.sayuri_hip_latency_state.argtypes = [ctypes.c_void_p]
-        if hasattr(lib, "sayuri_hip_create_ex"):
-            lib.sayuri_hip_create_ex.restype = ctypes.c_void_p
-            lib.sayuri_hip_create_ex.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
-        if hasattr(lib, "sayuri_hip_test_conv_split"):
-            lib.sayuri_hip_test_conv_split.argtypes = [ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                       ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                       ctypes.c_int, ctypes.c_int]
-        if not fake:  # the stand-in has no kernels to tap
-            lib.sayuri_hip_test_conv.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
-                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]
-            lib.sayuri_hip_test_tower_run.argtypes = ([ctypes.c_int, ctypes.c_int, c_int_p] + [ctypes.c_int] * 4 + [c_int_p, c_int_p, c_float_p, c_float_p,
-                                                      ctypes.c_int, ctypes.c_int] + [c_float_p] * 4 + [ctypes.c_int, c_float_p, c_float_p])
-            lib.sayuri_hip_test_last_tower_run.argtypes = [c_int_p]
+        # a device library may lack entry points (the stand-in knows the ABI it was written against and has no kernels to tap)
+        for name, (restype, argtypes) in HIP_ABI.items():
+            if hasattr(lib, name):
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _hip = lib
     return _hip
 

@@ -8,19 +8,12 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from .hipraw import hip_forward_packed_raw, hip_forward_packed_symm_raw, hip_forward_raw  # noqa: F401  (their importers' address)
 
 PLANES_LEN = 43 * 361  # InputData::planes
 OUT_LEN = 2 * 361 + 9
 MAX_BOARD = 19
 HIP_LATENCY = 1  # include/sayuri_hip.h: SAYURI_HIP_LATENCY
-
-
-def _fp(a: np.ndarray):
-    return a.ctypes.data_as(_lib.c_float_p)
-
-
-def _ip(a: np.ndarray):
-    return a.ctypes.data_as(_lib.c_int_p)
 
 
 class Weights:
@@ -48,7 +41,7 @@ class Weights:
             return None
         out = np.zeros(n, np.float32)
         if n:
-            lib.sayuri_weights_tensor(self._h, name.encode(), _fp(out), n)
+            lib.sayuri_weights_tensor(self._h, name.encode(), _lib.fp(out), n)
         return out
 
     def close(self):
@@ -157,7 +150,7 @@ class HipForwardPipe:
         km = np.asarray(komi if komi is not None else [7.5] * n, np.float32)
         off = np.asarray(offsets if offsets is not None else [0] * n, np.int32)
         out = np.zeros((n, OUT_LEN), np.float32)
-        if _lib.host().sayuri_pipe_eval(self._h, mode, gpu, n, _fp(buf), _ip(bsz), _fp(km), _ip(off), _fp(out)):
+        if _lib.host().sayuri_pipe_eval(self._h, mode, gpu, n, _lib.fp(buf), _lib.ip(bsz), _lib.fp(km), _lib.ip(off), _lib.fp(out)):
             raise RuntimeError(_lib.host().sayuri_host_last_error().decode())
         res = []
         for i in range(n):
@@ -188,7 +181,7 @@ class HipForwardPipe:
         p = np.ascontiguousarray(planes, np.float32).ravel()
         flat[:p.size] = p
         out = np.zeros((8, OUT_LEN), np.float32)
-        rc = _lib.host().sayuri_pipe_forward_ensemble(self._h, _fp(flat), board_size, komi, offset, _fp(out))
+        rc = _lib.host().sayuri_pipe_forward_ensemble(self._h, _lib.fp(flat), board_size, komi, offset, _lib.fp(out))
         if rc < 0:
             raise RuntimeError(_lib.host().sayuri_host_last_error().decode())
         s = board_size * board_size
@@ -209,7 +202,7 @@ class HipForwardPipe:
         kd = np.asarray(kinds, np.int32)
         out = np.zeros((n, 8, OUT_LEN), np.float32)
         got = np.zeros(n, np.int32)
-        if _lib.host().sayuri_pipe_ensemble_mix(self._h, n, _fp(buf), _ip(bsz), _fp(km), _ip(off), _ip(kd), fiber_threads, _fp(out), _ip(got)):
+        if _lib.host().sayuri_pipe_ensemble_mix(self._h, n, _lib.fp(buf), _lib.ip(bsz), _lib.fp(km), _lib.ip(off), _lib.ip(kd), fiber_threads, _lib.fp(out), _lib.ip(got)):
             raise RuntimeError(_lib.host().sayuri_host_last_error().decode())
         res = []
         for i in range(n):
@@ -224,41 +217,6 @@ class HipForwardPipe:
         return self._eval(3 if mixed else 2, planes, board_sizes, komi, offsets)
 
 
-def hip_forward_raw(ctx: int, planes_grid: np.ndarray, board_sizes, board: int, prob_ch: int = 5, pass_outs: int = 5,
-                    misc_outs: int = 15):
-    """sayuri_hip_forward on NN-grid planes [n][43][board*board] -> prob, pass, misc, own."""
-    lib = _lib.hip()
-    n = planes_grid.shape[0]
-    planes_grid = np.ascontiguousarray(planes_grid, np.float32)
-    bsz = np.asarray(board_sizes, np.int32)
-    prob = np.zeros((n, prob_ch, board * board), np.float32)
-    pas = np.zeros((n, pass_outs), np.float32)
-    misc = np.zeros((n, misc_outs), np.float32)
-    own = np.zeros((n, board * board), np.float32)
-    if lib.sayuri_hip_forward(ctx, n, _fp(planes_grid), _ip(bsz), _fp(prob), _fp(pas), _fp(misc), _fp(own)):
-        raise RuntimeError(lib.sayuri_hip_last_error().decode())
-    return prob, pas, misc, own
-
-
-def hip_forward_packed_raw(ctx: int, records: np.ndarray, binary: int, board_sizes, board: int, prob_ch: int = 5, pass_outs: int = 5,
-                           misc_outs: int = 15):
-    """sayuri_hip_forward_packed on packed records [n][binary*12 + 8] (uint32) -> prob, pass, misc, own."""
-    lib = _lib.hip()
-    lib.sayuri_hip_forward_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, _lib.c_int_p, _lib.c_float_p,
-                                              _lib.c_float_p, _lib.c_float_p, _lib.c_float_p]
-    records = np.ascontiguousarray(records, np.uint32)
-    n = records.shape[0]
-    assert records.shape[1] == binary * 12 + 8
-    bsz = np.asarray(board_sizes, np.int32)
-    prob = np.zeros((n, prob_ch, board * board), np.float32)
-    pas = np.zeros((n, pass_outs), np.float32)
-    misc = np.zeros((n, misc_outs), np.float32)
-    own = np.zeros((n, board * board), np.float32)
-    if lib.sayuri_hip_forward_packed(ctx, n, records.ctypes.data, binary, _ip(bsz), _fp(prob), _fp(pas), _fp(misc), _fp(own)):
-        raise RuntimeError(lib.sayuri_hip_last_error().decode())
-    return prob, pas, misc, own
-
-
 def packed_symmetry(record: np.ndarray, binary: int, board_size: int, symmetry: int) -> np.ndarray:
     """PackedPlanes::Symmetry (csrc/host/packed_planes.h): the record the encoder builds for `symmetry` from the identity's."""
     record = np.ascontiguousarray(record, np.uint32)
@@ -266,35 +224,3 @@ def packed_symmetry(record: np.ndarray, binary: int, board_size: int, symmetry: 
     if _lib.host().sayuri_packed_symmetry(record.ctypes.data, binary, board_size, symmetry, out.ctypes.data):
         raise ValueError("packed_symmetry: bad arguments")
     return out
-
-
-_SYMM_ARGS = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _lib.c_int_p, _lib.c_int_p, _lib.c_int_p,
-              _lib.c_float_p, _lib.c_float_p, _lib.c_float_p, _lib.c_float_p]
-
-
-def hip_forward_packed_symm_raw(ctx: int, records, binary: int, board_sizes, src, symm, board: int, prob_ch: int = 5,
-                                pass_outs: int = 5, misc_outs: int = 15, n_records: Optional[int] = None):
-    """sayuri_hip_forward_packed_symm: device sample i = record src[i] (None: the identity map) under board symmetry symm[i]
-    -> prob, pass, misc, own per device sample.  records: uint32 [n_records][binary*12 + 8], or the address of such an array
-    (memory from sayuri_hip_host_alloc) with n_records given."""
-    lib = _lib.hip()
-    lib.sayuri_hip_forward_packed_symm.argtypes = _SYMM_ARGS
-    if isinstance(records, np.ndarray):
-        records = np.ascontiguousarray(records, np.uint32)
-        assert records.shape[1] == binary * 12 + 8
-        n_records = records.shape[0] if n_records is None else n_records
-        addr = records.ctypes.data
-    else:
-        addr = int(records)
-    sym = np.ascontiguousarray(symm, np.int32)
-    n = sym.shape[0]
-    bsz = np.ascontiguousarray(board_sizes, np.int32)
-    sr = None if src is None else np.ascontiguousarray(src, np.int32)
-    prob = np.zeros((n, prob_ch, board * board), np.float32)
-    pas = np.zeros((n, pass_outs), np.float32)
-    misc = np.zeros((n, misc_outs), np.float32)
-    own = np.zeros((n, board * board), np.float32)
-    if lib.sayuri_hip_forward_packed_symm(ctx, n, addr, n_records, binary, _ip(bsz), None if sr is None else _ip(sr), _ip(sym),
-                                          _fp(prob), _fp(pas), _fp(misc), _fp(own)):
-        raise RuntimeError(lib.sayuri_hip_last_error().decode())
-    return prob, pas, misc, own

@@ -14,6 +14,8 @@ from typing import Optional
 
 import numpy as np
 
+from sayuri_amd._lib import fp
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 PORT_SO = os.path.join(ORACLE_DIR, "libsayuri_oracle.so")
@@ -27,10 +29,6 @@ def build_port(force: bool = False) -> str:
     if force or not os.path.exists(PORT_SO) or os.path.getmtime(PORT_SO) < os.path.getmtime(src):
         subprocess.check_call(["make", "-C", ORACLE_DIR, "port"], stdout=subprocess.DEVNULL)
     return PORT_SO
-
-
-def _fp(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
 class PortNet:
@@ -89,13 +87,13 @@ class PortNet:
             return None
         out = np.zeros(n, np.float32)
         if n:
-            self.lib().so_get_tensor(self._h, name.encode(), _fp(out), n)
+            self.lib().so_get_tensor(self._h, name.encode(), fp(out), n)
         return out
 
     def forward(self, planes: np.ndarray, board_size: int, komi: float = 7.5, offset: int = 0) -> np.ndarray:
         planes = np.ascontiguousarray(planes, np.float32)
         out = np.zeros(2 * board_size * board_size + TAIL, np.float32)
-        if self.lib().so_forward(self._h, board_size, komi, offset, _fp(planes), _fp(out)):
+        if self.lib().so_forward(self._h, board_size, komi, offset, fp(planes), fp(out)):
             raise RuntimeError("so_forward failed")
         return out
 
@@ -107,7 +105,7 @@ class PortNet:
         pas = np.zeros(self.info[7], np.float32)
         misc = np.zeros(self.info[9], np.float32)
         own = np.zeros((self.info[8], s), np.float32)
-        if self.lib().so_forward_raw(self._h, board_size, _fp(planes), _fp(prob), _fp(pas), _fp(misc), _fp(own)):
+        if self.lib().so_forward_raw(self._h, board_size, fp(planes), fp(prob), fp(pas), fp(misc), fp(own)):
             raise RuntimeError("so_forward_raw failed")
         return prob, pas, misc, own[0]
 
@@ -115,7 +113,7 @@ class PortNet:
     def postprocess(cls, raw: np.ndarray, board_size: int, temp: float = 1.0) -> np.ndarray:
         raw = np.ascontiguousarray(raw, np.float32)
         post = np.zeros(2 * board_size * board_size + 1 + 8, np.float32)
-        cls.lib().so_postprocess(board_size, temp, _fp(raw), _fp(post))
+        cls.lib().so_postprocess(board_size, temp, fp(raw), fp(post))
         return post
 
 
@@ -160,12 +158,12 @@ class RefNet:
             return None
         out = np.zeros(n, np.float32)
         if n:
-            self.lib().ref_get_tensor(name.encode(), _fp(out), n)
+            self.lib().ref_get_tensor(name.encode(), fp(out), n)
         return out
 
     def forward(self, planes: np.ndarray, board_size: int, komi: float = 7.5, offset: int = 0) -> np.ndarray:
         planes = np.ascontiguousarray(planes, np.float32)
         out = np.zeros(2 * board_size * board_size + TAIL, np.float32)
-        if self.lib().ref_forward(board_size, komi, 0, offset, _fp(planes), _fp(out)):
+        if self.lib().ref_forward(board_size, komi, 0, offset, fp(planes), fp(out)):
             raise RuntimeError(f"ref_forward: {self.lib().ref_last_error().decode()}")
         return out

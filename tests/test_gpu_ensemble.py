@@ -12,10 +12,9 @@ import time
 import numpy as np
 import pytest
 
-import test_gpu_fuzz as FZ
 from _ensemble import GAME_OF_SIZE, GOLDEN_GAMES, golden_game_at, permute_record
 from _golden import Golden
-from sayuri_amd import _lib
+from sayuri_amd import _lib, hipraw
 from sayuri_amd import search as S
 from sayuri_amd.engine import pack_planes
 from sayuri_amd.pipe import HipForwardPipe, hip_forward_packed_raw, hip_forward_packed_symm_raw
@@ -25,7 +24,6 @@ pytestmark = pytest.mark.gpu
 
 B, WORDS = 19, 37 * 12 + 8
 SIZES = (2, 3, 5, 9, 13, 19)   # 2 and 3: the bs-1-t edges; 19: the twelfth record word
-FP, IP = FZ.FP, FZ.IP
 K_AVERAGE = 2
 # sayuri_engine_net_output's layout behind the two maps of n cells
 FIELDS = ("pass_probability", "wdl0", "wdl1", "wdl2", "wdl_winrate", "stm_winrate", "final_score", "q_error", "score_error")
@@ -67,44 +65,16 @@ def assert_symmetries_differ(outs, src, symm):
             assert not np.array_equal(outs[0][i], outs[0][i0]), (k, int(symm[i]))
 
 
-class SymmPinned:
-    """Two sets of page-locked buffers for sayuri_hip_submit_packed_symm / wait: records, the four outputs."""
+def submit_symm(ctx, s, recs, bsz, src, symm):
+    """The records and board sizes into the set, then sayuri_hip_submit_packed_symm -> ticket."""
+    s.records[:recs.size] = recs.ravel()
+    s.bsz[:len(symm)] = bsz
+    return hipraw.submit_packed_symm(ctx, s, len(recs), 37, src, symm)
 
-    def __init__(self, lib, nmax):
-        self.lib, self.nmax = lib, nmax
-        lib.sayuri_hip_host_alloc.restype = ctypes.c_void_p
-        lib.sayuri_hip_host_alloc.argtypes = [ctypes.c_size_t]
-        lib.sayuri_hip_host_free.argtypes = [ctypes.c_void_p]
-        lib.sayuri_hip_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        lib.sayuri_hip_submit_packed_symm.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, IP, IP, IP,
-                                                      FP, FP, FP, FP, IP]
-        self.sizes = (nmax * WORDS, nmax * 5 * B * B, nmax * 5, nmax * 15, nmax * B * B)
-        self.sets = [[lib.sayuri_hip_host_alloc(k * 4) for k in self.sizes] for _ in range(2)]
-        assert all(q for ptrs in self.sets for q in ptrs)
 
-    def close(self):
-        for ptrs in self.sets:
-            for q in ptrs:
-                self.lib.sayuri_hip_host_free(ctypes.c_void_p(q))
-
-    def submit(self, ctx, i, recs, bsz, src, symm):
-        rc_, pr, pa, mi, ow = self.sets[i]
-        np.ctypeslib.as_array(ctypes.cast(rc_, ctypes.POINTER(ctypes.c_uint32)), (recs.size,))[:] = recs.ravel()
-        tick = ctypes.c_int(-1)
-        bsz, symm = np.ascontiguousarray(bsz, np.int32), np.ascontiguousarray(symm, np.int32)
-        src = None if src is None else np.ascontiguousarray(src, np.int32)
-        rc = self.lib.sayuri_hip_submit_packed_symm(ctx, len(symm), ctypes.c_void_p(rc_), len(recs), 37, bsz.ctypes.data_as(IP),
-                                                    None if src is None else src.ctypes.data_as(IP), symm.ctypes.data_as(IP),
-                                                    ctypes.cast(pr, FP), ctypes.cast(pa, FP), ctypes.cast(mi, FP), ctypes.cast(ow, FP),
-                                                    ctypes.byref(tick))
-        assert rc == 0, self.lib.sayuri_hip_last_error()
-        return tick.value   # (the small tables are copied by the call: the temporaries above may go)
-
-    def wait(self, ctx, i, tick, n):
-        assert self.lib.sayuri_hip_wait(ctx, tick) == 0, self.lib.sayuri_hip_last_error()
-        _, pr, pa, mi, ow = self.sets[i]
-        return (np.ctypeslib.as_array(ctypes.cast(pr, FP), (n, 5, B * B)).copy(), np.ctypeslib.as_array(ctypes.cast(pa, FP), (n, 5)).copy(),
-                np.ctypeslib.as_array(ctypes.cast(mi, FP), (n, 15)).copy(), np.ctypeslib.as_array(ctypes.cast(ow, FP), (n, B * B)).copy())
+def wait_copy(ctx, s, tick, n):
+    hipraw.wait(ctx, tick)
+    return tuple(a.copy() for a in s.outputs(n))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. expansion
@@ -116,19 +86,18 @@ def test_device_expansion_is_exact(tmp_weights_dir, case, name, fp16, latency):
     are those of sayuri_hip_forward_packed on the 48 host-permuted records, bit for bit -- with the records in pageable
     memory (copied) and in sayuri_hip_host_alloc memory (submit: read in place by the kernel)."""
     g = Golden(name, tmp_weights_dir)
-    lib = _lib.hip()
     pipe = make_pipe(g.weights_path, latency=latency, batch=64, fp16=fp16)
-    pinned = SymmPinned(lib, 64)
+    pinned = hipraw.PinnedSet(64, B, WORDS)
     try:
         ctx = pipe.ctx(0)
         want = hip_forward_packed_raw(ctx, case["host"], 37, case["bsz"], B)
         got = hip_forward_packed_symm_raw(ctx, case["recs"], 37, case["bsz"], case["src"], case["symm"], B)
         assert_bits(got, want, "pageable records")
         assert_symmetries_differ(got, case["src"], case["symm"])
-        tick = pinned.submit(ctx, 0, case["recs"], case["bsz"], case["src"], case["symm"])
-        assert_bits(pinned.wait(ctx, 0, tick, len(case["symm"])), want, "records in page-locked memory, in place")
+        tick = submit_symm(ctx, pinned, case["recs"], case["bsz"], case["src"], case["symm"])
+        assert_bits(wait_copy(ctx, pinned, tick, len(case["symm"])), want, "records in page-locked memory, in place")
         # the blocking form on page-locked records
-        got = hip_forward_packed_symm_raw(ctx, pinned.sets[0][0], 37, case["bsz"], case["src"], case["symm"], B, n_records=len(SIZES))
+        got = hip_forward_packed_symm_raw(ctx, pinned.records.ctypes.data, 37, case["bsz"], case["src"], case["symm"], B, n_records=len(SIZES))
         assert_bits(got, want, "records in page-locked memory, blocking call")
     finally:
         pinned.close()
@@ -169,7 +138,7 @@ def test_two_tickets_in_flight(tmp_weights_dir, case, latency):
     g = Golden("net_20b256", tmp_weights_dir)
     lib = _lib.hip()
     pipe = make_pipe(g.weights_path, latency=latency, batch=96)
-    pinned = SymmPinned(lib, 96)
+    pinned = [hipraw.PinnedSet(96, B, WORDS) for _ in range(2)]
     try:
         ctx = pipe.ctx(0)
         if not latency:
@@ -182,15 +151,16 @@ def test_two_tickets_in_flight(tmp_weights_dir, case, latency):
                    dict(recs=case["recs"][k19:k19 + 1], bsz=np.full(n_big, 19, np.int32), src=np.zeros(n_big, np.int32), symm=big_symm,
                         host=big_host)]
         solo = [hip_forward_packed_raw(ctx, b["host"], 37, b["bsz"], B) for b in batches]
-        sub = lambda i: pinned.submit(ctx, i, batches[i]["recs"], batches[i]["bsz"], batches[i]["src"], batches[i]["symm"])  # noqa: E731
+        sub = lambda i: submit_symm(ctx, pinned[i], batches[i]["recs"], batches[i]["bsz"], batches[i]["src"], batches[i]["symm"])  # noqa: E731
         tick = [sub(0), sub(1)]
         for r in range(6):
             i = r & 1
-            assert_bits(pinned.wait(ctx, i, tick[i], len(batches[i]["symm"])), solo[i], ("round", r))
+            assert_bits(wait_copy(ctx, pinned[i], tick[i], len(batches[i]["symm"])), solo[i], ("round", r))
             if r < 4:
                 tick[i] = sub(i)
     finally:
-        pinned.close()
+        for s in pinned:
+            s.close()
         pipe.Destroy()
 
 
@@ -306,35 +276,20 @@ def test_device_ensemble_halves_the_average(tmp_weights_dir, capsys):
 
 
 # ---------------------------------------------------------------------------------------------------------------- default untouched
-class _Block(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("type", "apply_se", "se_size", "btl", "ffn", "dw")]
-
-
-class _Desc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("version", "input_channels", "residual_channels", "residual_blocks", "policy_head_channels",
-                                              "value_head_channels", "probabilities_channels", "pass_probability_outputs",
-                                              "ownership_channels", "value_misc_outputs", "default_act", "policy_head_type",
-                                              "policy_dw_filter")] + [("blocks", ctypes.POINTER(_Block))]
-
-
 def direct_context(path, max_batch):
     """A context made at the C-ABI itself -- sayuri_hip_create(max_batch) and every tensor of a residual-block network loaded,
     the calls HipForwardPipe's BuildCtx makes -- so that what a pipe adds to its context can be told from outside."""
     from sayuri_amd.pipe import Weights
     lib = _lib.hip()
-    lib.sayuri_hip_create.restype = ctypes.c_void_p
-    lib.sayuri_hip_create.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.sayuri_hip_load_tensor.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, FP, ctypes.c_size_t]
-    lib.sayuri_hip_destroy.argtypes = [ctypes.c_void_p]
     w = Weights(path)
     ver, cin, nblocks, C, cp, cv, pc, po, oc, mo, act, ptype = w.info
     assert ptype == 0
-    blocks = (_Block * nblocks)()
+    blocks = (_lib.BlockDesc * nblocks)()
     for b in range(nblocks):
         bi = w.block_info(b)
         assert bi[0] == 1, "residual blocks only"
-        blocks[b] = _Block(1, bi[1], bi[2], 0, 0, 0)
-    desc = _Desc(ver, cin, C, nblocks, cp, cv, pc, po, oc, mo, act, 0, 0, blocks)
+        blocks[b] = _lib.BlockDesc(1, bi[1], bi[2], 0, 0, 0)
+    desc = _lib.NetDesc(ver, cin, C, nblocks, cp, cv, pc, po, oc, mo, act, 0, 0, blocks)
     ctx = lib.sayuri_hip_create(0, ctypes.byref(desc), max_batch, B, 1)
     assert ctx, lib.sayuri_hip_last_error()
     layers = [(0, "input_conv"), (1, "p_hd_conv"), (4, "p_inter_fc"), (5, "prob_conv"), (6, "pass_fc"), (7, "v_hd_conv"),
@@ -347,7 +302,7 @@ def direct_context(path, max_batch):
         for kind, suffix in ((0, ".w"), (1, ".b")):
             t = w.tensor(name + suffix)
             assert t is not None, name + suffix
-            assert lib.sayuri_hip_load_tensor(ctx, lid, kind, t.ctypes.data_as(FP), t.size) == 0, lib.sayuri_hip_last_error()
+            assert lib.sayuri_hip_load_tensor(ctx, lid, kind, _lib.fp(t), t.size) == 0, lib.sayuri_hip_last_error()
     w.close()
     return ctx
 
@@ -360,14 +315,14 @@ def test_a_pipe_without_ensembles_is_the_pipe_it_was(tmp_weights_dir):
     small tables of every ticket that has carried a symmetry batch."""
     g = Golden("net_6b96", tmp_weights_dir)
     lib = _lib.hip()
-    bytes_of_ctx = lambda c: int(lib.sayuri_hip_device_bytes(ctypes.c_void_p(c)))  # noqa: E731
+    bytes_of_ctx = lambda c: int(lib.sayuri_hip_device_bytes(c))  # noqa: E731
     bytes_of = lambda p: bytes_of_ctx(p.ctx(0))  # noqa: E731
     plain = HipForwardPipe(g.weights_path, board_size=B, batch_size=16, fp16=True, waittime_ms=0)
     default = HipForwardPipe(g.weights_path)
     ens = HipForwardPipe(g.weights_path, board_size=B, batch_size=16, fp16=True, waittime_ms=0, ensemble=2)
     big = HipForwardPipe(g.weights_path, board_size=B, batch_size=30, fp16=True, waittime_ms=0)
     direct = {n: direct_context(g.weights_path, n) for n in (16, 256)}
-    pinned = SymmPinned(lib, 1)
+    pinned = hipraw.PinnedSet(1, B, WORDS)
     try:
         assert not plain.AcceptsEnsemble() and ens.AcceptsEnsemble()
         for n, pipe in ((16, plain), (256, default)):
@@ -384,17 +339,12 @@ def test_a_pipe_without_ensembles_is_the_pipe_it_was(tmp_weights_dir):
             net.close()
         assert_same_output(outs["ens"], outs["plain"], game.n, "E = 0 against E = 2")
         # the same work on the directly made contexts: one 9x9 record, plain submit_packed, tickets 0 and 1 four times each
-        lib.sayuri_hip_submit_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, IP, FP, FP, FP, FP, IP]
         rec, _ = game.planes_packed(0)
-        rc_, pr, pa, mi, ow = pinned.sets[0]
-        np.ctypeslib.as_array(ctypes.cast(rc_, ctypes.POINTER(ctypes.c_uint32)), (WORDS,))[:] = rec
-        nine = np.asarray([9], np.int32)
+        pinned.records[:] = rec
+        pinned.bsz[0] = 9
         for ctx in direct.values():
             for _ in range(8):
-                tick = ctypes.c_int(-1)
-                assert lib.sayuri_hip_submit_packed(ctypes.c_void_p(ctx), 1, ctypes.c_void_p(rc_), 37, nine.ctypes.data_as(IP), ctypes.cast(pr, FP),
-                                                    ctypes.cast(pa, FP), ctypes.cast(mi, FP), ctypes.cast(ow, FP), ctypes.byref(tick)) == 0
-                assert lib.sayuri_hip_wait(ctypes.c_void_p(ctx), tick.value) == 0
+                hipraw.wait(ctx, hipraw.submit_packed(ctx, pinned, 1, 37))
         for n, pipe in ((16, plain), (256, default)):
             assert bytes_of(pipe) == bytes_of_ctx(direct[n]), ("after eight evaluations", n)
         # E = 2: a pipe of 16 + 14 samples plus the two small tables (256 bytes each) of every ticket that carried such a batch
@@ -404,6 +354,6 @@ def test_a_pipe_without_ensembles_is_the_pipe_it_was(tmp_weights_dir):
     finally:
         pinned.close()
         for c in direct.values():
-            lib.sayuri_hip_destroy(ctypes.c_void_p(c))
+            lib.sayuri_hip_destroy(c)
         for p in (plain, default, ens, big):
             p.Destroy()

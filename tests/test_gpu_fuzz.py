@@ -17,7 +17,6 @@ net is tight enough: with rounds 3-4's hand-back of the input buffer switched on
 fuzz comes back with wrong samples; with =1 the engine's row-stride table (engine.hip, "who may write which bytes when")
 refuses the forward before anything is launched.
 """
-import ctypes
 import os
 import threading
 import time
@@ -26,7 +25,7 @@ import numpy as np
 import pytest
 
 from _golden import Golden
-from sayuri_amd import _lib
+from sayuri_amd import _lib, hipraw
 from sayuri_amd import weights as W
 from sayuri_amd.engine import pack_planes
 from sayuri_amd.pipe import HipForwardPipe, hip_forward_packed_raw, hip_forward_raw
@@ -36,8 +35,6 @@ pytestmark = pytest.mark.gpu
 B = 19
 MAXB = 640
 WORDS = 37 * 12 + 8
-FP = ctypes.POINTER(ctypes.c_float)
-IP = ctypes.POINTER(ctypes.c_int)
 MAIN_SIZES, ODD_SIZES = (9, 13, 19), (2, 3, 5, 7, 11, 14, 16, 17)
 SWITCHES = ("SAYURI_TOWER", "SAYURI_CHAINS", "SAYURI_DEBUG_RECYCLE_INPUT")
 
@@ -101,48 +98,27 @@ def reference_bits(path, pool, fp16=True):
 
 
 class Pinned:
-    """Two sets of page-locked staging buffers for submit / wait (what the pump owns)."""
+    """Two sets of page-locked staging buffers for submit / wait (what the pump owns), filled from a Pool."""
 
-    def __init__(self, lib):
-        self.lib = lib
-        lib.sayuri_hip_host_alloc.restype = ctypes.c_void_p
-        lib.sayuri_hip_host_alloc.argtypes = [ctypes.c_size_t]
-        lib.sayuri_hip_host_free.argtypes = [ctypes.c_void_p]
-        lib.sayuri_hip_submit.argtypes = [ctypes.c_void_p, ctypes.c_int, FP, IP, FP, FP, FP, FP, IP]
-        lib.sayuri_hip_submit_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, IP, FP, FP, FP, FP, IP]
-        lib.sayuri_hip_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        self.sizes = (MAXB * 43 * B * B, MAXB * 5 * B * B, MAXB * 5, MAXB * 15, MAXB * B * B, MAXB)
-        self.sets = []
-        for _ in range(2):
-            ptrs = [lib.sayuri_hip_host_alloc(k * 4) for k in self.sizes]
-            assert all(ptrs)
-            self.sets.append(ptrs)
+    def __init__(self):
+        self.sets = [hipraw.PinnedSet(MAXB, B, 43 * B * B) for _ in range(2)]
 
     def close(self):
-        for ptrs in self.sets:
-            for q in ptrs:
-                self.lib.sayuri_hip_host_free(ctypes.c_void_p(q))
+        for s in self.sets:
+            s.close()
 
     def submit(self, ctx, i, pool, idx, packed):
-        pl, pr, pa, mi, ow, bz = self.sets[i]
-        n = len(idx)
-        np.ctypeslib.as_array(ctypes.cast(bz, ctypes.POINTER(ctypes.c_int32)), (n,))[:] = pool.bsz[idx]
-        tick = ctypes.c_int(-1)
-        args = (ctypes.cast(bz, IP), ctypes.cast(pr, FP), ctypes.cast(pa, FP), ctypes.cast(mi, FP), ctypes.cast(ow, FP), ctypes.byref(tick))
+        s, n = self.sets[i], len(idx)
+        s.bsz[:n] = pool.bsz[idx]
         if packed:
-            np.ctypeslib.as_array(ctypes.cast(pl, ctypes.POINTER(ctypes.c_uint32)), (n * WORDS,))[:] = pool.rec[idx].ravel()
-            rc = self.lib.sayuri_hip_submit_packed(ctx, n, ctypes.c_void_p(pl), 37, *args)
-        else:
-            np.ctypeslib.as_array(ctypes.cast(pl, FP), (n * 43 * B * B,))[:] = pool.grid[idx].ravel()
-            rc = self.lib.sayuri_hip_submit(ctx, n, ctypes.cast(pl, FP), *args)
-        assert rc == 0, self.lib.sayuri_hip_last_error()
-        return tick.value
+            s.records[:n * WORDS] = pool.rec[idx].ravel()
+            return hipraw.submit_packed(ctx, s, n, 37)
+        s.planes[:n * 43 * B * B] = pool.grid[idx].ravel()
+        return hipraw.submit(ctx, s, n)
 
     def wait(self, ctx, i, tick, n):
-        assert self.lib.sayuri_hip_wait(ctx, tick) == 0, self.lib.sayuri_hip_last_error()
-        _, pr, pa, mi, ow, _ = self.sets[i]
-        return (np.ctypeslib.as_array(ctypes.cast(pr, FP), (n, 5, B * B)).copy(), np.ctypeslib.as_array(ctypes.cast(pa, FP), (n, 5)).copy(),
-                np.ctypeslib.as_array(ctypes.cast(mi, FP), (n, 15)).copy(), np.ctypeslib.as_array(ctypes.cast(ow, FP), (n, B * B)).copy())
+        hipraw.wait(ctx, tick)
+        return tuple(a.copy() for a in self.sets[i].outputs(n))
 
 
 def wrong_samples(ref, got, idx):
@@ -202,7 +178,7 @@ def run_fuzz(nets, scenarios, seed, env_extra=None, stop_at_first=False, tmp_wei
     rng = np.random.default_rng(seed)
     paths = {name: Golden(name, tmp_weights_dir).weights_path for name in nets}
     refs = {name: reference_bits(paths[name], pool, fp16) for name in nets}
-    pipes, pinned, failures, ran = {}, Pinned(lib), [], []
+    pipes, pinned, failures, ran = {}, Pinned(), [], []
     env_extra = env_extra or {}
 
     def pipe_for(name, chains):

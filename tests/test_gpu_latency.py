@@ -45,9 +45,6 @@ def make_pipe(path, env=None, latency=False, batch=64, fp16=True):
                 os.environ[k] = v
 
 
-def _fp(a):
-    return a.ctypes.data_as(_lib.c_float_p)
-
 
 def grid_of(planes, bsz):
     gr = np.zeros((len(bsz), 43, B * B), np.float32)
@@ -95,14 +92,14 @@ def test_split_convolution_has_the_board_kernels_bits(case):
         xcat = np.concatenate([x.ravel() for x in xs])
         rcat = np.concatenate([r.ravel() for r in res]) if res else None
         board = np.zeros(sum(cout * b * b for b in bsz), np.float32)
-        rc = lib.sayuri_hip_test_conv(0, 1, n, bs_arr.ctypes.data_as(_lib.c_int_p), B, cin, cout, 3, 0, act, 0, _fp(xcat), _fp(w.ravel()),
-                                      _fp(bias), _fp(rcat) if res else None, _fp(board))
+        rc = lib.sayuri_hip_test_conv(0, 1, n, bs_arr.ctypes.data_as(_lib.c_int_p), B, cin, cout, 3, 0, act, 0, _lib.fp(xcat), _lib.fp(w.ravel()),
+                                      _lib.fp(bias), _lib.fp(rcat) if res else None, _lib.fp(board))
         assert rc == 0, lib.sayuri_hip_last_error().decode()
         assert lib.sayuri_hip_test_last_conv_kind() == KIND_BOARD, "the yardstick is the board kernel"
         for strips in (1, 2, 4, max(bsz), 0):
             y = np.full_like(board, np.nan)
-            rc = lib.sayuri_hip_test_conv_split(0, n, bs_arr.ctypes.data_as(_lib.c_int_p), B, cin, cout, act, _fp(xcat), _fp(w.ravel()),
-                                                _fp(bias), _fp(rcat) if res else None, _fp(y), 0, strips)
+            rc = lib.sayuri_hip_test_conv_split(0, n, bs_arr.ctypes.data_as(_lib.c_int_p), B, cin, cout, act, _lib.fp(xcat), _lib.fp(w.ravel()),
+                                                _lib.fp(bias), _lib.fp(rcat) if res else None, _lib.fp(y), 0, strips)
             assert rc == 0, lib.sayuri_hip_last_error().decode()
             assert lib.sayuri_hip_test_last_conv_kind() == KIND_SPLIT
             assert np.array_equal(y, board), (case, act, with_res, strips, float(np.nanmax(np.abs(y - board))))
@@ -129,12 +126,12 @@ def test_split_convolution_every_activation_and_post_residual_layer():
         for split in (None, 10):
             y = np.zeros(sum(128 * b * b for b in bsz), np.float32)
             if split is None:
-                rc = lib.sayuri_hip_test_conv(0, 1, 2, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, 3, 0, act, 0, _fp(xcat), _fp(w.ravel()),
-                                              _fp(bias), _fp(rcat), _fp(y))
+                rc = lib.sayuri_hip_test_conv(0, 1, 2, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, 3, 0, act, 0, _lib.fp(xcat), _lib.fp(w.ravel()),
+                                              _lib.fp(bias), _lib.fp(rcat), _lib.fp(y))
                 assert rc == 0 and lib.sayuri_hip_test_last_conv_kind() == KIND_BOARD
             else:
-                rc = lib.sayuri_hip_test_conv_split(0, 2, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, act, _fp(xcat), _fp(w.ravel()),
-                                                    _fp(bias), _fp(rcat), _fp(y), 2, split)
+                rc = lib.sayuri_hip_test_conv_split(0, 2, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, act, _lib.fp(xcat), _lib.fp(w.ravel()),
+                                                    _lib.fp(bias), _lib.fp(rcat), _lib.fp(y), 2, split)
                 assert rc == 0, lib.sayuri_hip_last_error().decode()
             out.append(y)
         assert np.array_equal(out[0], out[1]), act
@@ -144,10 +141,10 @@ def test_split_tap_refuses_what_the_kernel_does_not_cover():
     lib = _lib.hip()
     bs_arr = np.asarray([19], np.int32)
     x, w, y = np.zeros(96 * 361, np.float32), np.zeros(96 * 96 * 9, np.float32), np.zeros(96 * 361, np.float32)
-    rc = lib.sayuri_hip_test_conv_split(0, 1, bs_arr.ctypes.data_as(_lib.c_int_p), B, 96, 96, 0, _fp(x), _fp(w), None, None, _fp(y), 0, 0)
+    rc = lib.sayuri_hip_test_conv_split(0, 1, bs_arr.ctypes.data_as(_lib.c_int_p), B, 96, 96, 0, _lib.fp(x), _lib.fp(w), None, None, _lib.fp(y), 0, 0)
     assert rc == -1 and b"64-channel" in lib.sayuri_hip_last_error()   # 96 weight rows: the layer keeps the default route
     x, w, y = np.zeros(64 * 361, np.float32), np.zeros(128 * 64 * 9, np.float32), np.zeros(128 * 361, np.float32)
-    rc = lib.sayuri_hip_test_conv_split(0, 1, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, 0, _fp(x), _fp(w), None, None, _fp(y), 3, 0)
+    rc = lib.sayuri_hip_test_conv_split(0, 1, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, 0, _lib.fp(x), _lib.fp(w), None, None, _lib.fp(y), 3, 0)
     assert rc == -1 and b"channel tiles" in lib.sayuri_hip_last_error()
 
 
@@ -234,11 +231,10 @@ def test_a_position_does_not_depend_on_its_batch_mates_in_latency_mode(name, tmp
 def test_packed_planes_and_two_tickets_in_latency_mode(tmp_weights_dir):
     """submit_packed gives the submit bits, and two tickets in flight (different batches, six rounds) give the solo bits."""
     g = Golden("net_20b256", tmp_weights_dir)
-    lib = _lib.hip()
     pool = FZ.Pool()
     rng = np.random.default_rng(11)
     pipe = make_pipe(g.weights_path, latency=True, batch=FZ.MAXB)
-    pinned = FZ.Pinned(lib)
+    pinned = FZ.Pinned()
     try:
         ctx = pipe.ctx(0)
         idxs = [pool.draw(rng, 3, "mixed"), pool.draw(rng, 11, "wild")]
@@ -282,20 +278,9 @@ def test_default_context_is_untouched_and_flags_are_checked(tmp_weights_dir, mon
     with pytest.raises(RuntimeError, match="fp16 engine"):
         make_pipe(g.weights_path, latency=True, fp16=False)
     # ... and at the C-ABI itself: NULL and a message
-    from sayuri_amd import _lib as L
-
-    class Block(ctypes.Structure):
-        _fields_ = [(n, ctypes.c_int32) for n in ("type", "apply_se", "se_size", "btl", "ffn", "dw")]
-
-    class Desc(ctypes.Structure):
-        _fields_ = [(n, ctypes.c_int32) for n in ("version", "input_channels", "residual_channels", "residual_blocks", "policy_head_channels",
-                                                  "value_head_channels", "probabilities_channels", "pass_probability_outputs",
-                                                  "ownership_channels", "value_misc_outputs", "default_act", "policy_head_type",
-                                                  "policy_dw_filter")] + [("blocks", ctypes.POINTER(Block))]
-
-    blk = (Block * 1)(Block(1, 0, 0, 0, 0, 0))
-    d = Desc(5, 43, 64, 1, 16, 16, 5, 5, 1, 15, 5, 0, 0, blk)
-    assert L.hip().sayuri_hip_create_ex(0, ctypes.byref(d), 4, 19, 0, 1) is None
+    blk = (_lib.BlockDesc * 1)(_lib.BlockDesc(1, 0, 0, 0, 0, 0))
+    d = _lib.NetDesc(5, 43, 64, 1, 16, 16, 5, 5, 1, 15, 5, 0, 0, blk)
+    assert lib.sayuri_hip_create_ex(0, ctypes.byref(d), 4, 19, 0, 1) is None
     assert b"fp16" in lib.sayuri_hip_last_error()
 
 
@@ -315,7 +300,7 @@ def test_latency_context_needs_at_most_half_the_device_time_of_a_lone_board(tmp_
         times = {k: [] for k in pipes}
         bs = np.asarray([19], np.int32)
         for k, p in pipes.items():
-            assert lib.sayuri_hip_upload(p.ctx(0), 1, _fp(gr), bs.ctypes.data_as(_lib.c_int_p)) == 0
+            assert lib.sayuri_hip_upload(p.ctx(0), 1, _lib.fp(gr), bs.ctypes.data_as(_lib.c_int_p)) == 0
             ms = ctypes.c_float(0)
             assert lib.sayuri_hip_time_runs(p.ctx(0), 50, ctypes.byref(ms)) == 0   # warm-up
         for _ in range(3):
@@ -337,13 +322,12 @@ def test_latency_bit_identity_fuzz(tmp_weights_dir, capsys):
     """20 scenarios drawn the way test_gpu_fuzz.py draws them -- network, 1..64 positions, uniform / mixed / wild sizes, one or two
     tickets in flight, packed or fp32 planes -- in a latency context, every sample against the bits of its position in the
     separate-SE default context."""
-    lib = _lib.hip()
     pool = FZ.Pool()
     rng = np.random.default_rng(20261016)
     nets = ["net_20b256", "net_40b384", "net_6b96"]
     paths = {n: Golden(n, tmp_weights_dir).weights_path for n in nets}
     refs, pipes = {}, {}
-    pinned = FZ.Pinned(lib)
+    pinned = FZ.Pinned()
     failures, ran = [], []
     try:
         for k in range(20):

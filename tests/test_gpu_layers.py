@@ -15,9 +15,6 @@ from sayuri_amd import _lib
 pytestmark = pytest.mark.gpu
 
 
-def _fp(a):
-    return a.ctypes.data_as(_lib.c_float_p)
-
 
 def act_np(x, act):
     """The eight activations of the reference (src/neural/activation.h:36-81), float64."""
@@ -95,8 +92,8 @@ def run_case(fp16, bsz, cin, cout, k, depthwise=False, act=5, with_res=True, pos
     y = np.zeros(sum(cout * b * b for b in bsz), np.float32)
     bs_arr = np.asarray(bsz, np.int32)
     rc = _lib.hip().sayuri_hip_test_conv(0, int(fp16), n, bs_arr.ctypes.data_as(_lib.c_int_p), max_board, cin, cout, k,
-                                         int(depthwise), act, int(post), _fp(xcat), _fp(w.ravel()), _fp(bias),
-                                         _fp(rcat) if res else None, _fp(y))
+                                         int(depthwise), act, int(post), _lib.fp(xcat), _lib.fp(w.ravel()), _lib.fp(bias),
+                                         _lib.fp(rcat) if res else None, _lib.fp(y))
     assert rc == 0, _lib.hip().sayuri_hip_last_error().decode()
     off = 0
     worst = 0.0
@@ -184,7 +181,7 @@ def test_conv_board_batch256():
     def run(xx):
         y = np.zeros((n, cout, 361), np.float32)
         rc = lib.sayuri_hip_test_conv(0, 1, n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, cin, cout, 3, 0, 5, 0,
-                                      _fp(np.ascontiguousarray(xx).ravel()), _fp(w.ravel()), _fp(bias), None, _fp(y.ravel()))
+                                      _lib.fp(np.ascontiguousarray(xx).ravel()), _lib.fp(w.ravel()), _lib.fp(bias), None, _lib.fp(y.ravel()))
         assert rc == 0, lib.sayuri_hip_last_error().decode()
         assert lib.sayuri_hip_test_last_conv_kind() == KIND_BOARD
         return y
@@ -218,7 +215,7 @@ def test_conv_batch256_tile_seams():
     y = np.zeros((n, cout, 361), np.float32)
     lib = _lib.hip()
     rc = lib.sayuri_hip_test_conv(0, 0, n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, cin, cout, 3, 0, 0, 0,
-                                  _fp(x.ravel()), _fp(w.ravel()), None, None, _fp(y.ravel()))
+                                  _lib.fp(x.ravel()), _lib.fp(w.ravel()), None, None, _lib.fp(y.ravel()))
     assert rc == 0, lib.sayuri_hip_last_error().decode()
     for i in (0, 1, 100, 177, 255):
         ref = conv_ref([x[i].astype(np.float64)], [19], w.astype(np.float64), None, None, 3, False, 0, False)[0]
@@ -227,7 +224,7 @@ def test_conv_batch256_tile_seams():
     perm = rng.permutation(n)
     y2 = np.zeros_like(y)
     rc = lib.sayuri_hip_test_conv(0, 0, n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, cin, cout, 3, 0, 0, 0,
-                                  _fp(np.ascontiguousarray(x[perm]).ravel()), _fp(w.ravel()), None, None, _fp(y2.ravel()))
+                                  _lib.fp(np.ascontiguousarray(x[perm]).ravel()), _lib.fp(w.ravel()), None, None, _lib.fp(y2.ravel()))
     assert rc == 0
     np.testing.assert_array_equal(y2, y[perm])
 

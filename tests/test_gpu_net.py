@@ -790,9 +790,7 @@ def test_two_tickets_in_flight_give_the_solo_bits(tmp_weights_dir):
     persistent launches have 150 workgroups, so the other ticket's kernels run beside them and workgroups start late.  Every
     batch must come back with the bits the same batch gives alone (round 4's engine: 3 batches of 100 off, the 141 samples of the
     late workgroups -- the recycled input buffer of the test above)."""
-    import ctypes
-    from sayuri_amd import _lib
-    from sayuri_amd.pipe import hip_forward_raw
+    from sayuri_amd import hipraw
     g = Golden("net_20b256", tmp_weights_dir)
     rng = np.random.default_rng(56)
     B, n = 19, 256
@@ -801,41 +799,22 @@ def test_two_tickets_in_flight_give_the_solo_bits(tmp_weights_dir):
     grid = np.zeros((n, 43, B * B), np.float32)
     for i, (p, bs) in enumerate(zip(planes, bsz)):
         grid[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-    lib = _lib.hip()
-    FP = ctypes.POINTER(ctypes.c_float)
-    lib.sayuri_hip_host_alloc.restype = ctypes.c_void_p
-    lib.sayuri_hip_host_alloc.argtypes = [ctypes.c_size_t]
-    lib.sayuri_hip_host_free.argtypes = [ctypes.c_void_p]
-    lib.sayuri_hip_submit.argtypes = [ctypes.c_void_p, ctypes.c_int, FP, ctypes.POINTER(ctypes.c_int), FP, FP, FP, FP, ctypes.POINTER(ctypes.c_int)]
-    lib.sayuri_hip_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
     pipe = HipForwardPipe(g.weights_path, board_size=B, batch_size=n, fp16=True)
-    raw = []
+    sets = [hipraw.PinnedSet(n, B, 43 * B * B) for _ in range(2)]
     try:
         ctx = pipe.ctx(0)
-        ref = hip_forward_raw(ctx, grid, bsz, B)
-        sizes = (grid.size, n * 5 * B * B, n * 5, n * 15, n * B * B)
-        bufs = []
-        for _ in range(2):
-            ptrs = [lib.sayuri_hip_host_alloc(k * 4) for k in sizes]
-            raw += ptrs
-            np.ctypeslib.as_array(ctypes.cast(ptrs[0], FP), (grid.size,))[:] = grid.ravel()
-            bufs.append(ptrs)
-        hb = lib.sayuri_hip_host_alloc(n * 4)
-        raw.append(hb)
-        np.ctypeslib.as_array(ctypes.cast(hb, ctypes.POINTER(ctypes.c_int32)), (n,))[:] = np.asarray(bsz, np.int32)
-        bp = ctypes.cast(hb, ctypes.POINTER(ctypes.c_int))
-        tick = [ctypes.c_int(-1), ctypes.c_int(-1)]
+        ref = hipraw.hip_forward_raw(ctx, grid, bsz, B)
+        for s in sets:
+            s.planes[:] = grid.ravel()
+            s.bsz[:] = bsz
+        tick = [-1, -1]
 
         def submit(i):
-            pl, pr, pa, mi, ow = bufs[i]
-            assert lib.sayuri_hip_submit(ctx, n, ctypes.cast(pl, FP), bp, ctypes.cast(pr, FP), ctypes.cast(pa, FP), ctypes.cast(mi, FP),
-                                         ctypes.cast(ow, FP), ctypes.byref(tick[i])) == 0, lib.sayuri_hip_last_error()
+            tick[i] = hipraw.submit(ctx, sets[i], n)
 
         def check(i, k):
-            assert lib.sayuri_hip_wait(ctx, tick[i].value) == 0
-            pl, pr, pa, mi, ow = bufs[i]
-            got = (np.ctypeslib.as_array(ctypes.cast(pr, FP), (n, 5, B * B)), np.ctypeslib.as_array(ctypes.cast(pa, FP), (n, 5)),
-                   np.ctypeslib.as_array(ctypes.cast(mi, FP), (n, 15)), np.ctypeslib.as_array(ctypes.cast(ow, FP), (n, B * B)))
+            hipraw.wait(ctx, tick[i])
+            got = sets[i].outputs(n)
             bad = sum(1 for s_ in range(n) if not all(np.array_equal(a[s_], b[s_]) for a, b in zip(ref, got)))
             assert bad == 0, (k, bad)
 
@@ -844,8 +823,8 @@ def test_two_tickets_in_flight_give_the_solo_bits(tmp_weights_dir):
             check(k & 1, k); submit(k & 1)
         check(0, 120); check(1, 121)
     finally:
-        for q in raw:
-            lib.sayuri_hip_host_free(ctypes.c_void_p(q))
+        for s in sets:
+            s.close()
         pipe.Destroy()
 
 
@@ -856,9 +835,8 @@ def test_packed_records_are_read_where_the_pump_has_them(tmp_weights_dir):
     with DIFFERENT records in their two buffers, refilled between rounds: every batch must come back with the bits the
     blocking, copying entry point (sayuri_hip_forward_packed) gives for the same records; records in pageable memory take the
     copy and give the same bits again."""
-    from sayuri_amd import _lib
+    from sayuri_amd import hipraw
     from sayuri_amd.engine import pack_planes
-    from sayuri_amd.pipe import hip_forward_packed_raw
     g = Golden("net_20b256", tmp_weights_dir)
     B, n, words = 19, 64, 37 * 12 + 8
     sets = []
@@ -866,49 +844,28 @@ def test_packed_records_are_read_where_the_pump_has_them(tmp_weights_dir):
         bsz = [19] * n if k < 2 else [int(b) for b in np.random.default_rng(77).choice([9, 13, 19], size=n)]
         planes = W.synthetic_planes(n, bsz, seed=9100 + k)
         sets.append((np.stack([pack_planes(p, 37) for p in planes]).astype(np.uint32), bsz))
-    lib = _lib.hip()
-    FP = ctypes.POINTER(ctypes.c_float)
-    IP = ctypes.POINTER(ctypes.c_int)
-    lib.sayuri_hip_host_alloc.restype = ctypes.c_void_p
-    lib.sayuri_hip_host_alloc.argtypes = [ctypes.c_size_t]
-    lib.sayuri_hip_host_free.argtypes = [ctypes.c_void_p]
-    lib.sayuri_hip_submit_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, IP, FP, FP, FP, FP, IP]
-    lib.sayuri_hip_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
     pipe = HipForwardPipe(g.weights_path, board_size=B, batch_size=n, fp16=True)
-    raw = []
+    bufs = [hipraw.PinnedSet(n, B, words) for _ in range(2)]
     try:
         ctx = pipe.ctx(0)
-        refs = [hip_forward_packed_raw(ctx, rec, 37, bsz, B) for rec, bsz in sets]
+        refs = [hipraw.hip_forward_packed_raw(ctx, rec, 37, bsz, B) for rec, bsz in sets]
         assert not np.array_equal(refs[0][0], refs[1][0])
-        sizes = (n * words, n * 5 * B * B, n * 5, n * 15, n * B * B, n)
-        bufs = []
-        for _ in range(2):
-            ptrs = [lib.sayuri_hip_host_alloc(k * 4) for k in sizes]
-            assert all(ptrs)
-            raw += ptrs
-            bufs.append(ptrs)
-        tick = [ctypes.c_int(-1), ctypes.c_int(-1)]
+        tick = [-1, -1]
         holds = [None, None]
 
         def submit(i, k, pageable=False):
             rec, bsz = sets[k]
-            pl, pr, pa, mi, ow, bz = bufs[i]
-            np.ctypeslib.as_array(ctypes.cast(bz, ctypes.POINTER(ctypes.c_int32)), (n,))[:] = np.asarray(bsz, np.int32)
+            bufs[i].bsz[:] = bsz
             if pageable:
                 holds[i] = np.ascontiguousarray(rec)  # kept alive until the wait
-                src = ctypes.c_void_p(holds[i].ctypes.data)
             else:
-                np.ctypeslib.as_array(ctypes.cast(pl, ctypes.POINTER(ctypes.c_uint32)), (n * words,))[:] = rec.ravel()
-                src = ctypes.c_void_p(pl)
-            assert lib.sayuri_hip_submit_packed(ctx, n, src, 37, ctypes.cast(bz, IP), ctypes.cast(pr, FP), ctypes.cast(pa, FP),
-                                                ctypes.cast(mi, FP), ctypes.cast(ow, FP), ctypes.byref(tick[i])) == 0, lib.sayuri_hip_last_error()
+                holds[i] = None
+                bufs[i].records[:] = rec.ravel()
+            tick[i] = hipraw.submit_packed(ctx, bufs[i], n, 37, holds[i])
 
         def check(i, k):
-            assert lib.sayuri_hip_wait(ctx, tick[i].value) == 0
-            pl, pr, pa, mi, ow, bz = bufs[i]
-            got = (np.ctypeslib.as_array(ctypes.cast(pr, FP), (n, 5, B * B)), np.ctypeslib.as_array(ctypes.cast(pa, FP), (n, 5)),
-                   np.ctypeslib.as_array(ctypes.cast(mi, FP), (n, 15)), np.ctypeslib.as_array(ctypes.cast(ow, FP), (n, B * B)))
-            for a, b, what in zip(refs[k], got, ("prob", "pass", "misc", "own")):
+            hipraw.wait(ctx, tick[i])
+            for a, b, what in zip(refs[k], bufs[i].outputs(n), ("prob", "pass", "misc", "own")):
                 assert np.array_equal(a, b), (k, what)
 
         order = [0, 1, 2, 1, 0, 2, 2, 0, 1, 0]
@@ -917,8 +874,8 @@ def test_packed_records_are_read_where_the_pump_has_them(tmp_weights_dir):
             check(j & 1, order[j - 2]); submit(j & 1, order[j], pageable=(j >= 7))
         check(0, order[-2]); check(1, order[-1])
     finally:
-        for q in raw:
-            lib.sayuri_hip_host_free(ctypes.c_void_p(q))
+        for s in bufs:
+            s.close()
         pipe.Destroy()
 
 

@@ -35,10 +35,6 @@ pytestmark = pytest.mark.gpu
 FP = ctypes.POINTER(ctypes.c_float)
 
 
-def _fp(a):
-    return a.ctypes.data_as(FP)
-
-
 def oracle():
     lib = PortNet.lib()
     lib.so_tap_se_unit.argtypes = [ctypes.c_int] * 3 + [FP] * 6 + [ctypes.c_int]
@@ -74,25 +70,24 @@ def test_se_unit_kernels(act, fp16):
         y = np.zeros_like(xcat)
         gate = np.zeros((n, 2 * C), np.float32)
         bs_arr = np.asarray(bsz, np.int32)
-        lib.sayuri_hip_test_se_unit.argtypes = [ctypes.c_int] * 3 + [_lib.c_int_p] + [ctypes.c_int] * 4 + [FP] * 8
-        rc = lib.sayuri_hip_test_se_unit(0, int(fp16), n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, _fp(xcat),
-                                         _fp(rcat) if rs else None, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(y), _fp(gate))
+        rc = lib.sayuri_hip_test_se_unit(0, int(fp16), n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, _lib.fp(xcat),
+                                         _lib.fp(rcat) if rs else None, _lib.fp(w1), _lib.fp(b1), _lib.fp(w2), _lib.fp(b2), _lib.fp(y), _lib.fp(gate))
         assert rc == 0, lib.sayuri_hip_last_error().decode()
         off = 0
         for i, b in enumerate(bsz):
             S = b * b
             # GlobalPooling<false> + both FullyConnects -> the gate
             pool = np.zeros(3 * C, np.float32)
-            o.so_tap_global_pool(b, C, _fp(xs[i]), _fp(pool), 0)
+            o.so_tap_global_pool(b, C, _lib.fp(xs[i]), _lib.fp(pool), 0)
             mid = np.zeros(se, np.float32)
-            o.so_tap_fully_connect(3 * C, se, _fp(w1), _fp(b1), _fp(pool), _fp(mid), act)
+            o.so_tap_fully_connect(3 * C, se, _lib.fp(w1), _lib.fp(b1), _lib.fp(pool), _lib.fp(mid), act)
             exc = np.zeros(2 * C, np.float32)
-            o.so_tap_fully_connect(se, 2 * C, _fp(w2), _fp(b2), _fp(mid), _fp(exc), 0)
+            o.so_tap_fully_connect(se, 2 * C, _lib.fp(w2), _lib.fp(b2), _lib.fp(mid), _lib.fp(exc), 0)
             exp_gate = np.concatenate([1.0 / (1.0 + np.exp(-exc[:C].astype(np.float64))), exc[C:]])
             assert np.abs(gate[i] - exp_gate).max() <= 1e-4 * max(1.0, np.abs(exp_gate).max()), (bsz, i, "gate")
             # the whole unit
             ref = xs[i].copy()
-            o.so_tap_se_unit(b, C, se, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(ref), _fp(rs[i]) if rs else None, act)
+            o.so_tap_se_unit(b, C, se, _lib.fp(w1), _lib.fp(b1), _lib.fp(w2), _lib.fp(b2), _lib.fp(ref), _lib.fp(rs[i]) if rs else None, act)
             got = y[off:off + C * S].reshape(C, S)
             off += C * S
             scale = max(1.0, float(np.abs(ref).max()))
@@ -113,7 +108,7 @@ def test_head_tail_kernel(act, fp16):
         shapes = [(Cp, 3 * Cp), (Cp,), (pass_outs, Cp), (pass_outs,), (3 * Cv, 3 * Cv), (3 * Cv,), (misc_outs, 3 * Cv), (misc_outs,),
                   (prob_ch, Cp), (prob_ch,), (Cv,), (1,)]
         ws = [(rng.standard_normal(s) / np.sqrt(s[-1] if len(s) > 1 else 4)).astype(np.float32) for s in shapes]
-        warr = (FP * 12)(*[_fp(w) for w in ws])
+        warr = (FP * 12)(*[_lib.fp(w) for w in ws])
         pcat = np.concatenate([p.ravel() for p in pcs])
         vcat = np.concatenate([v.ravel() for v in vcs])
         prob = np.zeros((n, prob_ch, B2), np.float32)
@@ -121,17 +116,16 @@ def test_head_tail_kernel(act, fp16):
         misc = np.zeros((n, misc_outs), np.float32)
         own = np.zeros((n, B2), np.float32)
         bs_arr = np.asarray(bsz, np.int32)
-        lib.sayuri_hip_test_head_tail.argtypes = [ctypes.c_int] * 3 + [_lib.c_int_p] + [ctypes.c_int] * 7 + [FP, FP, ctypes.POINTER(FP)] + [FP] * 4
         rc = lib.sayuri_hip_test_head_tail(0, int(fp16), n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, Cp, Cv, prob_ch, pass_outs, misc_outs, act,
-                                           _fp(pcat), _fp(vcat), warr, _fp(prob), _fp(pas), _fp(misc), _fp(own))
+                                           _lib.fp(pcat), _lib.fp(vcat), warr, _lib.fp(prob), _lib.fp(pas), _lib.fp(misc), _lib.fp(own))
         assert rc == 0, lib.sayuri_hip_last_error().decode()
         for i, b in enumerate(bsz):
             S = b * b
             e_prob, e_pass = np.zeros((prob_ch, S), np.float32), np.zeros(pass_outs, np.float32)
             e_own, e_misc = np.zeros(S, np.float32), np.zeros(misc_outs, np.float32)
             pc = pcs[i].copy()
-            o.so_tap_head_tail(b, Cp, Cv, prob_ch, pass_outs, misc_outs, act, _fp(pc), _fp(vcs[i]), *[_fp(w) for w in ws],
-                               _fp(e_prob), _fp(e_pass), _fp(e_own), _fp(e_misc))
+            o.so_tap_head_tail(b, Cp, Cv, prob_ch, pass_outs, misc_outs, act, _lib.fp(pc), _lib.fp(vcs[i]), *[_lib.fp(w) for w in ws],
+                               _lib.fp(e_prob), _lib.fp(e_pass), _lib.fp(e_own), _lib.fp(e_misc))
             tol = 2e-4
             got_prob = prob[i].reshape(prob_ch, 19, 19)[:, :b, :b].reshape(prob_ch, S)
             got_own = own[i].reshape(19, 19)[:b, :b].ravel()
@@ -241,7 +235,6 @@ def test_conv_with_se_unit_inside(act, via_tower):
     one sample per tile (fused) and several samples per tile (the tap must report the fallback)."""
     lib, o = _lib.hip(), oracle()
     rng = np.random.default_rng(300 + act)
-    lib.sayuri_hip_test_conv_se.argtypes = [ctypes.c_int] * 2 + [_lib.c_int_p] + [ctypes.c_int] * 5 + [FP] * 9
     cases = [([19, 19, 19], 256, 64, True), ([19] * 2, 128, 32, False), ([19, 17, 16, 15, 14], 128, 24, True), ([19], 96, 24, True)]
     # small boards one per batch (a batch of several small boards shares a tile: checked below)
     cases += [([b], 128, 32, bool(b & 1)) for b in (2, 3, 5, 9, 13)][act % 5:act % 5 + 2]
@@ -259,8 +252,8 @@ def test_conv_with_se_unit_inside(act, via_tower):
         rcat = np.concatenate([r.ravel() for r in rs]) if rs else None
         y = np.zeros_like(xcat)
         bs_arr = np.asarray(bsz, np.int32)
-        rc = lib.sayuri_hip_test_conv_se(0, n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, via_tower, _fp(xcat), _fp(w), _fp(bias),
-                                         _fp(rcat) if rs else None, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(y))
+        rc = lib.sayuri_hip_test_conv_se(0, n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, via_tower, _lib.fp(xcat), _lib.fp(w), _lib.fp(bias),
+                                         _lib.fp(rcat) if rs else None, _lib.fp(w1), _lib.fp(b1), _lib.fp(w2), _lib.fp(b2), _lib.fp(y))
         if C % 128:  # no board kernel for this channel count (the engine runs such layers on conv_mfma + the separate SE kernels)
             assert rc == 1
             continue
@@ -270,7 +263,7 @@ def test_conv_with_se_unit_inside(act, via_tower):
             S = b * b
             ref = conv3x3_f64(xs[i], w, bias, b).astype(np.float32)
             ref = np.ascontiguousarray(ref)
-            o.so_tap_se_unit(b, C, se, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(ref), _fp(rs[i]) if rs else None, act)
+            o.so_tap_se_unit(b, C, se, _lib.fp(w1), _lib.fp(b1), _lib.fp(w2), _lib.fp(b2), _lib.fp(ref), _lib.fp(rs[i]) if rs else None, act)
             got = y[off:off + C * S].reshape(C, S)
             off += C * S
             scale = max(1.0, float(np.abs(ref).max()))
@@ -282,8 +275,8 @@ def test_conv_with_se_unit_inside(act, via_tower):
     dummy = np.zeros(4 * 128 * 81, np.float32)
     w = np.zeros((128, 128, 3, 3), np.float32)
     z = np.zeros(3 * 128 * 32 + 512, np.float32)
-    rc = lib.sayuri_hip_test_conv_se(0, 4, bs_arr.ctypes.data_as(_lib.c_int_p), 19, 128, 32, act, via_tower, _fp(dummy), _fp(w), _fp(z), None,
-                                     _fp(z), _fp(z), _fp(z), _fp(z), _fp(dummy.copy()))
+    rc = lib.sayuri_hip_test_conv_se(0, 4, bs_arr.ctypes.data_as(_lib.c_int_p), 19, 128, 32, act, via_tower, _lib.fp(dummy), _lib.fp(w), _lib.fp(z), None,
+                                     _lib.fp(z), _lib.fp(z), _lib.fp(z), _lib.fp(z), _lib.fp(dummy.copy()))
     assert rc == 1
 
 
@@ -294,7 +287,6 @@ def test_head_board_kernel(act):
     24 / 32 / 48."""
     lib, o = _lib.hip(), oracle()
     rng = np.random.default_rng(400 + act)
-    lib.sayuri_hip_test_head_board.argtypes = [ctypes.c_int] * 2 + [_lib.c_int_p] + [ctypes.c_int] * 8 + [FP] * 5 + [ctypes.POINTER(FP)] + [FP] * 4
     for bsz, C, Cp, Cv in ((BOARDS[act % len(BOARDS)], 128, 24, 24), (BOARDS[(act + 2) % len(BOARDS)], 256, 32, 32), ([19, 13, 2], 256, 32, 48),
                            ([19, 5], 128, 48, 32)):
         n, prob_ch, pass_outs, misc_outs, B2 = len(bsz), 5, 5, 15, 361
@@ -308,7 +300,7 @@ def test_head_board_kernel(act):
         ws = [(rng.standard_normal(s) / np.sqrt(s[-1] if len(s) > 1 else 4)).astype(np.float32) for s in shapes]
         ws[8] = r16(ws[8], True)   # the per-pixel weights are an fp16 MFMA image in the kernel
         ws[10] = r16(ws[10], True)
-        warr = (FP * 12)(*[_fp(w) for w in ws])
+        warr = (FP * 12)(*[_lib.fp(w) for w in ws])
         tcat = np.concatenate([t.ravel() for t in ts])
         prob = np.zeros((n, prob_ch, B2), np.float32)
         pas = np.zeros((n, pass_outs), np.float32)
@@ -316,7 +308,7 @@ def test_head_board_kernel(act):
         own = np.zeros((n, B2), np.float32)
         bs_arr = np.asarray(bsz, np.int32)
         rc = lib.sayuri_hip_test_head_board(0, n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, Cp, Cv, prob_ch, pass_outs, misc_outs, act,
-                                            _fp(tcat), _fp(p_w), _fp(p_b), _fp(v_w), _fp(v_b), warr, _fp(prob), _fp(pas), _fp(misc), _fp(own))
+                                            _lib.fp(tcat), _lib.fp(p_w), _lib.fp(p_b), _lib.fp(v_w), _lib.fp(v_b), warr, _lib.fp(prob), _lib.fp(pas), _lib.fp(misc), _lib.fp(own))
         assert rc == 0, (bsz, C, Cp, Cv, rc, lib.sayuri_hip_last_error().decode())
         for i, b in enumerate(bsz):
             S = b * b
@@ -326,8 +318,8 @@ def test_head_board_kernel(act):
             pc, vc = np.ascontiguousarray(pc), np.ascontiguousarray(vc)
             e_prob, e_pass = np.zeros((prob_ch, S), np.float32), np.zeros(pass_outs, np.float32)
             e_own, e_misc = np.zeros(S, np.float32), np.zeros(misc_outs, np.float32)
-            o.so_tap_head_tail(b, Cp, Cv, prob_ch, pass_outs, misc_outs, act, _fp(pc), _fp(vc), *[_fp(w) for w in ws],
-                               _fp(e_prob), _fp(e_pass), _fp(e_own), _fp(e_misc))
+            o.so_tap_head_tail(b, Cp, Cv, prob_ch, pass_outs, misc_outs, act, _lib.fp(pc), _lib.fp(vc), *[_lib.fp(w) for w in ws],
+                               _lib.fp(e_prob), _lib.fp(e_pass), _lib.fp(e_own), _lib.fp(e_misc))
             # the head planes stay in fp32 registers; the per-pixel product runs on fp16-rounded planes: 2e-3 of the scale
             tol = 2e-3
             got_prob = prob[i].reshape(prob_ch, 19, 19)[:, :b, :b].reshape(prob_ch, S)
@@ -347,9 +339,7 @@ SX_STANDARD = (19,) * 5 + (13,) * 5 + (9,) * 6  # 10 tiles: a second group of 8 
 
 
 def sx_lib():
-    lib = _lib.hip()
-    lib.sayuri_hip_test_conv_sx.argtypes = [ctypes.c_int] * 2 + [_lib.c_int_p] + [ctypes.c_int] * 4 + [FP] * 9
-    return lib
+    return _lib.hip()
 
 
 def sx_call(bsz, C, se, act, xs, rs, w, bias, fc, max_board=19):
@@ -360,8 +350,8 @@ def sx_call(bsz, C, se, act, xs, rs, w, bias, fc, max_board=19):
     rcat = np.concatenate([r.ravel() for r in rs]) if rs is not None else None
     y = np.full(xcat.shape, np.nan, np.float32)
     bs_arr = np.asarray(bsz, np.int32)
-    rc = lib.sayuri_hip_test_conv_sx(0, len(bsz), bs_arr.ctypes.data_as(_lib.c_int_p), max_board, C, se, act, _fp(xcat), _fp(w), _fp(bias),
-                                     _fp(rcat) if rcat is not None else None, *[_fp(a) for a in fc], _fp(y))
+    rc = lib.sayuri_hip_test_conv_sx(0, len(bsz), bs_arr.ctypes.data_as(_lib.c_int_p), max_board, C, se, act, _lib.fp(xcat), _lib.fp(w), _lib.fp(bias),
+                                     _lib.fp(rcat) if rcat is not None else None, *[_lib.fp(a) for a in fc], _lib.fp(y))
     outs, off = [], 0
     for b in bsz:
         outs.append(y[off:off + C * b * b].reshape(C, b * b))
@@ -746,13 +736,12 @@ def head_ratio(a, b, ref, tol):
 def conv_se_call(T, fc, C, se, act, via_tower, with_res=True):
     """one launch of sayuri_hip_test_conv_se -> (return code, [y of each sample [C][b*b]]); y starts as NaN on the host"""
     lib = _lib.hip()
-    lib.sayuri_hip_test_conv_se.argtypes = [ctypes.c_int] * 2 + [_lib.c_int_p] + [ctypes.c_int] * 5 + [FP] * 9
     xcat = np.concatenate([x.ravel() for x in T.xs])
     rcat = np.concatenate([r.ravel() for r in T.rs]) if with_res else None
     y = np.full(xcat.shape, np.nan, np.float32)
     bs_arr = np.asarray(T.bsz, np.int32)
-    rc = lib.sayuri_hip_test_conv_se(0, len(T.bsz), bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, via_tower, _fp(xcat), _fp(T.w), _fp(T.bias),
-                                     _fp(rcat) if with_res else None, *[_fp(np.ascontiguousarray(a)) for a in fc], _fp(y))
+    rc = lib.sayuri_hip_test_conv_se(0, len(T.bsz), bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, via_tower, _lib.fp(xcat), _lib.fp(T.w), _lib.fp(T.bias),
+                                     _lib.fp(rcat) if with_res else None, *[_lib.fp(np.ascontiguousarray(a)) for a in fc], _lib.fp(y))
     outs, off = [], 0
     for b in T.bsz:
         outs.append(y[off:off + C * b * b].reshape(C, b * b))
@@ -813,14 +802,13 @@ def test_conv_se_test_can_fail(C, se, via_tower):
 def se_unit_call(fp16, bsz, C, se, act, xs, rs, fc):
     """one run of se_pool / se_fc / se_scale -> (return code, [y of each sample], gate [n][2C])"""
     lib = _lib.hip()
-    lib.sayuri_hip_test_se_unit.argtypes = [ctypes.c_int] * 3 + [_lib.c_int_p] + [ctypes.c_int] * 4 + [FP] * 8
     xcat = np.concatenate([x.ravel() for x in xs])
     rcat = np.concatenate([r.ravel() for r in rs])
     y = np.full(xcat.shape, np.nan, np.float32)
     gate = np.zeros((len(bsz), 2 * C), np.float32)
     bs_arr = np.asarray(bsz, np.int32)
-    rc = lib.sayuri_hip_test_se_unit(0, int(fp16), len(bsz), bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, _fp(xcat), _fp(rcat),
-                                     *[_fp(np.ascontiguousarray(a)) for a in fc], _fp(y), _fp(gate))
+    rc = lib.sayuri_hip_test_se_unit(0, int(fp16), len(bsz), bs_arr.ctypes.data_as(_lib.c_int_p), 19, C, se, act, _lib.fp(xcat), _lib.fp(rcat),
+                                     *[_lib.fp(np.ascontiguousarray(a)) for a in fc], _lib.fp(y), _lib.fp(gate))
     outs, off = [], 0
     for b in bsz:
         outs.append(y[off:off + C * b * b].reshape(C, b * b))
@@ -879,20 +867,18 @@ def head_call(H, act, fp16=True):
     per-pixel outputs cut to each sample's board; asserts that the off-board cells of the NN grid stayed 0"""
     lib = _lib.hip()
     d, n, B2 = HEAD_DIMS, len(H.bsz), 361
-    warr = (FP * 12)(*[_fp(w) for w in H.ws])
+    warr = (FP * 12)(*[_lib.fp(w) for w in H.ws])
     prob, own = np.zeros((n, d["prob_ch"], B2), np.float32), np.zeros((n, B2), np.float32)
     pas, misc = np.zeros((n, d["pass_outs"]), np.float32), np.zeros((n, d["misc_outs"]), np.float32)
     bs_arr = np.asarray(H.bsz, np.int32)
     if H.C == 0:
-        lib.sayuri_hip_test_head_tail.argtypes = [ctypes.c_int] * 3 + [_lib.c_int_p] + [ctypes.c_int] * 7 + [FP, FP, ctypes.POINTER(FP)] + [FP] * 4
         pcat, vcat = np.concatenate([p.ravel() for p in H.pcs]), np.concatenate([v.ravel() for v in H.vcs])
         rc = lib.sayuri_hip_test_head_tail(0, int(fp16), n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, H.Cp, H.Cv, d["prob_ch"], d["pass_outs"],
-                                           d["misc_outs"], act, _fp(pcat), _fp(vcat), warr, _fp(prob), _fp(pas), _fp(misc), _fp(own))
+                                           d["misc_outs"], act, _lib.fp(pcat), _lib.fp(vcat), warr, _lib.fp(prob), _lib.fp(pas), _lib.fp(misc), _lib.fp(own))
     else:
-        lib.sayuri_hip_test_head_board.argtypes = [ctypes.c_int] * 2 + [_lib.c_int_p] + [ctypes.c_int] * 8 + [FP] * 5 + [ctypes.POINTER(FP)] + [FP] * 4
         tcat = np.concatenate([t.ravel() for t in H.ts])
         rc = lib.sayuri_hip_test_head_board(0, n, bs_arr.ctypes.data_as(_lib.c_int_p), 19, H.C, H.Cp, H.Cv, d["prob_ch"], d["pass_outs"], d["misc_outs"],
-                                            act, _fp(tcat), _fp(H.p_w), _fp(H.p_b), _fp(H.v_w), _fp(H.v_b), warr, _fp(prob), _fp(pas), _fp(misc), _fp(own))
+                                            act, _lib.fp(tcat), _lib.fp(H.p_w), _lib.fp(H.p_b), _lib.fp(H.v_w), _lib.fp(H.v_b), warr, _lib.fp(prob), _lib.fp(pas), _lib.fp(misc), _lib.fp(own))
     outs = []
     for i, b in enumerate(H.bsz):
         mask = np.ones((19, 19), bool)

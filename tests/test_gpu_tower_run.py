@@ -21,7 +21,6 @@ Measured on an MI355X (every bits check exact, every report as expected), worst 
 on boards 2..19 0.11 (Mish) and 0.12 (ReLU, identity) at both widths; several workgroups 0.12; compiled epilogue in a run 0.11;
 index tables 0.11; input convolution first 0.11; SE layer in a run 0.14 (C = 256, se = 64), 0.15 (C = 128, se = 32), 0.12 (from
 L2); eight layers 0.09.  The can-fail case lands 130 .. 263 x the tolerance away."""
-import ctypes
 import functools
 
 import numpy as np
@@ -36,13 +35,6 @@ pytestmark = pytest.mark.gpu
 PLAIN_TOL = 4e-3  # times max|ref|: test_gpu_layers.py, fp16
 MAX_BOARD = 19
 
-
-def _fp(a):
-    return a.ctypes.data_as(_lib.c_float_p)
-
-
-def _ip(a):
-    return a.ctypes.data_as(_lib.c_int_p)
 
 
 def conv3x3_taps_f64(x, w64, bias, b):
@@ -118,12 +110,12 @@ def tower_run(spec, D, chain=1):
     xcat = np.concatenate([x.ravel() for x in D.xs])
     wcat = np.concatenate([w.ravel() for w in D.ws])
     fc = [np.ascontiguousarray(a) for a in D.fc] if spec.se else [None] * 4
-    rc = lib.sayuri_hip_test_tower_run(0, n, _ip(np.asarray(spec.bsz, np.int32)), MAX_BOARD, C, spec.cin0, L, _ip(np.asarray(spec.acts, np.int32)),
-                                       _ip(np.asarray(spec.res_from, np.int32)), _fp(wcat), _fp(np.ascontiguousarray(D.bias)),
-                                       spec.se[0] if spec.se else -1, spec.se[1] if spec.se else 0, *[_fp(a) if a is not None else None for a in fc],
-                                       chain, _fp(xcat), _fp(y))
+    rc = lib.sayuri_hip_test_tower_run(0, n, _lib.ip(np.asarray(spec.bsz, np.int32)), MAX_BOARD, C, spec.cin0, L, _lib.ip(np.asarray(spec.acts, np.int32)),
+                                       _lib.ip(np.asarray(spec.res_from, np.int32)), _lib.fp(wcat), _lib.fp(np.ascontiguousarray(D.bias)),
+                                       spec.se[0] if spec.se else -1, spec.se[1] if spec.se else 0, *[_lib.fp(a) if a is not None else None for a in fc],
+                                       chain, _lib.fp(xcat), _lib.fp(y))
     report = np.zeros(3, np.int32)
-    assert lib.sayuri_hip_test_last_tower_run(_ip(report)) == 0
+    assert lib.sayuri_hip_test_last_tower_run(_lib.ip(report)) == 0
     form = lib.sayuri_hip_test_last_se_form()
     return rc, [split(y[l * per:(l + 1) * per], spec.bsz, C) for l in range(L)], tuple(int(v) for v in report), form
 
@@ -146,13 +138,12 @@ def per_layer_kernel(spec, D, l, xin, res):
     bs_arr = np.asarray(spec.bsz, np.int32)
     w, bias = np.ascontiguousarray(D.ws[l]), np.ascontiguousarray(D.bias[l])
     if spec.se and spec.se[0] == l:
-        lib.sayuri_hip_test_conv_se.argtypes = [ctypes.c_int] * 2 + [_lib.c_int_p] + [ctypes.c_int] * 5 + [_lib.c_float_p] * 9
-        rc = lib.sayuri_hip_test_conv_se(0, n, _ip(bs_arr), MAX_BOARD, C, spec.se[1], spec.acts[l], 0, _fp(xcat), _fp(w), _fp(bias),
-                                         _fp(rcat) if res is not None else None, *[_fp(np.ascontiguousarray(a)) for a in D.fc], _fp(y))
+        rc = lib.sayuri_hip_test_conv_se(0, n, _lib.ip(bs_arr), MAX_BOARD, C, spec.se[1], spec.acts[l], 0, _lib.fp(xcat), _lib.fp(w), _lib.fp(bias),
+                                         _lib.fp(rcat) if res is not None else None, *[_lib.fp(np.ascontiguousarray(a)) for a in D.fc], _lib.fp(y))
         assert rc == 0, (spec, l, rc, lib.sayuri_hip_last_error().decode())
     else:
-        rc = lib.sayuri_hip_test_conv(0, 1, n, _ip(bs_arr), MAX_BOARD, cin, C, 3, 0, spec.acts[l], 0, _fp(xcat), _fp(w), _fp(bias),
-                                      _fp(rcat) if res is not None else None, _fp(y))
+        rc = lib.sayuri_hip_test_conv(0, 1, n, _lib.ip(bs_arr), MAX_BOARD, cin, C, 3, 0, spec.acts[l], 0, _lib.fp(xcat), _lib.fp(w), _lib.fp(bias),
+                                      _lib.fp(rcat) if res is not None else None, _lib.fp(y))
         assert rc == 0, (spec, l, rc, lib.sayuri_hip_last_error().decode())
         assert lib.sayuri_hip_test_last_conv_kind() == KIND_BOARD, "the bits reference is the board kernel"
     return split(y, spec.bsz, C)

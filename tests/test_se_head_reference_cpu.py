@@ -22,16 +22,13 @@ import numpy as np
 import pytest
 
 from _oracle import PortNet
+from sayuri_amd._lib import fp
 from test_gpu_smallops import (HEAD_BOARDS, HEAD_DIMS, HEAD_PAIRS, HEAD_SEED, SE_CASE_IDS, SE_CASES, SE_LAYERS, SE_SEED, SE_UNIT_BATCHES, SX_TOL,
                                head_inputs, head_pool_f64, head_ratio, head_tail_f64, se_apply_f64, se_case_batches, se_gate_f64, se_inputs,
                                se_pool_f64, se_unit_x)
 
 FP = ctypes.POINTER(ctypes.c_float)
 BAR = 4.0
-
-
-def _fp(a):
-    return a.ctypes.data_as(FP)
 
 
 @pytest.mark.parametrize("act", range(8))
@@ -48,8 +45,8 @@ def test_head_tail_f64_matches_the_oracle(act):
                 got = head_tail_f64(pc, vc, H.ws, bs, act)
                 e_prob, e_pass = np.zeros((d["prob_ch"], S), np.float32), np.zeros(d["pass_outs"], np.float32)
                 e_own, e_misc = np.zeros(S, np.float32), np.zeros(d["misc_outs"], np.float32)
-                o.so_tap_head_tail(bs, Cp, Cv, d["prob_ch"], d["pass_outs"], d["misc_outs"], act, _fp(pc.copy()), _fp(vc), *[_fp(w) for w in H.ws],
-                                   _fp(e_prob), _fp(e_pass), _fp(e_own), _fp(e_misc))
+                o.so_tap_head_tail(bs, Cp, Cv, d["prob_ch"], d["pass_outs"], d["misc_outs"], act, fp(pc.copy()), fp(vc), *[fp(w) for w in H.ws],
+                                   fp(e_prob), fp(e_pass), fp(e_own), fp(e_misc))
                 for name, g, e in zip(("prob", "pass", "own", "misc"), got, (e_prob, e_pass, e_own, e_misc)):
                     scale = max(1.0, float(np.abs(e).max()))
                     err = float(np.abs(g - e).max())

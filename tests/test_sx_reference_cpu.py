@@ -12,13 +12,10 @@ import numpy as np
 import pytest
 
 from _oracle import PortNet
+from sayuri_amd._lib import fp
 from test_gpu_smallops import (SX_TOL, se_apply_f64, se_gate_f64, se_pool_f64, se_unit_f64, sx_fc, sx_reference, sx_trunk)
 
 FP = ctypes.POINTER(ctypes.c_float)
-
-
-def _fp(a):
-    return a.ctypes.data_as(FP)
 
 
 @pytest.mark.parametrize("act", range(8))
@@ -37,7 +34,7 @@ def test_se_unit_f64_matches_the_oracle(act):
             b2 = (rng.standard_normal(2 * C) * 0.5).astype(np.float32)
             got = se_unit_f64(x, res, w1, b1, w2, b2, bs, act)
             exp = x.copy()
-            o.so_tap_se_unit(bs, C, se, _fp(w1), _fp(b1), _fp(w2), _fp(b2), _fp(exp), _fp(res) if with_res else None, act)
+            o.so_tap_se_unit(bs, C, se, fp(w1), fp(b1), fp(w2), fp(b2), fp(exp), fp(res) if with_res else None, act)
             scale = max(1.0, float(np.abs(exp).max()))
             err = float(np.abs(got - exp).max())
             assert np.isfinite(got).all()

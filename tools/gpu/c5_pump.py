@@ -6,7 +6,6 @@ HipForwardPipe does), a mixed 9/13/19 batch of 256 on the 40b x 384 network, und
     python tools/gpu/c5_pump.py [--steps 40]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -17,44 +16,26 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from sayuri_amd import _lib  # noqa: E402
+from sayuri_amd import _lib, hipraw  # noqa: E402
 from sayuri_amd import weights as W  # noqa: E402
 from sayuri_amd.engine import pack_planes  # noqa: E402
 from sayuri_amd.pipe import HipForwardPipe  # noqa: E402
 
 
 def run(lib, wpath, records, bsz, n, steps):
-    FP = ctypes.POINTER(ctypes.c_float)
-    lib.sayuri_hip_host_alloc.restype = ctypes.c_void_p
-    lib.sayuri_hip_host_alloc.argtypes = [ctypes.c_size_t]
-    lib.sayuri_hip_host_free.argtypes = [ctypes.c_void_p]
-    lib.sayuri_hip_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.sayuri_hip_submit_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                             FP, FP, FP, FP, ctypes.POINTER(ctypes.c_int)]
     pipe = HipForwardPipe(wpath, board_size=19, batch_size=n, fp16=True)
     ctx = pipe.ctx(0)
-    B2 = 361
-    sizes = (records.size, n * 5 * B2, n * 8, n * 32, n * B2)
-    raw, bufs = [], []
-    for _ in range(2):
-        ptrs = [lib.sayuri_hip_host_alloc(k * 4) for k in sizes]
-        raw += ptrs
-        np.ctypeslib.as_array(ctypes.cast(ptrs[0], ctypes.POINTER(ctypes.c_uint32)), (records.size,))[:] = records.ravel()
-        bufs.append(ptrs)
-    hb = lib.sayuri_hip_host_alloc(n * 4)
-    np.ctypeslib.as_array(ctypes.cast(hb, ctypes.POINTER(ctypes.c_int32)), (n,))[:] = bsz
-    bp = ctypes.cast(hb, ctypes.POINTER(ctypes.c_int))
-    tick = [ctypes.c_int(-1), ctypes.c_int(-1)]
+    sets = [hipraw.PinnedSet(n, 19, records.shape[1]) for _ in range(2)]
+    for s in sets:
+        s.records[:] = records.ravel()
+        s.bsz[:] = bsz
+    tick = [-1, -1]
 
     def submit(i):
-        pl, pr, pa, mi, ow = bufs[i]
-        if lib.sayuri_hip_submit_packed(ctx, n, ctypes.c_void_p(pl), 37, bp, ctypes.cast(pr, FP), ctypes.cast(pa, FP), ctypes.cast(mi, FP),
-                                        ctypes.cast(ow, FP), ctypes.byref(tick[i])):
-            raise RuntimeError(lib.sayuri_hip_last_error().decode())
+        tick[i] = hipraw.submit_packed(ctx, sets[i], n, 37)
 
     def wait(i):
-        if lib.sayuri_hip_wait(ctx, tick[i].value):
-            raise RuntimeError(lib.sayuri_hip_last_error().decode())
+        hipraw.wait(ctx, tick[i])
 
     for _ in range(3):
         submit(0); wait(0)
@@ -65,8 +46,8 @@ def run(lib, wpath, records, bsz, n, steps):
     wait(steps & 1); wait((steps + 1) & 1)
     dt = time.perf_counter() - t0
     chains = int(lib.sayuri_hip_last_chains(ctx))
-    for q in raw + [hb]:
-        lib.sayuri_hip_host_free(ctypes.c_void_p(q))
+    for s in sets:
+        s.close()
     pipe.Destroy()
     return n * steps / dt, dt / steps * 1e3, chains
 

@@ -27,15 +27,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from sayuri_amd import _lib  # noqa: E402
+from sayuri_amd import _lib, hipraw  # noqa: E402
 from sayuri_amd import weights as W  # noqa: E402
 from sayuri_amd.engine import pack_planes  # noqa: E402
 from sayuri_amd.pipe import HipForwardPipe  # noqa: E402
 
 B = 19
 WORDS = 37 * 12 + 8
-FP = ctypes.POINTER(ctypes.c_float)
-IP = ctypes.POINTER(ctypes.c_int)
 NETS = {"20b256": (W.spec_20b256, 22), "40b384": (W.spec_40b384, 23)}
 POINTS = [(n, 19) for n in (1, 2, 4, 8, 16, 32, 64)] + [(1, 9), (1, 13)]
 
@@ -48,39 +46,12 @@ def weights_path(net):
     return path
 
 
-class Staging:
-    """Pinned buffers for submit_packed / wait (what the pump owns)."""
-
-    def __init__(self, lib, nmax):
-        self.lib = lib
-        lib.sayuri_hip_host_alloc.restype = ctypes.c_void_p
-        lib.sayuri_hip_host_alloc.argtypes = [ctypes.c_size_t]
-        lib.sayuri_hip_host_free.argtypes = [ctypes.c_void_p]
-        lib.sayuri_hip_submit_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, IP, FP, FP, FP, FP, IP]
-        lib.sayuri_hip_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        self.ptrs = [lib.sayuri_hip_host_alloc(k * 4) for k in (nmax * WORDS, nmax * 5 * B * B, nmax * 5, nmax * 15, nmax * B * B, nmax)]
-        assert all(self.ptrs)
-
-    def close(self):
-        for q in self.ptrs:
-            self.lib.sayuri_hip_host_free(ctypes.c_void_p(q))
-
-    def load(self, rec, bsz):
-        n = len(bsz)
-        np.ctypeslib.as_array(ctypes.cast(self.ptrs[0], ctypes.POINTER(ctypes.c_uint32)), (n * WORDS,))[:] = rec.ravel()
-        np.ctypeslib.as_array(ctypes.cast(self.ptrs[5], ctypes.POINTER(ctypes.c_int32)), (n,))[:] = bsz
-
-    def round_trips(self, ctx, n, iters):
-        """-> wall ms per submit_packed / wait round trip."""
-        rec, pr, pa, mi, ow, bz = self.ptrs
-        tick = ctypes.c_int(-1)
-        args = (ctypes.c_void_p(rec), 37, ctypes.cast(bz, IP), ctypes.cast(pr, FP), ctypes.cast(pa, FP), ctypes.cast(mi, FP), ctypes.cast(ow, FP),
-                ctypes.byref(tick))
-        t0 = time.perf_counter()
-        for _ in range(iters):
-            if self.lib.sayuri_hip_submit_packed(ctx, n, *args) or self.lib.sayuri_hip_wait(ctx, tick.value):
-                raise RuntimeError(self.lib.sayuri_hip_last_error().decode())
-        return (time.perf_counter() - t0) * 1e3 / iters
+def round_trips(ctx, stage, n, iters):
+    """-> wall ms per submit_packed / wait round trip of the set's first n records."""
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        hipraw.wait(ctx, hipraw.submit_packed(ctx, stage, n, 37))
+    return (time.perf_counter() - t0) * 1e3 / iters
 
 
 def device_ms(lib, ctx, iters):
@@ -124,7 +95,7 @@ def main():
                 pipes[f"latency_split{s}"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
             finally:
                 del os.environ["SAYURI_LATENCY_SPLIT"]
-        stage = Staging(lib, 64)
+        stage = hipraw.PinnedSet(64, B, WORDS)
         res = {"points": [], "tower_state": {k: lib.sayuri_hip_tower_state(p.ctx(0)) for k, p in pipes.items()}}
         try:
             for n, bs in POINTS:
@@ -133,17 +104,18 @@ def main():
                 for i, p in enumerate(planes):
                     grid[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
                 bsz = np.full(n, bs, np.int32)
-                stage.load(np.stack([pack_planes(p, 37) for p in planes]).astype(np.uint32), bsz)
+                stage.records[:n * WORDS] = np.stack([pack_planes(p, 37) for p in planes]).astype(np.uint32).ravel()
+                stage.bsz[:n] = bsz
                 use = {k: p for k, p in pipes.items() if n == 1 or "split" not in k}
                 dev = {k: [] for k in use}
                 rt = {k: [] for k in use}
                 for r in range(-1, args.rounds):  # round -1: the warm-up
                     for k, p in use.items():
                         ctx = p.ctx(0)
-                        if lib.sayuri_hip_upload(ctx, n, grid.ctypes.data_as(FP), bsz.ctypes.data_as(IP)):
+                        if lib.sayuri_hip_upload(ctx, n, _lib.fp(grid), _lib.ip(bsz)):
                             raise RuntimeError(lib.sayuri_hip_last_error().decode())
                         it = args.warmup if r < 0 else args.iters
-                        d, w = device_ms(lib, ctx, it), stage.round_trips(ctx, n, it)
+                        d, w = device_ms(lib, ctx, it), round_trips(ctx, stage, n, it)
                         if r >= 0:
                             dev[k].append(d)
                             rt[k].append(w)
@@ -157,7 +129,7 @@ def main():
                     for k, p in use.items():
                         if "split" in k:
                             continue
-                        lib.sayuri_hip_upload(p.ctx(0), n, grid.ctypes.data_as(FP), bsz.ctypes.data_as(IP))
+                        lib.sayuri_hip_upload(p.ctx(0), n, _lib.fp(grid), _lib.ip(bsz))
                         pt[k]["kernel_classes_one_forward"] = kernel_classes(lib, p.ctx(0))
                 res["points"].append(pt)
         finally:
