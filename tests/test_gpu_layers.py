@@ -201,6 +201,8 @@ def test_conv_board_batch256():
 def test_depthwise(k, fp16):
     run_case(fp16, [19, 9, 13], 1, 48, k, depthwise=True, act=5, with_res=True, post=True, seed=k)
     run_case(fp16, [19, 7], 1, 32, k, depthwise=True, act=1, with_res=False, seed=k + 1)
+    run_case(fp16, [2, 3, 5], 1, 48, k, depthwise=True, act=5, with_res=True, post=True, seed=k + 2)  # boards smaller than the 5x5 and 7x7 kernels
+    run_case(fp16, [2, 3, 5], 1, 40, k, depthwise=True, act=1, with_res=False, seed=k + 3)
 
 
 def test_conv_batch256_tile_seams():
