@@ -1,0 +1,248 @@
+"""The numpy references of the kernel parity tests, each once: float64 restatements of what the CPU oracle computes (the
+activations, the direct convolution, the SE unit, the head tail) and the exact-arithmetic reference of test_gpu_exact.py.  No
+GPU, no device library: the test_*_reference_cpu.py modules pin these functions to the oracle and to each other.
+
+conv_ref is the general layer (any k, depthwise, residual in front of or behind the activation) written as the oracle writes
+it; conv3x3_f64 is the cheap 3x3 convolution of one sample as nine matrix products, pinned to conv_ref by
+test_tower_run_reference_cpu.py.  The two stay independent implementations."""
+import numpy as np
+
+
+def r16(a, fp16):
+    return a.astype(np.float16).astype(np.float32) if fp16 else a
+
+
+def act_np(x, act):
+    """The eight activations of the reference (src/neural/activation.h:36-81), float64."""
+    if act == 0:
+        return x
+    if act == 1:
+        return np.maximum(x, 0)
+    if act == 2:  # ELU
+        return np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
+    if act == 3:  # SELU
+        return np.where(x > 0, 1.05070098 * x, 1.05070098 * 1.67326324 * np.expm1(np.minimum(x, 0)))
+    if act == 4:  # GELU, tanh form
+        return 0.5 * x * (1 + np.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
+    if act == 5:
+        return x * np.tanh(np.log1p(np.exp(x)))
+    if act == 6:
+        return x / (1 + np.exp(-x))
+    if act == 7:  # HardSwish
+        return np.where(x >= 3, x, np.where(x <= -3, 0.0, x * (x + 3) / 6))
+    raise ValueError(act)
+
+
+def conv_ref(xs, bsz, w, bias, res, k, depthwise, act, post):
+    """xs: list of [C][bs*bs] arrays; returns list of [K][bs*bs] float64."""
+    outs = []
+    pad = k // 2
+    for i, (x, bs) in enumerate(zip(xs, bsz)):
+        C = x.shape[0]
+        img = np.zeros((C, bs + 2 * pad, bs + 2 * pad))
+        img[:, pad:pad + bs, pad:pad + bs] = x.reshape(C, bs, bs)
+        K = w.shape[0]
+        y = np.zeros((K, bs, bs))
+        for kr in range(k):
+            for kc in range(k):
+                patch = img[:, kr:kr + bs, kc:kc + bs]
+                if depthwise:
+                    y += patch * w[:, 0, kr, kc][:, None, None]
+                else:
+                    y += np.einsum("kc,cyx->kyx", w[:, :, kr, kc].astype(np.float64), patch)
+        y = y.reshape(K, bs * bs)
+        if bias is not None:
+            y = y + bias[:, None]
+        if post:
+            y = act_np(y, act)
+            if res is not None:
+                y = y + res[i]
+        else:
+            if res is not None:
+                y = y + res[i]
+            y = act_np(y, act)
+        outs.append(y)
+    return outs
+
+
+def conv3x3_f64(x, w, bias, b):
+    """float64 direct 3x3 convolution of one sample as nine matrix products: x [C][b*b], w [K][C][3][3] -> [K][b*b]"""
+    w64 = np.asarray(w, np.float64)
+    C, K = x.shape[0], w64.shape[0]
+    xp = np.zeros((C, b + 2, b + 2), np.float64)
+    xp[:, 1:-1, 1:-1] = np.asarray(x, np.float64).reshape(C, b, b)
+    y = np.zeros((K, b * b), np.float64)
+    for dy in range(3):
+        for dx in range(3):
+            y += np.matmul(np.ascontiguousarray(w64[:, :, dy, dx]), np.ascontiguousarray(xp[:, dy:dy + b, dx:dx + b]).reshape(C, b * b))
+    return y + np.asarray(bias, np.float64)[:, None]
+
+
+def se_pool_f64(x, bs):
+    """GlobalPooling<false> (se_unit.cc:9-40) of x [C][bs*bs] in float64: (mean, mean * (bs - 14) / 10, max) -> [3C]"""
+    x = np.asarray(x, np.float64)
+    mean = x.sum(axis=1) / float(bs * bs)
+    return np.concatenate([mean, mean * ((bs - 14.0) / 10.0), x.max(axis=1)])
+
+
+def se_gate_f64(pool, w1, b1, w2, b2, act):
+    """squeeze FC with `act`, excite FC: pooled [3C] -> (sigmoid(gamma) [C], beta [C]), float64"""
+    mid = act_np(np.asarray(w1, np.float64) @ pool + np.asarray(b1, np.float64), act)
+    exc = np.asarray(w2, np.float64) @ mid + np.asarray(b2, np.float64)
+    C = exc.shape[0] // 2
+    return 1.0 / (1.0 + np.exp(-exc[:C])), exc[C:]
+
+
+def se_apply_f64(x, res, gamma, beta, act):
+    v = gamma[:, None] * np.asarray(x, np.float64) + beta[:, None]
+    if res is not None:
+        v = v + np.asarray(res, np.float64)
+    return act_np(v, act)
+
+
+def se_unit_f64(x, res, w1, b1, w2, b2, bs, act):
+    """SEUnit::Forward (se_unit.cc:70-128) on x [C][bs*bs] in float64 throughout: pool = (mean, mean * (bs-14)/10, max),
+    squeeze FC with `act`, excite FC, act(sigmoid(gamma) * x + beta + res).  w1 [se][3C], w2 [2C][se]; res or None."""
+    gamma, beta = se_gate_f64(se_pool_f64(x, bs), w1, b1, w2, b2, act)
+    return se_apply_f64(x, res, gamma, beta, act)
+
+
+# ---- the heads: float64 restatement of so_tap_head_tail (oracle/sayuri_oracle.c; reference blas_forward_pipe.cc:496-580), in
+# pieces a test can replace.  weights12 as the head taps of include/sayuri_hip.h take them.
+def head_pool_f64(x, bs, value_head):
+    """GlobalPooling<false/true> (se_unit.cc:9-68) of x [C][bs*bs]: (mean, mean * (bs-14)/10, max | mean * ((bs-14)^2/100 - 0.1))"""
+    x = np.asarray(x, np.float64)
+    mean = x.sum(axis=1) / float(bs * bs)
+    d = bs - 14.0
+    return np.concatenate([mean, mean * (d / 10.0), mean * (d * d / 100.0 - 0.1) if value_head else x.max(axis=1)])
+
+
+def head_inter_f64(pool, w, b, act):
+    return act_np(np.asarray(w, np.float64) @ pool + np.asarray(b, np.float64), act)
+
+
+def head_pixel_f64(planes, w, b):
+    """a 1x1 convolution with bias over planes [C][S]: w [K][C] -> [K][S]"""
+    return np.asarray(w, np.float64) @ planes + np.asarray(b, np.float64)[:, None]
+
+
+def head_tail_f64(pc, vc, ws, bs, act, ppool=None, vpool=None, spatial_bias=True):
+    """-> (prob [prob_ch][S], pass, own [S], misc) from the activated head planes pc [Cp][S], vc [Cv][S].  ppool / vpool: a
+    pooled vector to use in place of the sample's own; spatial_bias=False leaves p_inter's output off the policy planes."""
+    p_inter_w, p_inter_b, pass_w, pass_b, v_inter_w, v_inter_b, v_misc_w, v_misc_b, prob_w, prob_b, own_w, own_b = ws
+    pc, vc = np.asarray(pc, np.float64), np.asarray(vc, np.float64)
+    pinter = head_inter_f64(head_pool_f64(pc, bs, False) if ppool is None else ppool, p_inter_w, p_inter_b, act)
+    prob = head_pixel_f64(pc + pinter[:, None] if spatial_bias else pc, prob_w, prob_b)
+    pas = head_inter_f64(pinter, pass_w, pass_b, 0)
+    vinter = head_inter_f64(head_pool_f64(vc, bs, True) if vpool is None else vpool, v_inter_w, v_inter_b, act)
+    own = head_pixel_f64(vc, np.asarray(own_w, np.float64).reshape(1, -1), own_b)[0]
+    misc = head_inter_f64(vinter, v_misc_w, v_misc_b, 0)
+    return prob, pas, own, misc
+
+
+def head_ratio(a, b, ref, tol):
+    """largest |a - b| over the four outputs, each in units of its own tolerance tol * max(1, |ref|max)"""
+    return max(float(np.abs(np.asarray(x) - y).max()) / (tol * max(1.0, float(np.abs(r).max()))) for x, y, r in zip(a, b, ref))
+
+
+# ---- exact arithmetic (test_gpu_exact.py states the principle)
+def quantum_bits(*arrays):
+    """the smallest q with every value of `arrays` a multiple of 2^-q (0: integers)"""
+    for q in range(25):
+        if all(a is None or np.array_equal(np.rint(np.asarray(a, np.float64) * 2.0 ** q), np.asarray(a, np.float64) * 2.0 ** q) for a in arrays):
+            return q
+    raise AssertionError("an operand is no multiple of 2^-24")
+
+
+def exact_conv(x, w, bs, k, depthwise):
+    """The k x k convolution of one sample as k*k matrix products in float64, which holds these sums exactly: x [C][bs*bs], w
+    [K][C | 1][k][k] -> (sum w x, sum |w x|), each [K][bs*bs]"""
+    x, w64 = np.asarray(x, np.float64), np.asarray(w, np.float64)
+    C, K, pad = x.shape[0], w64.shape[0], k // 2
+    xp = np.zeros((C, bs + 2 * pad, bs + 2 * pad), np.float64)
+    xp[:, pad:pad + bs, pad:pad + bs] = x.reshape(C, bs, bs)
+    wa = np.abs(w64)
+    S, A = np.zeros((K, bs * bs), np.float64), np.zeros((K, bs * bs), np.float64)
+    for dy in range(k):
+        for dx in range(k):
+            patch = np.ascontiguousarray(xp[:, dy:dy + bs, dx:dx + bs]).reshape(C, bs * bs)
+            if depthwise:
+                S += w64[:, 0, dy, dx][:, None] * patch
+                A += wa[:, 0, dy, dx][:, None] * np.abs(patch)
+            else:
+                S += np.matmul(np.ascontiguousarray(w64[:, :, dy, dx]), patch)
+                A += np.matmul(np.ascontiguousarray(wa[:, :, dy, dx]), np.abs(patch))
+    return S, A
+
+
+def exact_layer(x, w, bias, res, bs, k, depthwise, act, post=False, beta=None, store=np.float16, conv=None):
+    """The one correct output of a layer on operands of the exact regime: x [C][bs*bs], w, bias [K] or None, res [K][bs*bs] or None
+    -> float16(act(conv + bias + beta + res)) as float32, [K][bs*bs]; post: act(conv + bias) + res (the depthwise kernel's order);
+    beta: a second per-channel addend (an SE unit's); store=np.float32: the fp32 kernels' store; store=None: the exact value
+    before the store, float64; conv: exact_conv(x, w, bs, k, depthwise) where the caller has it already.  Asserts the regime: act
+    is the identity or ReLU, w / bias / beta are integers, A * 2^q < 2^24, |S| < 65504."""
+    assert act in (0, 1), "only the identity and ReLU are exact functions"
+    assert quantum_bits(w, bias, beta) == 0, "weights and biases are integers"
+    q = quantum_bits(x, res)
+    S, A = exact_conv(x, w, bs, k, depthwise) if conv is None else conv
+    for addend in (bias, beta):
+        if addend is not None:
+            S = S + np.asarray(addend, np.float64)[:, None]
+            A = A + np.abs(np.asarray(addend, np.float64))[:, None]
+    r = np.asarray(res, np.float64) if res is not None else 0.0
+    A = A + np.abs(r)
+    assert float(A.max()) * 2.0 ** q < 2.0 ** 24, ("outside the exact regime: sum |w x| + |bias| + |res| =", float(A.max()), "in units of 2^-%d" % q)
+    v = act_np(S, act) + r if post else act_np(S + r, act)
+    assert max(float(np.abs(S + r).max()), float(np.abs(v).max())) < 65504.0, "an output leaves the fp16 range"
+    return v if store is None else v.astype(store).astype(np.float32)
+
+
+def exact_diff(got, exp):
+    """the predicate of assert_exact: [(sample, channel, pixel, got, exp)] of every value that differs (== on values: -0 equals +0)"""
+    bad = []
+    for i, (g, e) in enumerate(zip(got, exp)):
+        for c, p in zip(*np.nonzero(np.asarray(g) != np.asarray(e))):
+            bad.append((i, int(c), int(p), float(g[c, p]), float(e[c, p])))
+    return bad
+
+
+def assert_exact(got, exp, what):
+    """every sample's output finite and equal to the reference, value for value"""
+    assert len(got) == len(exp), what
+    for i, g in enumerate(got):
+        assert g.shape == exp[i].shape and np.isfinite(g).all(), (what, "sample", i, "an output nobody wrote, or a non-finite one")
+    bad = exact_diff(got, exp)
+    assert not bad, (what, len(bad), "values differ; the first (sample, channel, pixel, got, exp):", bad[:8])
+
+
+def mutated(w, k, c, kr, kc):
+    """w with the one entry changed by 1 (still a small integer)"""
+    w2 = w.copy()
+    w2[k, c, kr, kc] += 1.0
+    return w2
+
+
+def predicted_change(xs, bsz, cout, k, c, kr, kc):
+    """what adding 1 to w[k][c][kr][kc] adds to every sample's 3x3 convolution: channel k only, the input channel c shifted by the tap"""
+    out = []
+    for x, b in zip(xs, bsz):
+        xp = np.zeros((b + 2, b + 2), np.float64)
+        xp[1:-1, 1:-1] = np.asarray(x[c], np.float64).reshape(b, b)
+        d = np.zeros((cout, b * b), np.float64)
+        d[k] = xp[kr:kr + b, kc:kc + b].ravel()
+        out.append(d)
+    return out
+
+
+def assert_localised(got, exp, delta, what):
+    """the real kernel on the changed weight against the UNCHANGED reference: it differs exactly where, and by what, the integer
+    arithmetic says"""
+    n_pred = sum(int(np.count_nonzero(d)) for d in delta)
+    assert n_pred > 0, (what, "the changed weight meets no non-zero input")
+    for i, (g, e, d) in enumerate(zip(got, exp, delta)):
+        assert np.isfinite(g).all(), (what, "sample", i)
+        wrong = np.nonzero((g != e) != (d != 0))
+        assert wrong[0].size == 0, (what, "sample", i, wrong[0].size, "outputs differ where none was predicted, or do not where one was; the first (channel, pixel):",
+                                    list(zip(*wrong))[:8])
+        assert np.array_equal(g.astype(np.float64) - e, d), (what, "sample", i, "an output moved by another amount than the input under the tap")
+    return n_pred

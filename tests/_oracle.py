@@ -51,6 +51,12 @@ class PortNet:
             lib.so_forward_raw.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.POINTER(ctypes.c_float)] * 5
             lib.so_postprocess.argtypes = [ctypes.c_int, ctypes.c_float,
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+            # the layer taps
+            FP = ctypes.POINTER(ctypes.c_float)
+            lib.so_tap_se_unit.argtypes = [ctypes.c_int] * 3 + [FP] * 6 + [ctypes.c_int]
+            lib.so_tap_global_pool.argtypes = [ctypes.c_int, ctypes.c_int, FP, FP, ctypes.c_int]
+            lib.so_tap_fully_connect.argtypes = [ctypes.c_int, ctypes.c_int, FP, FP, FP, FP, ctypes.c_int]
+            lib.so_tap_head_tail.argtypes = [ctypes.c_int] * 7 + [FP] * 18
             cls._lib = lib
         return cls._lib
 

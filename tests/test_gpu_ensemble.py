@@ -14,11 +14,11 @@ import pytest
 
 from _ensemble import GAME_OF_SIZE, GOLDEN_GAMES, golden_game_at, permute_record
 from _golden import Golden
+from _pipes import make_pipe
 from sayuri_amd import _lib, hipraw
 from sayuri_amd import search as S
 from sayuri_amd.engine import pack_planes
 from sayuri_amd.pipe import HipForwardPipe, hip_forward_packed_raw, hip_forward_packed_symm_raw
-from test_gpu_latency import make_pipe
 
 pytestmark = pytest.mark.gpu
 

@@ -25,58 +25,16 @@ import numpy as np
 import pytest
 
 from _golden import Golden
-from sayuri_amd import _lib, hipraw
-from sayuri_amd import weights as W
-from sayuri_amd.engine import pack_planes
-from sayuri_amd.pipe import HipForwardPipe, hip_forward_packed_raw, hip_forward_raw
+from _pipes import B, Pinned, Pool, make_pipe, wrong_samples
+from sayuri_amd import _lib
+from sayuri_amd.pipe import hip_forward_packed_raw, hip_forward_raw
 
 pytestmark = pytest.mark.gpu
-
-B = 19
-MAXB = 640
-WORDS = 37 * 12 + 8
-MAIN_SIZES, ODD_SIZES = (9, 13, 19), (2, 3, 5, 7, 11, 14, 16, 17)
-SWITCHES = ("SAYURI_TOWER", "SAYURI_CHAINS", "SAYURI_DEBUG_RECYCLE_INPUT")
-
-
-class Pool:
-    """Positions of the fuzz: planes on the NN grid, packed records, board sizes -- 40 per main size, 6 per odd size."""
-
-    def __init__(self, seed=606):
-        sizes = [s for s in MAIN_SIZES for _ in range(40)] + [s for s in ODD_SIZES for _ in range(6)]
-        planes = W.synthetic_planes(len(sizes), sizes, seed=seed)
-        self.bsz = np.asarray(sizes, np.int32)
-        self.grid = np.zeros((len(sizes), 43, B * B), np.float32)
-        for i, (p, bs) in enumerate(zip(planes, sizes)):
-            self.grid[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-        self.rec = np.stack([pack_planes(p, 37) for p in planes]).astype(np.uint32)
-        self.by_size = {s: np.flatnonzero(self.bsz == s) for s in set(sizes)}
-
-    def draw(self, rng, n, mix):
-        if mix == "uniform19":
-            return rng.choice(self.by_size[19], size=n)
-        if mix == "mixed":
-            return np.asarray([rng.choice(self.by_size[int(s)]) for s in rng.choice(MAIN_SIZES, size=n)])
-        return rng.integers(0, len(self.bsz), size=n)  # "wild": anything from 2x2 to 19x19
-
-
-def make_pipe(path, env, fp16=True):
-    keep = {k: os.environ.get(k) for k in SWITCHES}
-    for k in SWITCHES:
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    try:
-        return HipForwardPipe(path, board_size=B, batch_size=MAXB, fp16=fp16)  # the switches are read at creation
-    finally:
-        for k, v in keep.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
 
 
 def reference_bits(path, pool, fp16=True):
     """prob / pass / misc / own of every pool position from the per-layer, one-chain, one-stream engine."""
-    pipe = make_pipe(path, {"SAYURI_TOWER": "0", "SAYURI_CHAINS": "1"}, fp16)
+    pipe = make_pipe(path, {"SAYURI_TOWER": "0", "SAYURI_CHAINS": "1"}, fp16=fp16)
     try:
         ctx = pipe.ctx(0)
         assert _lib.hip().sayuri_hip_tower_state(ctx) == 0
@@ -95,39 +53,6 @@ def reference_bits(path, pool, fp16=True):
         return ref
     finally:
         pipe.Destroy()
-
-
-class Pinned:
-    """Two sets of page-locked staging buffers for submit / wait (what the pump owns), filled from a Pool."""
-
-    def __init__(self):
-        self.sets = [hipraw.PinnedSet(MAXB, B, 43 * B * B) for _ in range(2)]
-
-    def close(self):
-        for s in self.sets:
-            s.close()
-
-    def submit(self, ctx, i, pool, idx, packed):
-        s, n = self.sets[i], len(idx)
-        s.bsz[:n] = pool.bsz[idx]
-        if packed:
-            s.records[:n * WORDS] = pool.rec[idx].ravel()
-            return hipraw.submit_packed(ctx, s, n, 37)
-        s.planes[:n * 43 * B * B] = pool.grid[idx].ravel()
-        return hipraw.submit(ctx, s, n)
-
-    def wait(self, ctx, i, tick, n):
-        hipraw.wait(ctx, tick)
-        return tuple(a.copy() for a in self.sets[i].outputs(n))
-
-
-def wrong_samples(ref, got, idx):
-    """Samples of a batch whose bits differ from their position's reference bits (any of the four outputs)."""
-    bad = np.zeros(len(idx), bool)
-    for a, b in zip(ref, got):
-        a = a[idx]
-        bad |= (a.reshape(len(idx), -1).view(np.uint32) != b.reshape(len(idx), -1).view(np.uint32)).any(axis=1)
-    return np.flatnonzero(bad)
 
 
 class Hammer:
@@ -187,7 +112,7 @@ def run_fuzz(nets, scenarios, seed, env_extra=None, stop_at_first=False, tmp_wei
             env = dict(env_extra)
             if chains == "1":
                 env["SAYURI_CHAINS"] = "1"
-            pipes[key] = make_pipe(paths[name], env, fp16)
+            pipes[key] = make_pipe(paths[name], env, fp16=fp16)
         return pipes[key]
 
     hammers = {}
@@ -208,7 +133,7 @@ def run_fuzz(nets, scenarios, seed, env_extra=None, stop_at_first=False, tmp_wei
                     other = name
                 sc["hammer_net"] = other
                 if other not in hammers:
-                    hammers[other] = Hammer(make_pipe(paths[other], dict(env_extra), fp16), pool)
+                    hammers[other] = Hammer(make_pipe(paths[other], dict(env_extra), fp16=fp16), pool)
                 ham = hammers[other]
                 ham.start()
             try:

@@ -3,47 +3,34 @@ tower convolution cut into many small workgroups, for the batches of 1 to 16 pos
 
 The split kernel accumulates in the board kernel's K order (32-channel chunk, kernel row, tap; bias first) and shares its
 epilogue arithmetic, so the checks are on BITS, against code that existed before the feature:
-  layer level  sayuri_hip_test_conv_split == sayuri_hip_test_conv (board kernel, kind 2), for every forced split
+  layer level  the conv_split tap == the conv tap (board kernel, kind 2), for every forced split
   whole net    a latency context == a default context created under SAYURI_SE_FUSED=0 SAYURI_SE_SPLIT=0 SAYURI_TOWER=0
-The tolerance checks (float64 direct convolution, the goldens) reuse the helpers and bounds of test_gpu_layers.py / test_gpu_net.py.
+The tolerance checks (float64 direct convolution, the goldens) reuse conv_ref of _kref.py, check / fp16_tol of _pipes.py and the bounds
+of test_gpu_layers.py / test_gpu_net.py.
 """
 import ctypes
-import os
+import functools
 
 import numpy as np
 import pytest
 
-import test_gpu_fuzz as FZ
+import _pipes
+import _taps
+from _cases import LAYER_SHAPES
 from _golden import Golden
+from _kref import conv_ref
+from _pipes import MAXB, Pinned, Pool, check, fp16_tol, wrong_samples
+from _taps import KIND_BOARD, KIND_SPLIT
 from golden_specs import FIXTURES
 from sayuri_amd import _lib
 from sayuri_amd import weights as W
-from sayuri_amd.pipe import HipForwardPipe, hip_forward_packed_raw, hip_forward_raw
-from test_gpu_layers import KIND_BOARD, conv_ref
-from test_gpu_net import check, fp16_tol
+from sayuri_amd.pipe import hip_forward_packed_raw, hip_forward_raw
 
 pytestmark = pytest.mark.gpu
 
 B = 19
-KIND_SPLIT = 4
 SEPARATE = {"SAYURI_SE_FUSED": "0", "SAYURI_SE_SPLIT": "0", "SAYURI_TOWER": "0"}
-SWITCHES = tuple(SEPARATE) + ("SAYURI_LATENCY", "SAYURI_LATENCY_SPLIT", "SAYURI_CHAINS", "SAYURI_CONV")
-
-
-def make_pipe(path, env=None, latency=False, batch=64, fp16=True):
-    """A pipe created under exactly `env` of the engine's switches (they are read once, at creation)."""
-    keep = {k: os.environ.get(k) for k in SWITCHES}
-    for k in SWITCHES:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    try:
-        return HipForwardPipe(path, board_size=B, batch_size=batch, fp16=fp16, latency=latency)
-    finally:
-        for k, v in keep.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
+make_pipe = functools.partial(_pipes.make_pipe, batch=64)  # the batch of this module's pipes where a test names none
 
 
 def grid_of(planes, bsz):
@@ -54,17 +41,6 @@ def grid_of(planes, bsz):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. layer level
-LAYER_SHAPES = [
-    # bsz, cin, cout
-    ([19], 256, 256),
-    ([19, 19, 19], 128, 128),
-    ([19, 13], 384, 384),
-    ([9], 256, 256),
-    ([13], 128, 384),
-    ([19, 19, 13, 13, 9, 9, 9, 9, 19, 13], 256, 256),   # mixed sizes: boards that share a board tile are cut per sample
-    ([13, 9, 9, 19, 13, 9], 43, 128),                   # an input convolution (cin padded to 64: two chunks)
-    ([9] * 9, 128, 256),
-]
 VARIANTS = [  # act, with residual
     (5, True), (5, False), (1, True), (0, False), (0, True), (1, False),
 ]
@@ -84,68 +60,40 @@ def test_split_convolution_has_the_board_kernels_bits(case):
     """Every forced split (1, 2, 4 strips, one strip per row, the engine's choice) of every epilogue variant gives the fp16
     outputs of the one-workgroup-per-board kernel, and those are within test_gpu_layers.py's bound of the float64 convolution."""
     bsz, cin, cout = case
-    lib = _lib.hip()
-    n = len(bsz)
-    bs_arr = np.asarray(bsz, np.int32)
     for k, (act, with_res) in enumerate(VARIANTS):
         xs, w, bias, res = _layer_tensors(bsz, cin, cout, with_res, seed=cin + cout + 7 * k)
-        xcat = np.concatenate([x.ravel() for x in xs])
-        rcat = np.concatenate([r.ravel() for r in res]) if res else None
-        board = np.zeros(sum(cout * b * b for b in bsz), np.float32)
-        rc = lib.sayuri_hip_test_conv(0, 1, n, bs_arr.ctypes.data_as(_lib.c_int_p), B, cin, cout, 3, 0, act, 0, _lib.fp(xcat), _lib.fp(w.ravel()),
-                                      _lib.fp(bias), _lib.fp(rcat) if res else None, _lib.fp(board))
-        assert rc == 0, lib.sayuri_hip_last_error().decode()
-        assert lib.sayuri_hip_test_last_conv_kind() == KIND_BOARD, "the yardstick is the board kernel"
+        board = _taps.ok(_taps.conv(True, bsz, cin, cout, 3, act, xs, w, bias, res))
+        assert board.kind == KIND_BOARD, "the yardstick is the board kernel"
         for strips in (1, 2, 4, max(bsz), 0):
-            y = np.full_like(board, np.nan)
-            rc = lib.sayuri_hip_test_conv_split(0, n, bs_arr.ctypes.data_as(_lib.c_int_p), B, cin, cout, act, _lib.fp(xcat), _lib.fp(w.ravel()),
-                                                _lib.fp(bias), _lib.fp(rcat) if res else None, _lib.fp(y), 0, strips)
-            assert rc == 0, lib.sayuri_hip_last_error().decode()
-            assert lib.sayuri_hip_test_last_conv_kind() == KIND_SPLIT
-            assert np.array_equal(y, board), (case, act, with_res, strips, float(np.nanmax(np.abs(y - board))))
+            t = _taps.ok(_taps.conv_split(bsz, cin, cout, act, xs, w, bias, res, strips))
+            assert t.kind == KIND_SPLIT
+            for y, yb in zip(t.outs, board.outs):
+                assert np.array_equal(y, yb), (case, act, with_res, strips, float(np.nanmax(np.abs(y - yb))))
         # ... and the float64 direct convolution on the fp16-rounded operands, with test_gpu_layers.py's fp16 tolerance
         ref = conv_ref([x.astype(np.float16).astype(np.float64) for x in xs], bsz, w.astype(np.float16).astype(np.float64),
                        bias.astype(np.float64), [r.astype(np.float16).astype(np.float64) for r in res] if res else None, 3, False, act, False)
         scale = max(float(np.abs(r).max()) for r in ref)
-        off = 0
-        for i, b in enumerate(bsz):
-            got = board[off:off + cout * b * b].reshape(cout, b * b)
-            off += cout * b * b
-            assert float(np.abs(got - ref[i]).max()) <= 4e-3 * scale
+        for got, exp in zip(board.outs, ref):
+            assert float(np.abs(got - exp).max()) <= 4e-3 * scale
 
 
 def test_split_convolution_every_activation_and_post_residual_layer():
     """All eight activations with the residual added in front of them (the tower's post-residual layers), one strip per two rows."""
-    lib = _lib.hip()
     bsz = [19, 13]
-    bs_arr = np.asarray(bsz, np.int32)
     for act in range(8):
         xs, w, bias, res = _layer_tensors(bsz, 64, 128, True, seed=300 + act)
-        xcat, rcat = np.concatenate([x.ravel() for x in xs]), np.concatenate([r.ravel() for r in res])
-        out = []
-        for split in (None, 10):
-            y = np.zeros(sum(128 * b * b for b in bsz), np.float32)
-            if split is None:
-                rc = lib.sayuri_hip_test_conv(0, 1, 2, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, 3, 0, act, 0, _lib.fp(xcat), _lib.fp(w.ravel()),
-                                              _lib.fp(bias), _lib.fp(rcat), _lib.fp(y))
-                assert rc == 0 and lib.sayuri_hip_test_last_conv_kind() == KIND_BOARD
-            else:
-                rc = lib.sayuri_hip_test_conv_split(0, 2, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, act, _lib.fp(xcat), _lib.fp(w.ravel()),
-                                                    _lib.fp(bias), _lib.fp(rcat), _lib.fp(y), 2, split)
-                assert rc == 0, lib.sayuri_hip_last_error().decode()
-            out.append(y)
-        assert np.array_equal(out[0], out[1]), act
+        board = _taps.ok(_taps.conv(True, bsz, 64, 128, 3, act, xs, w, bias, res))
+        assert board.kind == KIND_BOARD
+        t = _taps.ok(_taps.conv_split(bsz, 64, 128, act, xs, w, bias, res, strips=10, channel_tiles=2))
+        for y, yb in zip(t.outs, board.outs):
+            assert np.array_equal(y, yb), act
 
 
 def test_split_tap_refuses_what_the_kernel_does_not_cover():
-    lib = _lib.hip()
-    bs_arr = np.asarray([19], np.int32)
-    x, w, y = np.zeros(96 * 361, np.float32), np.zeros(96 * 96 * 9, np.float32), np.zeros(96 * 361, np.float32)
-    rc = lib.sayuri_hip_test_conv_split(0, 1, bs_arr.ctypes.data_as(_lib.c_int_p), B, 96, 96, 0, _lib.fp(x), _lib.fp(w), None, None, _lib.fp(y), 0, 0)
-    assert rc == -1 and b"64-channel" in lib.sayuri_hip_last_error()   # 96 weight rows: the layer keeps the default route
-    x, w, y = np.zeros(64 * 361, np.float32), np.zeros(128 * 64 * 9, np.float32), np.zeros(128 * 361, np.float32)
-    rc = lib.sayuri_hip_test_conv_split(0, 1, bs_arr.ctypes.data_as(_lib.c_int_p), B, 64, 128, 0, _lib.fp(x), _lib.fp(w), None, None, _lib.fp(y), 3, 0)
-    assert rc == -1 and b"channel tiles" in lib.sayuri_hip_last_error()
+    x, w = [np.zeros((96, 361), np.float32)], np.zeros(96 * 96 * 9, np.float32)
+    assert _taps.conv_split([19], 96, 96, 0, x, w, None).rc == -1 and "64-channel" in _taps.last_error()   # 96 weight rows: the layer keeps the default route
+    x, w = [np.zeros((64, 361), np.float32)], np.zeros(128 * 64 * 9, np.float32)
+    assert _taps.conv_split([19], 64, 128, 0, x, w, None, channel_tiles=3).rc == -1 and "channel tiles" in _taps.last_error()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. whole net
@@ -231,10 +179,10 @@ def test_a_position_does_not_depend_on_its_batch_mates_in_latency_mode(name, tmp
 def test_packed_planes_and_two_tickets_in_latency_mode(tmp_weights_dir):
     """submit_packed gives the submit bits, and two tickets in flight (different batches, six rounds) give the solo bits."""
     g = Golden("net_20b256", tmp_weights_dir)
-    pool = FZ.Pool()
+    pool = Pool()
     rng = np.random.default_rng(11)
-    pipe = make_pipe(g.weights_path, latency=True, batch=FZ.MAXB)
-    pinned = FZ.Pinned()
+    pipe = make_pipe(g.weights_path, latency=True, batch=MAXB)
+    pinned = Pinned()
     try:
         ctx = pipe.ctx(0)
         idxs = [pool.draw(rng, 3, "mixed"), pool.draw(rng, 11, "wild")]
@@ -322,12 +270,12 @@ def test_latency_bit_identity_fuzz(tmp_weights_dir, capsys):
     """20 scenarios drawn the way test_gpu_fuzz.py draws them -- network, 1..64 positions, uniform / mixed / wild sizes, one or two
     tickets in flight, packed or fp32 planes -- in a latency context, every sample against the bits of its position in the
     separate-SE default context."""
-    pool = FZ.Pool()
+    pool = Pool()
     rng = np.random.default_rng(20261016)
     nets = ["net_20b256", "net_40b384", "net_6b96"]
     paths = {n: Golden(n, tmp_weights_dir).weights_path for n in nets}
     refs, pipes = {}, {}
-    pinned = FZ.Pinned()
+    pinned = Pinned()
     failures, ran = [], []
     try:
         for k in range(20):
@@ -335,13 +283,13 @@ def test_latency_bit_identity_fuzz(tmp_weights_dir, capsys):
             sc = dict(k=k, net=name, n=int(rng.integers(1, 65)), mix=str(rng.choice(["uniform19", "mixed", "mixed", "wild"])),
                       tickets=int(rng.integers(1, 3)), packed=bool(rng.integers(0, 2)))
             if name not in refs:
-                ref = make_pipe(paths[name], SEPARATE, batch=FZ.MAXB)
+                ref = make_pipe(paths[name], SEPARATE, batch=MAXB)
                 try:
                     outs = [hip_forward_raw(ref.ctx(0), pool.grid[lo:lo + 96], pool.bsz[lo:lo + 96], B) for lo in range(0, len(pool.bsz), 96)]
                 finally:
                     ref.Destroy()
                 refs[name] = tuple(np.concatenate([o[j] for o in outs]) for j in range(4))
-                pipes[name] = make_pipe(paths[name], latency=True, batch=FZ.MAXB)
+                pipes[name] = make_pipe(paths[name], latency=True, batch=MAXB)
             ctx = pipes[name].ctx(0)
             batches = []
             if sc["tickets"] == 1:
@@ -362,7 +310,7 @@ def test_latency_bit_identity_fuzz(tmp_weights_dir, capsys):
                         tick[i] = pinned.submit(ctx, i, pool, idxs[i], sc["packed"])
             ran.append(sc)
             for idx, got in batches:
-                bad = FZ.wrong_samples(refs[name], got, idx)
+                bad = wrong_samples(refs[name], got, idx)
                 if len(bad):
                     failures.append((dict(sc), bad.tolist()[:16], len(idx), len(bad)))
     finally:

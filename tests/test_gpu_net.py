@@ -15,6 +15,7 @@ import pytest
 
 from _golden import Golden
 from _oracle import PortNet
+from _pipes import FP16_ATOL, check, fp16_tol, self_check_l2
 from golden_specs import FIXTURES
 from sayuri_amd import weights as W
 from sayuri_amd.pipe import HipForwardPipe
@@ -22,34 +23,6 @@ from sayuri_amd.pipe import HipForwardPipe
 pytestmark = pytest.mark.gpu
 
 FP32_ATOL = 1e-4
-FP16_ATOL = 4e-3  # times max(1, output scale): fp16_tol()
-
-
-def fp16_tol(exp):
-    return FP16_ATOL * max(1.0, float(np.abs(exp).max()))
-
-
-def self_check_l2(got, exp, bs):
-    """reference Network::SelfCheck (network.cc:333-359) on post-processed outputs."""
-    a, b = PortNet.postprocess(got, bs), PortNet.postprocess(exp, bs)
-    s = bs * bs
-    va = np.concatenate([a[:s + 1], [a[2 * s + 1 + 3]]])
-    vb = np.concatenate([b[:s + 1], [b[2 * s + 1 + 3]]])
-    return float(np.sqrt(((va - vb) ** 2).sum()))
-
-
-def check(pipe, cases, atol, label):
-    planes = [c[0] for c in cases]
-    bsz = [c[1] for c in cases]
-    offs = [c[2] for c in cases]
-    for mode, outs in (("batch", pipe.BatchForward(planes, bsz, offsets=offs)),
-                       ("queue", pipe.Forward(planes, bsz, offsets=offs))):
-        for (p, bs, off, exp), got in zip(cases, outs):
-            assert got.shape == exp.shape
-            assert np.isfinite(got).all(), (label, mode)
-            err = float(np.abs(got - exp).max())
-            assert err <= (atol(exp) if callable(atol) else atol), (label, mode, bs, off, err)
-            assert self_check_l2(got, exp, bs) <= 0.2
 
 
 @pytest.mark.parametrize("fp16", [False, True], ids=["fp32", "fp16"])

@@ -65,6 +65,18 @@ def test_signatures_are_assigned_in_one_place():
     assert not found, found
 
 
+def test_every_layer_tap_has_its_one_caller_in_taps():
+    """tests/_taps.py names every layer tap of HIP_ABI, and no other file under tests/ names one."""
+    taps = {name for name in _lib.HIP_ABI if "_test_" in name}
+    pat = re.compile(os.path.commonprefix(sorted(taps)).encode() + rb"\w+")
+    named = {}
+    for path in glob.glob(os.path.join(ROOT, "tests", "**", "*"), recursive=True):
+        if os.path.isfile(path) and "__pycache__" not in path:
+            named[os.path.relpath(path, ROOT)] = {m.decode() for m in pat.findall(open(path, "rb").read())}
+    assert taps and named.pop(os.path.join("tests", "_taps.py")) == taps
+    assert not any(named.values()), {k: v for k, v in named.items() if v}
+
+
 DRIVER = textwrap.dedent(r"""
     import os, sys
     import numpy as np

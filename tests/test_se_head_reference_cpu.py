@@ -16,25 +16,21 @@ se_pool / se_fc / se_scale, head_tail_kernel, head_board_kernel), checked withou
 3. An emulation of the staged kernel's rounding -- the folded squeeze image W_mean + (bs-14)/10 W_scaled, the excite image and the
    output in fp16, everything else float64 -- stays within half the GPU tolerance of the reference on every case, so a correct
    kernel keeps as much again for its accumulation order."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from _oracle import PortNet
 from sayuri_amd._lib import fp
-from test_gpu_smallops import (HEAD_BOARDS, HEAD_DIMS, HEAD_PAIRS, HEAD_SEED, SE_CASE_IDS, SE_CASES, SE_LAYERS, SE_SEED, SE_UNIT_BATCHES, SX_TOL,
-                               head_inputs, head_pool_f64, head_ratio, head_tail_f64, se_apply_f64, se_case_batches, se_gate_f64, se_inputs,
-                               se_pool_f64, se_unit_x)
+from _cases import (HEAD_BOARDS, HEAD_DIMS, head_inputs, HEAD_PAIRS, HEAD_SEED, se_case_batches, SE_CASE_IDS, SE_CASES, se_inputs, SE_LAYERS, SE_SEED,
+                    SE_UNIT_BATCHES, se_unit_x, SX_TOL)
+from _kref import head_pool_f64, head_ratio, head_tail_f64, se_apply_f64, se_gate_f64, se_pool_f64
 
-FP = ctypes.POINTER(ctypes.c_float)
 BAR = 4.0
 
 
 @pytest.mark.parametrize("act", range(8))
 def test_head_tail_f64_matches_the_oracle(act):
     o = PortNet.lib()
-    o.so_tap_head_tail.argtypes = [ctypes.c_int] * 7 + [FP] * 18
     d = HEAD_DIMS
     for draw in ("spread", "probe"):
         for Cp, Cv in ((32, 32), (24, 48)):

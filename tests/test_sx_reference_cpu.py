@@ -6,22 +6,18 @@
 2. The inputs of those tests make them sensitive: on the very generator they use (sx_trunk / sx_fc), the ways
    conv_board_sx_kernel could be subtly wrong each move the result by at least 4x the GPU tolerance
    (3e-3 * max(1, |ref|max)) -- on every sample the defect touches, not just somewhere."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from _oracle import PortNet
 from sayuri_amd._lib import fp
-from test_gpu_smallops import (SX_TOL, se_apply_f64, se_gate_f64, se_pool_f64, se_unit_f64, sx_fc, sx_reference, sx_trunk)
-
-FP = ctypes.POINTER(ctypes.c_float)
+from _cases import SX_TOL, sx_fc, sx_reference, sx_trunk
+from _kref import se_apply_f64, se_gate_f64, se_pool_f64, se_unit_f64
 
 
 @pytest.mark.parametrize("act", range(8))
 def test_se_unit_f64_matches_the_oracle(act):
     o = PortNet.lib()
-    o.so_tap_se_unit.argtypes = [ctypes.c_int] * 3 + [FP] * 6 + [ctypes.c_int]
     rng = np.random.default_rng(900 + act)
     for bs in (2, 9, 11, 13, 19):
         for C, se, with_res in ((96, 24, True), (40, 12, False)):

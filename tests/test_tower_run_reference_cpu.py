@@ -1,7 +1,7 @@
 """The yardstick of the run-level tower tests (test_gpu_tower_run.py), checked without a GPU.
 
-1. conv3x3_taps_f64, the float64 convolution as nine matrix products that keeps 256 channels cheap, against conv_ref of
-   test_gpu_layers.py (the float64 restatement of the oracle's direct convolution) on small cases: 1e-12 * scale, both are
+1. conv3x3_f64 of _kref.py, the float64 convolution as nine matrix products that every kernel test uses, against conv_ref of
+   _kref.py (the float64 restatement of the oracle's direct convolution) on small cases: 1e-12 * scale, both are
    float64 sums of the same products in another order.
 2. The can-fail case of the GPU module (the eight-layer run checked against a reference that was given layer 2's and layer 3's
    weights swapped) on the very draw it uses: with every layer's output rounded to fp16 as the kernel stores it, the float64
@@ -10,9 +10,8 @@
 import numpy as np
 import pytest
 
-from test_gpu_layers import conv_ref
-from test_gpu_tower_run import CAN_FAIL_BAR, SWAP, blocks_spec, conv3x3_taps_f64, layer_f64, layer_io, run_draw
-from test_gpu_smallops import r16
+from _cases import CAN_FAIL_BAR, SWAP, blocks_spec, layer_f64, layer_io, run_draw
+from _kref import conv3x3_f64, conv_ref, r16
 
 
 @pytest.mark.parametrize("bs,cin,cout", [(2, 40, 24), (5, 33, 64), (19, 16, 8)])
@@ -22,7 +21,7 @@ def test_conv3x3_taps_f64_matches_conv_ref(bs, cin, cout):
     w = rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(9 * cin)
     bias = rng.standard_normal(cout)
     exp = conv_ref([x], [bs], w, bias, None, 3, False, 0, False)[0]
-    got = conv3x3_taps_f64(x, w, bias, bs)
+    got = conv3x3_f64(x, w, bias, bs)
     assert got.shape == exp.shape
     assert np.abs(got - exp).max() <= 1e-12 * max(1.0, float(np.abs(exp).max()))
 
