@@ -145,6 +145,7 @@ int sayuri_hip_submit(sayuri_hip_ctx* ctx, int n, const float* planes, const int
  *            SAMPLE's own cell order -- no re-padding into the NN grid), then 8 floats (the value of each broadcast
  *            plane: rule, wave, komi/20, -komi/20, N/361, 1 for 43-plane nets)
  *   binary_planes = input_channels - 6 (37) for v3+ nets, 34 for the 38-plane v1/v2 encoder
+ *            A record holds at most 40 bit planes and 8 scalars: any other count returns -1 with a message, nothing is launched.
  * 1.8 KB per sample instead of 62 KB; the first kernel expands the bits into the fp16 activations, the network sees the
  * same values as through sayuri_hip_forward and returns bit-identical outputs. */
 int sayuri_hip_forward_packed(sayuri_hip_ctx* ctx, int n, const unsigned* records, int binary_planes, const int* board_sizes,
@@ -314,6 +315,34 @@ int sayuri_hip_test_head_board(int device, int n, const int* board_sizes, int ma
                                int value_channels, int prob_channels, int pass_outs, int misc_outs, int act, const float* trunk,
                                const float* p_w, const float* p_b, const float* v_w, const float* v_b,
                                const float* const* weights12, float* prob, float* pass, float* misc, float* own);
+
+/* The input stage, the first kernel of every forward: planes or packed records -> the input convolution's NHWC image.  ONE of
+ * pack_input_kernel (chunked), pack_input_flat_kernel, pack_bits_kernel, pack_bits_symm_kernel (csrc/hip/small_ops.h) on host
+ * data, the kernel, its chunk, LDS and workgroups per sample chosen by the engine's own code (pack_plan, engine_plan.h).
+ *   board_sizes [n]  the board of every DEVICE sample; perm [n] the caller's slot each shows, NULL = no table (sample i shows
+ *                    slot i); the launch covers the device samples [n0, n0 + ns) as one chain of a chained forward does
+ *   planes != NULL   fp32 planes [n][cin][max_board^2] on the NN grid, by slot
+ *   else records     [n_records][binary_planes*12 + 8] as sayuri_hip_forward_packed takes them, read by slot (n_records >= n);
+ *                    symm != NULL: read through the record map src [n] (NULL = the identity) under the symmetries symm [n], both by
+ *                    slot, as sayuri_hip_forward_packed_symm takes them
+ *   stage_batch > 0  off | bsz | perm and src | symm travel through geom_stage_kernel / symm_stage_kernel from a pinned ring laid
+ *                    out for stage_batch >= n samples (a mixed batch's path; a missing perm is staged as the identity); 0: copied
+ *   in_place != 0    the records stay in pinned host memory of sayuri_hip_host_alloc's allocator and one workgroup per sample
+ *                    reads them there (sayuri_hip_submit_packed's path)
+ *   image            float [n*max_board^2 + guard_rows][cs], cs = cin rounded up to 32: the whole device image and guard_rows rows
+ *                    behind its last slot, all set to `sentinel` (converted to the engine's type) before the launch, returned
+ *                    as stored: every row of every slot, every pad channel
+ * Refused (-1, the engine's messages) like a forward with max_batch = stage_batch (or n): board sizes outside 2..max_board, a
+ * binary plane count the network or a record cannot have (more than 40 bit planes, more than 8 scalars), a symm outside 0..7, a src
+ * outside the records; and a perm outside the batch or a sample range outside it.
+ * sayuri_hip_test_last_pack: out = {kernel: 0 chunked, 1 flat, 2 bits, 3 bits + symmetry (-1: the call launched nothing), cs,
+ * workgroups per sample, passes: the chunked kernel's passes per workgroup on the largest board of the launch, the flat
+ * kernel's passes over a sample's planes, else 1} of the calling thread's last sayuri_hip_test_pack_input. */
+int sayuri_hip_test_pack_input(int device, int use_fp16, int n, const int* board_sizes, int max_board, int cin, const float* planes,
+                               const unsigned* records, int n_records, int binary_planes, const int* src, const int* symm,
+                               const int* perm, int n0, int ns, int stage_batch, int in_place, float sentinel, int guard_rows,
+                               float* image);
+int sayuri_hip_test_last_pack(int out[4]);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,10 @@ HIP_ABI = {
     "sayuri_hip_test_conv_sx": (_I, [_I] * 2 + [_IP] + [_I] * 4 + [_F] * 9),
     "sayuri_hip_test_last_sx_kts": (_I, []),
     "sayuri_hip_test_head_board": (_I, [_I] * 2 + [_IP] + [_I] * 8 + [_F] * 5 + [_W12] + _OUT),
+    # device, use_fp16, n, board_sizes, max_board, cin, planes, records, n_records, binary, src, symm, perm, n0, ns, stage_batch, in_place,
+    # sentinel, guard_rows, image
+    "sayuri_hip_test_pack_input": (_I, [_I] * 3 + [_IP] + [_I] * 2 + [_F, _V, _I, _I] + [_IP] * 3 + [_I] * 4 + [ctypes.c_float, _I, _F]),
+    "sayuri_hip_test_last_pack": (_I, [_IP]),
 }
 HIP_SYMBOLS = list(HIP_ABI)
 

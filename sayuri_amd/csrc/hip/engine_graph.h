@@ -6,14 +6,6 @@
 
 namespace sayuri {
 
-// A packed batch whose device samples name their record and board symmetry (sayuri_hip_forward_packed_symm): `n_records`
-// records in the caller's array, src[n] (null: sample i reads record i) and symm[n] in the caller's sample order.
-struct SymmReq {
-    int n_records = 0;
-    const int* src = nullptr;
-    const int* symm = nullptr;
-};
-
 class EngineBase {
 public:
     virtual ~EngineBase() {}
@@ -337,23 +329,7 @@ public:
     }
     std::map<int, IdentGeom> ident_;
 
-    // A symmetry request's arguments, checked before anything is enqueued.  The record array is bounded by max_batch: the copy
-    // path moves it into the slot's record buffer, which holds that many.
-    int check_symm(int n, const unsigned* packed, const SymmReq& sy) {
-        if (!packed || !sy.symm) return fail("packed_symm: null argument");
-        if (n <= 0 || n > max_batch_) return fail("batch size out of range");
-        if (sy.n_records <= 0 || sy.n_records > max_batch_)
-            return fail("packed_symm: n_records " + std::to_string(sy.n_records) + " out of range (1.." + std::to_string(max_batch_) + ")");
-        if (!sy.src && n > sy.n_records) return fail("packed_symm: the identity record map needs n <= n_records");
-        for (int i = 0; i < n; ++i) {
-            if (sy.symm[i] < 0 || sy.symm[i] > 7)
-                return fail("packed_symm: symm[" + std::to_string(i) + "] = " + std::to_string(sy.symm[i]) + " is no board symmetry (0..7)");
-            if (sy.src && (sy.src[i] < 0 || sy.src[i] >= sy.n_records))
-                return fail("packed_symm: src[" + std::to_string(i) + "] = " + std::to_string(sy.src[i]) + " is outside the " +
-                            std::to_string(sy.n_records) + " records");
-        }
-        return 0;
-    }
+    int check_symm(int n, const unsigned* packed, const SymmReq& sy) { return check_symm_request(n, max_batch_, packed, sy); }
 
     // geometry + planes of ticket t to the device (no sync): the planes or packed records H2D on `copy_stream`, the geometry
     // arrays of a mixed batch from a 2-deep pinned ring (a second batch can be enqueued while the first is still in flight) on
@@ -362,8 +338,7 @@ public:
                        int binary = 0, bool in_place = false, const SymmReq* sy = nullptr) {
         HIP_OK(hipSetDevice(device_));
         if (n <= 0 || n > max_batch_) return fail("batch size out of range");
-        if (packed && (binary <= 0 || binary > desc_.input_channels || desc_.input_channels - binary > 8 || board_ * board_ > 12 * 32))
-            return fail("packed planes: bad binary plane count for this network");
+        if (packed && packed_binary_check(binary, desc_.input_channels, board_)) return -1;
         if (finalize()) return -1;
         prev_bsz_.swap(geom_.bsz);
         geom_.n = n;
@@ -453,7 +428,7 @@ public:
             HIP_OK(hipGetLastError());
         }
         if (packed) {
-            const size_t words = (size_t)binary * 12 + 8;
+            const size_t words = (size_t)binary * kPackedWords + kPackedScalars;
             const int nrec = sy ? sy->n_records : n;
             // Packed records in device-addressable host memory (sayuri_hip_host_alloc: the pump's buffers) are not copied at all:
             // pack_bits_kernel reads the 1.8 KB per sample across PCIe itself.  The copy was 14 us of DMA -- but the copy engine
@@ -465,7 +440,7 @@ public:
             io.packed_src = nullptr;
             if (in_place) io.packed_src = (const unsigned*)zc_device_pointer((float*)const_cast<unsigned*>(packed));
             if (io.packed_src) return 0;
-            if (!io.packed && dev_alloc(&io.packed, (size_t)max_batch_ * (40 * 12 + 8))) return -1;
+            if (!io.packed && dev_alloc(&io.packed, (size_t)max_batch_ * kPackedRecordWords)) return -1;
             HIP_OK(hipMemcpyAsync(io.packed, packed, sizeof(unsigned) * nrec * words, hipMemcpyHostToDevice, copy_stream));
             return 0;
         }
@@ -800,7 +775,7 @@ private:
         const size_t B2 = (size_t)board_ * board_;
         for (IoSlot& io : io_) {
             if (dev_alloc(&io.planes, (size_t)max_batch_ * desc_.input_channels * B2)) return -1;
-            if (dev_alloc(&io.packed, (size_t)max_batch_ * (40 * 12 + 8))) return -1;  // the packed form of the same planes (packed_planes.h)
+            if (dev_alloc(&io.packed, (size_t)max_batch_ * kPackedRecordWords)) return -1;  // the packed form of the same planes (packed_planes.h)
             if (dev_alloc(&io.off, max_batch_ + 1) || dev_alloc(&io.bsz, max_batch_) || dev_alloc(&io.perm, max_batch_)) return -1;
             if (dev_alloc(&io.prob, (size_t)max_batch_ * desc_.probabilities_channels * B2)) return -1;
             if (dev_alloc(&io.pass, (size_t)max_batch_ * desc_.pass_probability_outputs)) return -1;
@@ -1414,35 +1389,16 @@ private:
         const double px = f.px;
         const BatchGeom g = dgeom(f.io);
         const IoSlot& io = f.io;
-        if (io.packed_binary > 0) {
-            // (records read across PCIe: one workgroup per sample, so that a record crosses once)
-            const unsigned* rec = io.packed_src ? io.packed_src : io.packed;
-            const int split = io.packed_src ? 1 : kPackSplit;
-            const int nbin = io.packed_binary, words = nbin * 12 + 8;
-            if (io.symm_on)
-                return timed(f, "pack_input", 0, (double)ns * words * 4 + px * cs * sizeof(T), [&] {
-                    hipLaunchKernelGGL(pack_bits_symm_kernel<T>, dim3(ns * split), dim3(256), 0, f.stream, rec, words, nbin, dst, g, cin, cs,
-                                       io.g_perm, (const int*)io.sy_src, (const int*)io.sy_symm, n0, split);
-                });
-            return timed(f, "pack_input", 0, (double)ns * words * 4 + px * cs * sizeof(T), [&] {
-                hipLaunchKernelGGL(pack_bits_kernel<T>, dim3(ns * split), dim3(256), 0, f.stream, rec, words, nbin, dst, g, cin, cs,
-                                   io.g_perm, n0, split);
-            });
-        }
-        const int grid = ns * kPackSplit;  // kPackSplit workgroups per sample
-        const int chunk = pack_input_chunk(slot_pix_, cs, (int)sizeof(T));
-        const size_t lds = (size_t)chunk * (cs * sizeof(T) + 16);
-        const size_t flat_lds = pack_input_flat_lds(slot_pix_, cs, (int)sizeof(T));
-        // a sample that fits 64 KiB of LDS whole and whose planes are below 2^16 floats: one workgroup per sample
-        const bool flat = flat_lds <= 64 * 1024 && (size_t)cin * board * board < 65536;
-        return timed(f, "pack_input", 0, px * cin * 4 + px * cs * sizeof(T), [&] {
-            if (flat)
-                hipLaunchKernelGGL(pack_input_flat_kernel<T>, dim3(ns), dim3(kPackFlatThreads), flat_lds, f.stream,
-                                   (const float*)io.planes, dst, g, cin, cs, board, io.g_perm, n0);
-            else
-                hipLaunchKernelGGL(pack_input_kernel<T>, dim3(grid), dim3(kPackThreads), lds, f.stream,
-                                   (const float*)io.planes, dst, g, cin, cs, board, io.g_perm, chunk, n0);
-        });
+        // (which kernel, its workgroups per sample -- one for records read across PCIe --, chunk and LDS: pack_plan, engine_plan.h)
+        const bool records = io.packed_binary > 0;
+        const PackPlan pl = pack_plan(sizeof(T), cin, cs, board, records, io.symm_on, io.packed_src != nullptr);
+        PackSource in;
+        in.planes = (const float*)io.planes;
+        in.records = io.packed_src ? io.packed_src : io.packed;
+        in.nbin = io.packed_binary;
+        in.src_map = io.sy_src; in.symm_map = io.sy_symm;
+        const double bytes_in = records ? (double)ns * (in.nbin * kPackedWords + kPackedScalars) * 4 : px * cin * 4;
+        return timed(f, "pack_input", 0, bytes_in + px * cs * sizeof(T), [&] { pack_launch<T>(pl, f.stream, in, dst, g, cin, cs, board, io.g_perm, n0, ns); });
     }
 
     int forward_graph(Fwd& f) {

@@ -756,6 +756,114 @@ static int se_unit_launches(hipStream_t s, const BatchGeom& g, double px, T* x, 
                [&] { hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, s, (const T*)x, res, x, (const float*)gate, g, C, cs, act, n0); });
 }
 
+// ------------------------------------------------------------------ the input stage (small_ops.h), shared by the engine and its tap
+// A packed batch whose device samples name their record and board symmetry (sayuri_hip_forward_packed_symm): `n_records`
+// records in the caller's array, src[n] (null: sample i reads record i) and symm[n] in the caller's sample order.
+struct SymmReq {
+    int n_records = 0;
+    const int* src = nullptr;
+    const int* symm = nullptr;
+};
+// Packed records with `binary` bit planes for a network of `input_channels` planes on an NN grid of `board`: 0, or the refusal.
+// A record holds at most kPackedMaxBinary bit planes -- the bit kernels' LDS copy and the record buffers are sized by it -- and
+// 8 scalars behind them; a plane is 12 words of 32 cells.
+static int packed_binary_check(int binary, int input_channels, int board) {
+    if (binary > kPackedMaxBinary)
+        return fail("packed planes: binary_planes = " + std::to_string(binary) + ": a record holds at most " + std::to_string(kPackedMaxBinary) +
+                    " bit planes");
+    if (binary <= 0 || binary > input_channels || input_channels - binary > kPackedScalars || board * board > kPackedWords * 32)
+        return fail("packed planes: bad binary plane count for this network");
+    return 0;
+}
+// A symmetry request's arguments, checked before anything is enqueued.  The record array is bounded by max_batch: the copy
+// path moves it into the slot's record buffer, which holds that many.
+static int check_symm_request(int n, int max_batch, const unsigned* packed, const SymmReq& sy) {
+    if (!packed || !sy.symm) return fail("packed_symm: null argument");
+    if (n <= 0 || n > max_batch) return fail("batch size out of range");
+    if (sy.n_records <= 0 || sy.n_records > max_batch)
+        return fail("packed_symm: n_records " + std::to_string(sy.n_records) + " out of range (1.." + std::to_string(max_batch) + ")");
+    if (!sy.src && n > sy.n_records) return fail("packed_symm: the identity record map needs n <= n_records");
+    for (int i = 0; i < n; ++i) {
+        if (sy.symm[i] < 0 || sy.symm[i] > 7)
+            return fail("packed_symm: symm[" + std::to_string(i) + "] = " + std::to_string(sy.symm[i]) + " is no board symmetry (0..7)");
+        if (sy.src && (sy.src[i] < 0 || sy.src[i] >= sy.n_records))
+            return fail("packed_symm: src[" + std::to_string(i) + "] = " + std::to_string(sy.src[i]) + " is outside the " +
+                        std::to_string(sy.n_records) + " records");
+    }
+    return 0;
+}
+// Which kernel turns a batch's planes or records into the input convolution's image, and its launch.  fp32 planes: a sample
+// that fits 64 KiB of LDS whole and whose planes are below 2^16 floats takes the flat kernel, one workgroup per sample; else
+// the chunked one, kPackSplit workgroups per sample and `chunk` pixels per pass.  Records: kPackSplit workgroups per sample, or
+// one when they are read in place across PCIe (a record then crosses once).  The values of `kernel` are what
+// sayuri_hip_test_last_pack reports.
+enum PackKernel { kPackChunked = 0, kPackFlat = 1, kPackBits = 2, kPackBitsSymm = 3 };
+struct PackPlan {
+    PackKernel kernel = kPackChunked;
+    int split = kPackSplit;  // workgroups per sample
+    int threads = kPackThreads;
+    int chunk = 0;           // chunked: pixels per pass
+    size_t lds = 0;          // dynamic LDS of the launch
+    // passes a workgroup makes over its pixel range on a bs x bs sample (chunked); passes over a sample's planes (flat); else 1
+    int passes(int bs, int cin, int board) const {
+        if (kernel == kPackChunked) return ((bs * bs + kPackSplit - 1) / kPackSplit + chunk - 1) / chunk;
+        if (kernel == kPackFlat) return (cin * board * board + kPackFlatThreads * kPackFlatLoads - 1) / (kPackFlatThreads * kPackFlatLoads);
+        return 1;
+    }
+};
+static PackPlan pack_plan(size_t elem, int cin, int cs, int board, bool records, bool symm, bool in_place) {
+    PackPlan pl;
+    if (records) {
+        pl.kernel = symm ? kPackBitsSymm : kPackBits;
+        pl.split = in_place ? 1 : kPackSplit;
+        pl.threads = 256;
+        return pl;
+    }
+    const int slot_pix = board * board;
+    const size_t flat_lds = pack_input_flat_lds(slot_pix, cs, (int)elem);
+    if (flat_lds <= 64 * 1024 && (size_t)cin * board * board < 65536) {
+        pl.kernel = kPackFlat;
+        pl.split = 1;
+        pl.threads = kPackFlatThreads;
+        pl.lds = flat_lds;
+        return pl;
+    }
+    pl.chunk = pack_input_chunk(slot_pix, cs, (int)elem);
+    pl.lds = (size_t)pl.chunk * (cs * elem + 16);
+    return pl;
+}
+// The launch of `pl` over the samples [n0, n0 + ns): planes, or records of nbin bit planes (with the symmetry kernel the record
+// map and the symmetries, in the caller's order) -> dst.  perm: device sample -> caller's slot.
+struct PackSource {
+    const float* planes = nullptr;
+    const unsigned* records = nullptr;
+    int nbin = 0;
+    const int* src_map = nullptr;
+    const int* symm_map = nullptr;
+};
+template <typename T>
+static void pack_launch(const PackPlan& pl, hipStream_t s, const PackSource& in, T* dst, const BatchGeom& g, int cin, int cs, int board,
+                        const int* perm, int n0, int ns) {
+    const int words = in.nbin * kPackedWords + kPackedScalars;
+    switch (pl.kernel) {
+    case kPackBitsSymm:
+        hipLaunchKernelGGL(pack_bits_symm_kernel<T>, dim3(ns * pl.split), dim3(pl.threads), 0, s, in.records, words, in.nbin, dst, g, cin, cs, perm,
+                           in.src_map, in.symm_map, n0, pl.split);
+        break;
+    case kPackBits:
+        hipLaunchKernelGGL(pack_bits_kernel<T>, dim3(ns * pl.split), dim3(pl.threads), 0, s, in.records, words, in.nbin, dst, g, cin, cs, perm, n0,
+                           pl.split);
+        break;
+    case kPackFlat:
+        hipLaunchKernelGGL(pack_input_flat_kernel<T>, dim3(ns), dim3(pl.threads), pl.lds, s, in.planes, dst, g, cin, cs, board, perm, n0);
+        break;
+    case kPackChunked:
+        hipLaunchKernelGGL(pack_input_kernel<T>, dim3(ns * pl.split), dim3(pl.threads), pl.lds, s, in.planes, dst, g, cin, cs, board, perm, pl.chunk,
+                           n0);
+        break;
+    }
+}
+
 // the persistent tower kernels (conv_tower.h) out of the embedded code object: [0] 256-channel tile, [1] 128-channel tile
 }  // namespace sayuri
 extern "C" const unsigned char sayuri_tower_hsaco[];

@@ -1,5 +1,5 @@
 // engine_taps.h -- layer-level test taps of the C-ABI (sayuri_hip_test_*): one kernel family at a time on host tensors, for the
-// parity tests (tests/test_gpu_layers.py, test_gpu_smallops.py).  Not used by the pipe.  A tap converts the layouts on the host,
+// parity tests (tests/test_gpu_layers.py, test_gpu_smallops.py, test_gpu_input.py).  Not used by the pipe.  A tap converts the layouts on the host,
 // in and out, and launches ONE layer -- sayuri_hip_test_tower_run one RUN of layers, as one persistent launch; the device images,
 // the routing of a convolution to its kernel family, the launch parameters and the linking of a run are the engine's own code
 // (engine_plan.h), so the tests check the host code the engine runs.
@@ -595,6 +595,147 @@ static int test_head_board_impl(int device, int n, const int* board_sizes, int m
     return o.download(prob, pass, misc, own);
 }
 
+// The input stage: ONE of pack_input_kernel / pack_input_flat_kernel / pack_bits_kernel / pack_bits_symm_kernel on host data,
+// chosen and launched by the engine's own pack_plan / pack_launch (engine_plan.h), into an image that starts as a sentinel and
+// comes back whole.  The arguments are refused as Engine::enqueue_inputs / check_symm refuse them (max_batch = stage_batch, or n).
+// Geometry and maps reach the device as the engine's do: copied (the resident arrays of a uniform batch), or -- stage_batch > 0
+// -- from a pinned ring laid out for stage_batch samples through geom_stage_kernel / symm_stage_kernel.  What the staging
+// kernels left is read back and compared BEFORE the pack kernel runs on it: a board size that is not the batch's would send a
+// pack kernel past the image.  (The unused entries of the ring and of the device arrays hold harmless values for the same reason.)
+static thread_local int g_test_pack[4] = {-1, 0, 0, 0};  // the last sayuri_hip_test_pack_input launch: kernel (-1: none), cs, workgroups per sample, passes
+struct TestPinned {  // host memory from the allocator behind sayuri_hip_host_alloc, freed at scope exit
+    ~TestPinned() { for (void* p : ptrs_) sayuri_hip_host_free(p); }
+    void* alloc(size_t bytes) {
+        void* p = sayuri_hip_host_alloc(bytes);
+        if (p) ptrs_.push_back(p);
+        return p;
+    }
+private:
+    std::vector<void*> ptrs_;
+};
+struct TestPackArgs {
+    int n, max_board, cin;
+    const int* board_sizes;  // [n] the board of every DEVICE sample
+    const float* planes;
+    const unsigned* records;
+    int n_records, binary;
+    const int *src, *symm, *perm;
+    int n0, ns, stage_batch, in_place;
+    float sentinel;
+    int guard_rows;
+};
+static bool test_staged_equal(const int* dev, const std::vector<int>& want) {
+    std::vector<int> got(want.size());
+    return hipMemcpy(got.data(), dev, sizeof(int) * want.size(), hipMemcpyDeviceToHost) == hipSuccess && got == want;
+}
+template <typename T> static int test_pack_input_impl(int device, const TestPackArgs& a, float* image) {
+    g_test_pack[0] = -1; g_test_pack[1] = g_test_pack[2] = g_test_pack[3] = 0;
+    const int n = a.n, board = a.max_board, cin = a.cin;
+    const int max_batch = a.stage_batch > 0 ? a.stage_batch : n;
+    if (n <= 0 || n > max_batch) return fail("batch size out of range");
+    if (board < 2 || board > 25 || cin < 1 || cin > 512 || a.guard_rows < 0) return fail("test_pack_input: bad argument");
+    const bool records = a.planes == nullptr, symm = records && a.symm != nullptr;
+    if (records && !a.records) return fail("test_pack_input: neither planes nor records");
+    if (records && packed_binary_check(a.binary, cin, board)) return -1;
+    const SymmReq sy{a.n_records, a.src, a.symm};
+    if (symm && check_symm_request(n, max_batch, a.records, sy)) return -1;
+    if (records && !symm && a.n_records < n) return fail("test_pack_input: records are read by slot: n_records >= n");
+    if (a.in_place && !records) return fail("test_pack_input: only records are read in place");
+    if (a.n0 < 0 || a.ns <= 0 || a.n0 + a.ns > n) return fail("test_pack_input: the sample range [n0, n0 + ns) is not inside the batch");
+    for (int i = 0; i < n; ++i)
+        if (a.perm && (a.perm[i] < 0 || a.perm[i] >= n)) return fail("test_pack_input: perm[" + std::to_string(i) + "] is no slot of the batch");
+    HIP_OK(hipSetDevice(device));
+    TestArena A;
+    TestPinned P;
+    const int B2 = board * board, cs = round_up(cin, 32);
+    // the geometry arrays: off[n + 1], bsz[n], perm[n]
+    std::vector<int> off(n + 1, 0), bsz(a.board_sizes, a.board_sizes + n), perm(n);
+    for (int i = 0; i < n; ++i) {
+        if (bsz[i] < 2 || bsz[i] > board) return fail("sample board size out of range");
+        off[i + 1] = off[i] + bsz[i] * bsz[i];
+        perm[i] = a.perm ? a.perm[i] : i;
+    }
+    int* d_off = A.upload(std::vector<int>(max_batch + 1, 0));
+    int* d_bsz = A.upload(std::vector<int>(max_batch, 2));
+    int* d_perm = A.upload(std::vector<int>(max_batch, 0));
+    int *d_src = nullptr, *d_symm = nullptr;
+    if (!d_off || !d_bsz || !d_perm) return fail("test_pack_input: hipMalloc failed");
+    std::vector<int> src(n, 0), sym(n, 0);
+    if (symm) {
+        for (int i = 0; i < n; ++i) { src[i] = a.src ? a.src[i] : i; sym[i] = a.symm[i]; }
+        d_src = A.upload(std::vector<int>(max_batch, 0));
+        d_symm = A.upload(std::vector<int>(max_batch, 0));
+        if (!d_src || !d_symm) return fail("test_pack_input: hipMalloc failed");
+    }
+    if (a.stage_batch > 0) {
+        // Engine::enqueue_inputs' rings: off | bsz | perm at strides of max_batch + 1 / max_batch, src | symm at max_batch
+        int* hg = (int*)P.alloc(sizeof(int) * (3 * max_batch + 1));
+        if (!hg) return fail("test_pack_input: hipHostMalloc failed");
+        for (int i = 0; i < 3 * max_batch + 1; ++i) hg[i] = i > max_batch && i <= 2 * max_batch ? 2 : 0;
+        std::memcpy(hg, off.data(), sizeof(int) * (n + 1));
+        std::memcpy(hg + max_batch + 1, bsz.data(), sizeof(int) * n);
+        std::memcpy(hg + 2 * max_batch + 1, perm.data(), sizeof(int) * n);
+        hipLaunchKernelGGL(geom_stage_kernel, dim3(1), dim3(256), 0, 0, (const int*)hg, max_batch, n, d_off, d_bsz, d_perm);
+        HIP_OK(hipGetLastError());
+        if (symm) {
+            int* hs = (int*)P.alloc(sizeof(int) * 2 * max_batch);
+            if (!hs) return fail("test_pack_input: hipHostMalloc failed");
+            std::memset(hs, 0, sizeof(int) * 2 * max_batch);
+            std::memcpy(hs, src.data(), sizeof(int) * n);
+            std::memcpy(hs + max_batch, sym.data(), sizeof(int) * n);
+            hipLaunchKernelGGL(symm_stage_kernel, dim3(1), dim3(256), 0, 0, (const int*)hs, max_batch, n, d_src, d_symm);
+            HIP_OK(hipGetLastError());
+        }
+        HIP_OK(hipDeviceSynchronize());
+        if (!test_staged_equal(d_off, off) || !test_staged_equal(d_bsz, bsz) || !test_staged_equal(d_perm, perm))
+            return fail("test_pack_input: geom_stage_kernel left other geometry arrays than the ring holds");
+        if (symm && (!test_staged_equal(d_src, src) || !test_staged_equal(d_symm, sym)))
+            return fail("test_pack_input: symm_stage_kernel left another record map or other symmetries than the ring holds");
+    } else {
+        HIP_OK(hipMemcpy(d_off, off.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_bsz, bsz.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_perm, perm.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        if (symm) {
+            HIP_OK(hipMemcpy(d_src, src.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(d_symm, sym.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        }
+    }
+    // the planes, or the records: copied, or where they lie in pinned memory (submit_packed's in-place path)
+    PackSource in;
+    if (records) {
+        const size_t words = (size_t)(symm ? a.n_records : n) * (a.binary * kPackedWords + kPackedScalars);
+        if (a.in_place) {
+            unsigned* h = (unsigned*)P.alloc(sizeof(unsigned) * words);
+            if (!h) return fail("test_pack_input: hipHostMalloc failed");
+            std::memcpy(h, a.records, sizeof(unsigned) * words);
+            HIP_OK(hipHostGetDevicePointer((void**)&in.records, h, 0));
+        } else {
+            in.records = A.upload(std::vector<unsigned>(a.records, a.records + words));
+        }
+        in.nbin = a.binary;
+        in.src_map = d_src; in.symm_map = d_symm;
+        if (!in.records) return fail("test_pack_input: hipMalloc failed");
+    } else {
+        in.planes = A.upload(std::vector<float>(a.planes, a.planes + (size_t)n * cin * B2));
+        if (!in.planes) return fail("test_pack_input: hipMalloc failed");
+    }
+    // the image and the guard behind its last slot: the sentinel everywhere
+    const size_t elems = ((size_t)n * B2 + a.guard_rows) * cs;
+    T* dimg = A.upload(std::vector<T>(elems, (T)a.sentinel));
+    if (!dimg) return fail("test_pack_input: hipMalloc failed");
+    const PackPlan pl = pack_plan(sizeof(T), cin, cs, board, records, symm, a.in_place != 0);
+    const BatchGeom g{d_off, d_bsz, n, off[n], B2};
+    pack_launch<T>(pl, 0, in, dimg, g, cin, cs, board, a.perm || a.stage_batch > 0 ? d_perm : nullptr, a.n0, a.ns);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    g_test_pack[0] = pl.kernel; g_test_pack[1] = cs; g_test_pack[2] = pl.split;
+    g_test_pack[3] = pl.passes(*std::max_element(bsz.begin() + a.n0, bsz.begin() + a.n0 + a.ns), cin, board);
+    std::vector<T> h(elems);
+    HIP_OK(hipMemcpy(h.data(), dimg, elems * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < elems; ++i) image[i] = (float)h[i];
+    return 0;
+}
+
 }  // namespace sayuri
 
 extern "C" int sayuri_hip_test_conv_se(int device, int n, const int* board_sizes, int max_board, int channels, int se_size, int act,
@@ -677,4 +818,19 @@ extern "C" int sayuri_hip_test_conv(int device, int use_fp16, int n, const int* 
                                    bias, res, y);
     return test_conv_impl<float>(device, n, board_sizes, max_board, cin, cout, k, depthwise, act, post_residual, x, w,
                                  bias, res, y);
+}
+
+extern "C" int sayuri_hip_test_pack_input(int device, int use_fp16, int n, const int* board_sizes, int max_board, int cin, const float* planes,
+                                          const unsigned* records, int n_records, int binary_planes, const int* src, const int* symm,
+                                          const int* perm, int n0, int ns, int stage_batch, int in_place, float sentinel, int guard_rows,
+                                          float* image) {
+    if (!board_sizes || !image) return fail("test_pack_input: bad argument");
+    const sayuri::TestPackArgs a{n, max_board, cin, board_sizes, planes, records, n_records, binary_planes, src, symm, perm, n0, ns, stage_batch,
+                                 in_place, sentinel, guard_rows};
+    return use_fp16 ? sayuri::test_pack_input_impl<f16>(device, a, image) : sayuri::test_pack_input_impl<float>(device, a, image);
+}
+extern "C" int sayuri_hip_test_last_pack(int out[4]) {
+    if (!out) return fail("test_last_pack: bad argument");
+    std::copy(sayuri::g_test_pack, sayuri::g_test_pack + 4, out);
+    return 0;
 }

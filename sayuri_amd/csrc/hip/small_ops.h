@@ -125,8 +125,13 @@ static inline int pack_input_chunk(int slot_pix, int cs, int elem) {
 // The same activations from PACKED planes (csrc/host/packed_planes.h): record of a sample = uint32
 // bits[nbin][12] (bit y*bs+x of a 0/1 plane, the sample's OWN cell order -- no re-padding into the NN grid) followed by 8
 // floats (the value of each broadcast plane).  1.8 KB per sample instead of 62 KB over PCIe and out of HBM.
+// A record holds at most kPackedMaxBinary bit planes (the host's PackedPlanes::kMaxBinary): the bit kernels' LDS copy and the
+// engine's record buffers are sized by it, and whoever launches a bit kernel refuses more (packed_binary_check, engine_plan.h).
 // kPackSplit workgroups per sample (pixel ranges): the record goes to LDS with one coalesced load, then thread = (pixel,
 // 16-byte piece) in output order -- every store of a wave is 1 KiB contiguous.
+constexpr int kPackedMaxBinary = 40;
+constexpr int kPackedWords = 12, kPackedScalars = 8;  // 32-bit words per bit plane (19 x 19 cells), float slots behind the planes
+constexpr int kPackedRecordWords = kPackedMaxBinary * kPackedWords + kPackedScalars;  // the largest record
 // The geometry arrays of a MIXED batch, moved from the engine's pinned staging ring to device memory by the forward's own
 // stream (one workgroup; `stage` is host memory the device reads over PCIe: off[n+1] | bsz[n] | perm[n] at strides of
 // max_batch + 1 / max_batch).  Not a hipMemcpyAsync: see Engine::enqueue_inputs.
@@ -144,7 +149,7 @@ __global__ __launch_bounds__(256) void pack_bits_kernel(const unsigned* __restri
                                                         T* __restrict__ out, BatchGeom g, int cin, int cs,
                                                         const int* __restrict__ perm, int n0 = 0, int split = kPackSplit) {
     constexpr int EPP = ElemTraits<T>::kPieceElems;
-    __shared__ unsigned rec[40 * 13 + 8];  // 13 words per plane: the eight planes a wave reads at once fall on different banks
+    __shared__ unsigned rec[kPackedMaxBinary * 13 + 8];  // 13 words per plane: the eight planes a wave reads at once fall on different banks
     const int n = n0 + blockIdx.x / split, part = blockIdx.x % split, tid = threadIdx.x;  // split: workgroups per sample
     const int bs = g.bsz[n], npix = bs * bs, ppr = cs / EPP;
     const int per = (npix + split - 1) / split, pbeg = part * per, pend = min(npix, pbeg + per);
@@ -196,7 +201,7 @@ __global__ __launch_bounds__(256) void pack_bits_symm_kernel(const unsigned* __r
                                                              const int* __restrict__ perm, const int* __restrict__ src_map,
                                                              const int* __restrict__ symm_map, int n0, int split) {
     constexpr int EPP = ElemTraits<T>::kPieceElems;
-    __shared__ unsigned rec[40 * 13 + 8];
+    __shared__ unsigned rec[kPackedMaxBinary * 13 + 8];
     const int n = n0 + blockIdx.x / split, part = blockIdx.x % split, tid = threadIdx.x;
     const int bs = g.bsz[n], npix = bs * bs, ppr = cs / EPP;
     const int per = (npix + split - 1) / split, pbeg = part * per, pend = min(npix, pbeg + per);

@@ -551,3 +551,214 @@ CAN_FAIL = [("board", Case("unit", True, (19, 19), 384, 384, 3, False, 0, False,
             ("generic-input43", Case("unit", True, (19,) * 4, 43, 96, 3, False, 0, False, False, 105), (95, 42))]
 CAN_FAIL_TAPS = ((1, 1), (0, 2))  # an interior tap and a corner tap
 CAN_FAIL_TOWER = TowerCase("one-layer", (19, 19, 19), (0,), (-1,), False, False, (), 1)
+
+
+# ====================================================================================================================
+# The input stage (test_gpu_input.py, test_input_reference_cpu.py): planes or packed records -> the input convolution's image.
+#
+# A case names the CALLER's slots (cbsz: the board of slot j; for a symmetry case slot j shows record src[j] under symm[j]) and
+# the device order perm (device sample i shows slot perm[i]): "sorted" is the engine's own (largest board first, stable), a
+# tuple any permutation.  kernel / split / multi are what the tap's report must say: the kernel that ran, the workgroups per
+# sample, and whether a workgroup made more than one pass (chunked) or the sample took more than one `base` pass (flat).
+PackCase = collections.namedtuple("PackCase", "name fp16 form board cbsz cin binary perm n0 ns kernel split multi stage in_place beyond src symm nrec")
+PACK_SPLIT = 4           # kPackSplit
+PACK_FLAT_PASS = 16384   # kPackFlatThreads * kPackFlatLoads
+PACK_MAX_BINARY = 40     # kPackedMaxBinary
+PACK_STAGE_BATCH = 24    # the max_batch the staging ring of a staged case is laid out for (> every case's n)
+PACK_GUARD_ROWS = 64
+PACK_SENTINEL = -65504.0   # exact in fp16 and in fp32, and no value of a draw
+
+
+def pack_rule(fp16, cin, board):
+    """Engine::pack_input's rule for fp32 planes restated (engine_plan.h pack_plan): -> ("flat", 0, base passes) when a sample's
+    image fits 64 KiB of LDS and its planes are below 2^16 floats, else ("chunked", pixels per pass, None)"""
+    elem, cs, B2 = (2 if fp16 else 4), (cin + 31) // 32 * 32, board * board
+    stride = cs * elem + 16
+    if B2 * stride <= 64 * 1024 and cin * B2 < 65536:
+        return "flat", 0, -(-cin * B2 // PACK_FLAT_PASS)
+    return "chunked", min((B2 + PACK_SPLIT - 1) // PACK_SPLIT, 64 * 1024 // stride), None
+
+
+def chunked_passes(chunk, bs):
+    return -(-((bs * bs + PACK_SPLIT - 1) // PACK_SPLIT) // chunk)
+
+
+def _pack_case(name, fp16, form, board, cbsz, cin, binary=0, perm="sorted", n0=0, ns=None, kernel=None, multi=False, stage=0, in_place=0, beyond=0,
+               src=None, symm=None, nrec=0):
+    n = len(cbsz)
+    if kernel is None:
+        kernel = {"bits": "bits", "symm": "symm"}[form]
+    split = 1 if kernel == "flat" or in_place else PACK_SPLIT
+    return PackCase(name, fp16, form, board, tuple(cbsz), cin, binary, perm, n0, n - n0 if ns is None else ns, kernel, split, multi, stage, in_place, beyond,
+                    src, symm, nrec or n)
+
+
+def pack_order(c):
+    """-> (perm, bsz in device order)"""
+    n = len(c.cbsz)
+    perm = sorted(range(n), key=lambda j: -c.cbsz[j]) if c.perm == "sorted" else list(range(n) if c.perm is None else c.perm)
+    return perm, [c.cbsz[j] for j in perm]
+
+
+_SHUFFLE12 = (7, 2, 11, 0, 5, 9, 3, 10, 1, 8, 6, 4)   # no involution: used backwards it is another permutation
+_SHUFFLE8 = (5, 0, 3, 7, 1, 6, 4, 2)
+_SHUFFLE5 = (3, 0, 4, 1, 2)
+PACK_PLANE_CASES = [
+    # ---- the flat kernel (one workgroup per sample)
+    _pack_case("f16-flat-g19-c43-sorted", True, "planes", 19, (9, 19, 2, 13, 3, 19, 7, 5, 16, 11, 18, 4), 43, kernel="flat"),
+    _pack_case("f16-flat-g19-c38-shuffled-mid", True, "planes", 19, (6, 8, 10, 12, 14, 15, 17, 19, 2, 3, 19, 13), 38, perm=_SHUFFLE12, n0=3, ns=7, kernel="flat"),
+    _pack_case("f16-flat-g19-c64-two-base-passes", True, "planes", 19, (19, 3, 17, 2, 12), 64, perm=_SHUFFLE5, kernel="flat", multi=True),
+    _pack_case("f16-flat-g9-c384-two-base-passes", True, "planes", 9, (9, 2, 5, 8, 3), 384, kernel="flat", multi=True),
+    _pack_case("f16-flat-g19-c6", True, "planes", 19, (19, 2, 3, 11), 6, perm=None, kernel="flat"),
+    _pack_case("f16-flat-g13-c43-mid", True, "planes", 13, (13, 4, 9, 2, 13, 3, 10, 6), 43, perm=_SHUFFLE8, n0=2, ns=5, kernel="flat"),
+    _pack_case("f32-flat-g13-c43-sorted", False, "planes", 13, (5, 13, 2, 3, 9, 11, 12, 13), 43, kernel="flat"),
+    _pack_case("f32-flat-g9-c38-shuffled", False, "planes", 9, (9, 2, 3, 7, 9, 4, 6, 8), 38, perm=_SHUFFLE8, kernel="flat"),
+    _pack_case("f32-flat-g13-c64", False, "planes", 13, (13, 2, 7, 3, 12), 64, perm=_SHUFFLE5, n0=1, ns=3, kernel="flat"),
+    # ---- the chunked kernel, one pass per workgroup
+    _pack_case("f32-chunked-g19-c43-sorted", False, "planes", 19, (9, 19, 2, 13, 3, 19, 7, 5, 16, 11, 18, 4), 43, kernel="chunked"),
+    _pack_case("f32-chunked-g19-c38-shuffled-mid", False, "planes", 19, (6, 8, 10, 12, 14, 15, 17, 19, 2, 3, 19, 13), 38, perm=_SHUFFLE12, n0=4, ns=6, kernel="chunked"),
+    _pack_case("f32-chunked-g19-c64", False, "planes", 19, (19, 2, 3, 14, 5), 64, perm=_SHUFFLE5, kernel="chunked"),
+    _pack_case("f16-chunked-g19-c96", True, "planes", 19, (19, 3, 17, 2, 12, 19, 6, 9), 96, perm=_SHUFFLE8, kernel="chunked"),
+    # ---- the chunked kernel, more than one pass (the first 19x19 workgroups whose pixel range does not fit the LDS at once)
+    _pack_case("f32-chunked-g19-c192-passes", False, "planes", 19, (19, 2, 18, 3, 19), 192, perm=_SHUFFLE5, kernel="chunked", multi=True),
+    _pack_case("f16-chunked-g19-c384-passes", True, "planes", 19, (3, 19, 2, 19), 384, n0=1, ns=3, kernel="chunked", multi=True),
+]
+
+# both bit kernels five ways: split, in place, staged, resident, and with every record bit at or beyond bs*bs set
+_WAYS = (dict(), dict(in_place=1), dict(stage=1), dict(stage=1, in_place=1), dict(beyond=1))
+_WAY_IDS = ("split-resident", "inplace-resident", "split-staged", "inplace-staged", "split-beyond")
+_BIT_SHAPES = (
+    # fp16, grid, caller's boards, cin, binary, perm, n0, ns
+    (True, 19, (9, 19, 2, 13, 3, 19, 7, 5, 16, 11, 18, 4), 43, 37, "sorted", 0, None),
+    (False, 19, (6, 8, 10, 12, 14, 15, 17, 19, 2, 3, 19, 13), 38, 34, _SHUFFLE12, 3, 7),
+    (True, 13, (13, 4, 9, 2, 13, 3, 10, 6), 43, 37, _SHUFFLE8, 0, None),
+    (False, 9, (9, 2, 3, 7, 9, 4, 6, 8), 43, 37, "sorted", 2, 5),
+    (True, 19, (19, 2, 3, 17, 12), 48, 40, _SHUFFLE5, 0, None),    # the record limit itself: 40 bit planes, 8 scalars
+)
+PACK_BIT_CASES = [_pack_case(f"bits-{'f16' if s[0] else 'f32'}-g{s[1]}-c{s[3]}-{wid}", s[0], "bits", s[1], s[2], s[3], s[4], perm=s[5], n0=s[6], ns=s[7], **way)
+                  for s, way, wid in zip(_BIT_SHAPES, _WAYS, _WAY_IDS)]
+PACK_BIT_CASES.append(_pack_case("bits-f16-g19-c6", True, "bits", 19, (19, 2, 5, 3), 6, 2, perm=None))
+
+
+def _symm_case(k, big, small):
+    """all eight symmetries of one record of each of two board sizes, as sixteen shuffled device samples"""
+    fp16, cin, binary = ((True, 43, 37), (False, 38, 34), (False, 43, 37))[k % 3]
+    rng = np.random.default_rng([911, big, small])
+    slots = [(r, s) for r in (0, 1) for s in range(8)]
+    slots = [slots[j] for j in rng.permutation(16)]
+    src, symm = tuple(r for r, _ in slots), tuple(s for _, s in slots)
+    cbsz = tuple((big, small)[r] for r in src)
+    perm = "sorted" if k % 2 == 0 else tuple(int(v) for v in rng.permutation(16))
+    way = _WAYS[k % 5]
+    return _pack_case(f"symm-{'f16' if fp16 else 'f32'}-b{big}+{small}-{_WAY_IDS[k % 5]}", fp16, "symm", 19, cbsz, cin, binary, perm=perm, src=src, symm=symm,
+                      nrec=2, **way)
+
+
+PACK_SYMM_CASES = [_symm_case(k, 19 - k, 2 + k) for k in range(9)]   # (19, 2), (18, 3) ... (11, 10): every size once
+# the map and a window: three records, device samples that skip one of them, a launch over the middle samples only
+PACK_SYMM_CASES.append(_pack_case("symm-f16-g13-three-records-mid", True, "symm", 13, (13, 7, 13, 7, 7, 13, 13, 7), 43, 37, perm=_SHUFFLE8, n0=2, ns=5,
+                                  src=(2, 0, 2, 0, 0, 2, 2, 0), symm=(5, 3, 0, 6, 1, 7, 2, 4), nrec=3, stage=1))
+PACK_CASES = PACK_PLANE_CASES + PACK_BIT_CASES + PACK_SYMM_CASES
+PACK_IDS = [c.name for c in PACK_CASES]
+# the plane cases whose planes can also travel as records (cin - binary scalars): both routes must leave one image
+PACK_BOTH_ROUTES = [(c, b) for c, b in ((PACK_PLANE_CASES[0], 37), (PACK_PLANE_CASES[1], 34), (PACK_PLANE_CASES[6], 37), (PACK_PLANE_CASES[9], 37),
+                                        (PACK_PLANE_CASES[10], 34))]
+
+F16_OFF_BOARD = np.uint16(0x7BFF)   # 65504: the fp16 normal the off-board cells of a placement draw hold, and nothing else
+F32_OFF_BOARD = np.float32(-3.0e7)
+# a tie between two fp16 neighbours, just above and below one, a quarter and three quarters of the way, one fp32 ulp above the
+# lower neighbour and one below the upper: the low 13 bits of the fp32 mantissa
+ROUNDING_TAILS = np.array([0x1000, 0x1001, 0x0FFF, 0x0800, 0x1800, 0x0001, 0x1FFF], np.uint32)
+
+
+def _f16_normals(rng, count):
+    """`count` fp16 normals (0x0400..0x7BFE and their negatives: all but the off-board value) as float32, each as rarely as possible"""
+    pool = np.concatenate([np.arange(0x0400, 0x7BFF, dtype=np.uint16), np.arange(0x8400, 0xFBFF, dtype=np.uint16)])
+    picks = np.concatenate([rng.permutation(pool) for _ in range(-(-count // len(pool)))])[:count]
+    return picks.view(np.float16).astype(np.float32)
+
+
+def _rounding_values(rng, count):
+    """fp32 values that are no fp16 values, inside the fp16 normal range: a random fp16 normal below 65504 as the lower neighbour
+    (either parity) plus one of ROUNDING_TAILS; the first entries sit at the two ends of the range"""
+    h = rng.integers(0x0400, 0x7BFF, count).astype(np.uint16)
+    tails = ROUNDING_TAILS[rng.integers(0, len(ROUNDING_TAILS), count)]
+    ends = [(0x0400, 0x1000), (0x0401, 0x1000), (0x0400, 0x0001), (0x7BFE, 0x1000), (0x7BFD, 0x1000), (0x7BFE, 0x1FFF), (0x7BFF, 0x0FFF)]
+    for k, (hh, tt) in enumerate(ends[:count]):
+        h[k], tails[k] = hh, tt
+    bits = h.view(np.float16).astype(np.float32).view(np.uint32) | tails
+    sign = rng.integers(0, 2, count).astype(np.uint32)
+    sign[:len(ends)] = 0   # (-65504 is the image's sentinel)
+    bits |= sign << np.uint32(31)
+    return bits.view(np.float32)
+
+
+def _record(rng, binary, bs, scalars, beyond):
+    rec = np.zeros(binary * 12 + 8, np.uint32)
+    on = rng.integers(0, 2, (binary, bs * bs))
+    bits = rec[:binary * 12].reshape(binary, 12)
+    for c in range(binary):
+        cells = np.flatnonzero(on[c])
+        np.bitwise_or.at(bits[c], cells >> 5, np.uint32(1) << (cells & 31).astype(np.uint32))
+    if beyond:   # every bit at or beyond the board's last cell, up to the end of the twelfth word
+        cells = np.arange(bs * bs, 12 * 32)
+        for c in range(binary):
+            np.bitwise_or.at(bits[c], cells >> 5, np.uint32(1) << (cells & 31).astype(np.uint32))
+    rec[binary * 12:] = np.asarray(scalars, np.float32).view(np.uint32)
+    return rec
+
+
+class PackDraw:
+    """The inputs of one case on one draw ("placement" | "rounding"): planes [n][cin][board^2] on the NN grid, or records
+    [nrec][binary*12 + 8] (record r of a symmetry case has the board of the slots that name it)."""
+
+    def __init__(self, c, draw):
+        rng = np.random.default_rng([5150, PACK_CASES.index(c), int(draw == "rounding")])
+        n, B = len(c.cbsz), c.board
+        self.planes = self.records = None
+        if c.form == "planes":
+            self.planes = np.empty((n, c.cin, B, B), np.float32)
+            self.planes[:] = F16_OFF_BOARD.view(np.float16).astype(np.float32) if c.fp16 or draw == "rounding" else F32_OFF_BOARD
+            for j, bs in enumerate(c.cbsz):
+                count = c.cin * bs * bs
+                if draw == "rounding":
+                    v = _rounding_values(rng, count)
+                elif c.fp16:
+                    v = _f16_normals(rng, count)
+                else:   # distinct fp32 values that are mostly no fp16 values: k / 256, k = 1 .. count in a shuffled order, signs mixed
+                    v = ((rng.permutation(count) + 1) / 256.0 * rng.choice((-1.0, 1.0), count)).astype(np.float32)
+                self.planes[j, :, :bs, :bs] = v.reshape(c.cin, bs, bs)
+            self.planes = self.planes.reshape(n, c.cin, B * B)
+            return
+        sizes = list(c.cbsz) if c.form == "bits" else [c.cbsz[c.src.index(r)] if r in c.src else 2 for r in range(c.nrec)]
+        recs = []
+        for bs in sizes:   # eight distinct scalars per record, the slots past cin - binary included
+            scal = _rounding_values(rng, 8) if draw == "rounding" else (_f16_normals(rng, 8) if c.fp16 else ((rng.permutation(8) + 1) / 256.0 * (1 + rng.integers(0, 999))).astype(np.float32))
+            recs.append(_record(rng, c.binary, bs, scal, c.beyond))
+        self.records = np.stack(recs)
+
+
+@functools.lru_cache(maxsize=None)
+def pack_draw(c, draw):
+    return PackDraw(c, draw)
+
+
+def pack_reference(c, draw, sentinel, **kw):
+    """pack_image_ref of the case on the draw (kw: a defect, or other inputs in place of the draw's)"""
+    from _kref import pack_image_ref
+    D = pack_draw(c, draw)
+    perm, bsz = pack_order(c)
+    args = dict(planes=D.planes, records=D.records, binary=c.binary, src=c.src, symm=c.symm, perm=None if c.perm is None else perm, n0=c.n0, ns=c.ns,
+                guard_rows=PACK_GUARD_ROWS, split=c.split)
+    args.update(kw)
+    return pack_image_ref(c.fp16, bsz, c.board, c.cin, sentinel, **args)
+
+
+def planes_of_records(records, binary, cbsz, cin, board):
+    """the NN-grid planes [n][cin][board^2] that record j of board cbsz[j] stands for (off-board cells 0)"""
+    from _kref import record_bits
+    out = np.zeros((len(cbsz), cin, board, board), np.float32)
+    for j, bs in enumerate(cbsz):
+        out[j, :binary, :bs, :bs] = record_bits(records[j], binary, np.arange(bs * bs)).reshape(binary, bs, bs)
+        out[j, binary:, :bs, :bs] = records[j][binary * 12:binary * 12 + cin - binary].view(np.float32)[:, None, None]
+    return out.reshape(len(cbsz), cin, board * board)

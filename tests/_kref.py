@@ -246,3 +246,83 @@ def assert_localised(got, exp, delta, what):
                                     list(zip(*wrong))[:8])
         assert np.array_equal(g.astype(np.float64) - e, d), (what, "sample", i, "an output moved by another amount than the input under the tap")
     return n_pred
+
+
+# ---- the input stage (test_gpu_input.py): planes or packed records -> the input convolution's NHWC image
+PACK_DEFECTS = ("swap_xy", "sample_stride_on_grid", "grid_stride_on_sample", "lost_last_cell", "perm_backwards", "map_ignored", "symm_bit_1",
+                "symm_bit_2", "symm_bit_4", "pad_nonzero", "scalar_neighbour", "round_toward_zero")
+
+
+def f16_toward_zero(a):
+    """float32 -> the fp16 value next to it toward zero, as float32 (the defect "round_toward_zero"; normal range only)"""
+    a = np.asarray(a, np.float32)
+    return (a.view(np.uint32) & np.uint32(0xFFFFE000)).view(np.float32)
+
+
+def record_bits(rec, binary, cells):
+    """bit `cells[...]` of every bit plane of a packed record (uint32 [binary*12 + 8]) -> float32 [binary][len(cells)]; a cell past
+    the twelve words reads 0"""
+    bits = np.asarray(rec, np.uint32)[:binary * 12].reshape(binary, 12)
+    cells = np.asarray(cells)
+    inside = cells < 12 * 32
+    c = np.where(inside, cells, 0)
+    return (((bits[:, c >> 5] >> (c & 31).astype(np.uint32)) & 1) * inside).astype(np.float32)
+
+
+def pack_image_ref(fp16, bsz, max_board, cin, sentinel, planes=None, records=None, binary=0, src=None, symm=None, perm=None, n0=0, ns=None,
+                   guard_rows=0, split=1, defect=None):
+    """What an input-stage kernel leaves in a sentinel-filled image: float32 [n * max_board^2 + guard_rows][cs], cs = cin rounded
+    up to 32.  bsz [n]: the board of DEVICE sample i, which shows the caller's slot j = perm[i] (None: i).  Row p = y*bs + x of
+    slot i, channel c < cin:
+        planes [n][cin][max_board^2] (the NN grid)   planes[j][c][y*max_board + x]
+        records [.][binary*12 + 8]                   c < binary: bit p of plane c of record j (with symm: record src[j], bit
+                                                     symm_index(bs, symm[j])[p]); else the record's scalar c - binary
+    rounded to fp16 (nearest even) for the fp16 engine; channels [cin, cs) are +0; rows >= bs*bs, the slots outside [n0, n0 + ns)
+    and the guard keep the sentinel.  defect: one of PACK_DEFECTS, the image a kernel with that mistake would leave (split: the
+    workgroups per sample, for "lost_last_cell")."""
+    assert defect is None or defect in PACK_DEFECTS, defect
+    n, B2, cs = len(bsz), max_board * max_board, (cin + 31) // 32 * 32
+    ns = n - n0 if ns is None else ns
+    img = np.full((n * B2 + guard_rows, cs), sentinel, np.float32)
+    perm = np.arange(n) if perm is None else np.asarray(perm)
+    if defect == "perm_backwards":
+        perm = np.argsort(perm)
+    if symm is not None:
+        from _ensemble import symm_index
+    for i in range(n0, n0 + ns):
+        bs, j = int(bsz[i]), int(perm[i])
+        y, x = np.divmod(np.arange(bs * bs), bs)
+        if defect == "swap_xy":
+            y, x = x, y
+        rows = np.zeros((bs * bs, cs), np.float32)
+        if planes is not None:
+            cells = y * (bs if defect == "sample_stride_on_grid" else max_board) + x
+            rows[:, :cin] = np.asarray(planes[j], np.float32).reshape(cin, B2)[:, cells].T
+        else:
+            r, cells = j, y * bs + x
+            if symm is not None:
+                r = j if src is None or defect == "map_ignored" else int(src[j])
+                s = int(symm[j])
+                if defect and defect.startswith("symm_bit_"):
+                    s &= ~int(defect[-1])
+                cells = symm_index(bs, s)[cells]
+            if defect == "grid_stride_on_sample":
+                ty, tx = np.divmod(cells, bs)
+                cells = ty * max_board + tx
+            rec = np.asarray(records[r % len(records)], np.uint32)
+            rows[:, :binary] = record_bits(rec, binary, cells).T
+            scal = rec[binary * 12:binary * 12 + 8].view(np.float32)
+            for c in range(binary, cin):
+                rows[:, c] = scal[min(7, c - binary + 1) if defect == "scalar_neighbour" else c - binary]
+        if fp16:
+            rows[:, :cin] = f16_toward_zero(rows[:, :cin]) if defect == "round_toward_zero" else rows[:, :cin].astype(np.float16).astype(np.float32)
+        if defect == "pad_nonzero" and cin < cs:
+            rows[:, cin] = 1.0
+        if defect == "lost_last_cell":
+            per = (bs * bs + split - 1) // split
+            for part in range(split):
+                pend = min(bs * bs, (part + 1) * per)
+                if pend > part * per:
+                    rows[pend - 1] = sentinel
+        img[i * B2:i * B2 + bs * bs] = rows
+    return img

@@ -147,3 +147,31 @@ def tower_run(spec, D, chain=1, max_board=MAX_BOARD):
     assert lib.sayuri_hip_test_last_tower_run(_lib.ip(report)) == 0
     return TowerRun(rc, [split(y[l * per:(l + 1) * per], spec.bsz, spec.C) for l in range(spec.L)], lib.sayuri_hip_test_last_se_form(),
                     tuple(int(v) for v in report))
+
+
+# sayuri_hip_test_last_pack: the input-stage kernel that ran
+PACK_KERNELS = ("chunked", "flat", "bits", "symm")
+PACK_TAPS = ("sayuri_hip_test_pack_input", "sayuri_hip_test_last_pack")
+Pack = collections.namedtuple("Pack", "rc image guard kernel cs split passes")  # image [n][max_board^2][cs], guard [guard_rows][cs], as stored
+
+
+def pack_input(fp16, bsz, cin, sentinel, planes=None, records=None, binary=0, src=None, symm=None, n_records=0, perm=None, n0=0, ns=None, stage_batch=0,
+               in_place=False, guard_rows=0, max_board=MAX_BOARD):
+    """One input-stage kernel on host data, chosen and launched by the engine's own code.  bsz: the board of every DEVICE sample;
+    perm: the caller's slot of each (None: no table).  planes [n][cin][max_board^2], or records (uint32 [.][binary*12 + 8]) read
+    by slot, or -- symm given -- by the record map src (None: the identity) under symm.  stage_batch > 0: the geometry (and the
+    map) go through the staging kernels from a ring laid out for that batch size; in_place: the records stay in pinned host
+    memory.  The whole image and guard_rows rows behind it start as `sentinel` and come back raw."""
+    lib, n = _lib.hip(), len(bsz)
+    cs = (cin + 31) // 32 * 32
+    out = np.full((n * max_board * max_board + guard_rows, cs), np.nan, np.float32)
+    rec = None if records is None else np.ascontiguousarray(records, np.uint32)
+    rc = lib.sayuri_hip_test_pack_input(0, int(fp16), n, _i(bsz), max_board, cin, _f(planes), None if rec is None else rec.ctypes.data,
+                                        n_records or (0 if rec is None else len(rec)), binary, None if src is None else _i(src),
+                                        None if symm is None else _i(symm), None if perm is None else _i(perm), n0, n - n0 if ns is None else ns,
+                                        stage_batch, int(in_place), float(sentinel), guard_rows, _lib.fp(out))
+    report = np.zeros(4, np.int32)
+    assert lib.sayuri_hip_test_last_pack(_lib.ip(report)) == 0
+    k = int(report[0])
+    return Pack(rc, out[:n * max_board * max_board].reshape(n, max_board * max_board, cs), out[n * max_board * max_board:],
+                PACK_KERNELS[k] if 0 <= k < 4 else None, int(report[1]), int(report[2]), int(report[3]))
