@@ -60,6 +60,11 @@ void* sayuri_pipe_raw(void* pipe);                          /* as NetworkForward
 int sayuri_pipe_weights_version(void* pipe);
 int sayuri_pipe_eval(void* pipe, int mode, int gpu, int n, const float* planes, const int* board_sizes,
                      const float* komi, const int* offsets, float* out);
+/* group requests (HipForwardPipe::ForwardGroup): n packable positions of ONE caller as one call, sent without waiting for
+ * other callers; arguments and packing of sayuri_pipe_eval (mode 2), one ForwardGroup call from the calling thread */
+int sayuri_pipe_accepts_group(void* pipe);
+int sayuri_pipe_group_eval(void* pipe, int n, const float* planes, const int* board_sizes, const float* komi,
+                           const int* offsets, float* out);
 int sayuri_pipe_netbench(void* pipe, int threads, double seconds, int board, double* evals_per_sec, long* total);
 void sayuri_pipe_pump_times(void* pipe, double* out8, long* batches, long* evals);
 
@@ -100,9 +105,18 @@ unsigned long sayuri_engine_net_queries(void* net);
 /* NetworkOptions::device_ensemble (option "device_ensemble", default 1): kAverage as one ensemble request of a pipe that
  * accepts them, or as eight evaluations in a row; the result is the same bit for bit */
 void sayuri_engine_net_set_device_ensemble(void* net, int on);
+/* NetworkOptions::group_forward (option "group_forward", default 1): the evaluations of one round of a search with
+ * playouts_in_flight > 1 as one group request of a pipe that accepts them, or one by one; same results bit for bit */
+void sayuri_engine_net_set_group_forward(void* net, int on);
 void sayuri_engine_net_output(void* net, void* game, int ensemble, int symmetry, float temperature, int use_cache,
                               uint64_t seed, float* out /* [2N+9] */);
+/* NULL (message in sayuri_engine_last_error) when an option is refused, e.g. playouts_in_flight outside 1..64 */
 void* sayuri_engine_search_new(void* game, void* net, const char* options);
+/* option playouts_in_flight = K > 1: out8 = rounds, leaves evaluated, largest group, collisions, in flight now (virtual-loss
+ * counters + pending nodes over the tree: 0 outside a computation), K, descents answered at once (terminal / cache), 0 */
+void sayuri_engine_search_flight_stats(void* search, long* out8);
+/* wall seconds the rounds spent collecting leaves, waiting for their evaluation, applying the results */
+void sayuri_engine_search_round_seconds(void* search, double* out3);
 void sayuri_engine_search_free(void* search);
 void sayuri_engine_search_seed(void* search, uint64_t caller_seed, uint64_t playout_seed);
 void sayuri_engine_search_computation(void* search, void* game, int playouts, int tag, int* ints16, float* floats8,

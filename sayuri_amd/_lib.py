@@ -162,6 +162,8 @@ def host() -> ctypes.CDLL:
         lib.sayuri_pipe_reconstruct.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         lib.sayuri_pipe_eval.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p,
                                          c_int_p, c_float_p, c_int_p, c_float_p]
+        lib.sayuri_pipe_accepts_group.argtypes = [ctypes.c_void_p]
+        lib.sayuri_pipe_group_eval.argtypes = [ctypes.c_void_p, ctypes.c_int, c_float_p, c_int_p, c_float_p, c_int_p, c_float_p]
         lib.sayuri_pipe_pump_times.restype = None
         lib.sayuri_pipe_pump_times.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long)]

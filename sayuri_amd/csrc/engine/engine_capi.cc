@@ -99,6 +99,8 @@ void Export(const GameState& g, const ComputationResult& r, int* ints, float* fl
     }
 }
 
+thread_local std::string g_engine_err;
+
 } // namespace
 
 extern "C" {
@@ -139,10 +141,26 @@ void sayuri_engine_net_output(void* n, void* game, int ensemble, int symmetry, f
     s[8] = r.score_error;
 }
 
+// NetworkOptions::group_forward after construction (the option "group_forward=0/1" sets it at construction)
+void sayuri_engine_net_set_group_forward(void* n, int on) { static_cast<Network*>(n)->SetGroupForward(on != 0); }
+
+// NULL with the message in sayuri_engine_last_error() when the options are refused
 void* sayuri_engine_search_new(void* game, void* net, const char* options) {
-    EngineOptions opt;
-    opt.Parse(options ? options : "");
-    return new Search(*static_cast<GameState*>(game), *static_cast<Network*>(net), opt.search);
+    try {
+        EngineOptions opt;
+        opt.Parse(options ? options : "");
+        return new Search(*static_cast<GameState*>(game), *static_cast<Network*>(net), opt.search);
+    } catch (const std::exception& e) {
+        g_engine_err = e.what();
+        return nullptr;
+    }
+}
+// Search::FlightStats: rounds, leaves evaluated, largest group, collisions, in flight now, K, direct results, 0
+void sayuri_engine_search_flight_stats(void* s, long* out8) { static_cast<Search*>(s)->FlightStats(out8); }
+// Search::round_seconds: seconds spent collecting, evaluating, applying
+void sayuri_engine_search_round_seconds(void* s, double* out3) {
+    const double* v = static_cast<Search*>(s)->round_seconds();
+    out3[0] = v[0]; out3[1] = v[1]; out3[2] = v[2];
 }
 void sayuri_engine_search_free(void* s) { delete static_cast<Search*>(s); }
 void sayuri_engine_search_seed(void* s, std::uint64_t caller_seed, std::uint64_t playout_seed) {
@@ -170,7 +188,6 @@ void sayuri_engine_search_update_territory_helper(void* s) { static_cast<Search*
 // Self-play on a forward pipe (raw = sayuri_pipe_raw(handle); NULL = the dummy random-output backend).
 // stats[10] = games_started, games_done, moves, playouts, nn_queries, cache_lookups, cache_hits, records,
 // chunks_saved, 0.  Returns 0, or -1 with the message in sayuri_engine_last_error().
-static thread_local std::string g_engine_err;
 const char* sayuri_engine_last_error() { return g_engine_err.c_str(); }
 namespace {
 constexpr int kStatSlots = 20;

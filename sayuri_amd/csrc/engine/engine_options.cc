@@ -27,6 +27,12 @@ void EngineOptions::Parse(const std::string& text) {
         OPT_INT("batch_size", s.batch_size);
         OPT_INT("playouts", s.playouts);
         OPT_INT("virtual_loss_count", s.virtual_loss_count);
+        else if (k == "playouts_in_flight") {
+            const int flight = std::stoi(v);
+            if (flight < 1 || flight > kMaxPlayoutsInFlight)
+                throw std::invalid_argument("playouts_in_flight must be in 1.." + std::to_string(kMaxPlayoutsInFlight) + ", got " + v);
+            s.playouts_in_flight = flight;
+        }
         OPT_INT("random_min_visits", s.random_min_visits);
         OPT_FLT("random_min_ratio", s.random_min_ratio);
         OPT_FLT("random_moves_factor", s.random_moves_factor);
@@ -76,6 +82,7 @@ void EngineOptions::Parse(const std::string& text) {
         OPT_BOOL("early_symm_cache", network.early_symm_cache);
         OPT_BOOL("packed_inputs", network.packed_inputs);
         OPT_BOOL("device_ensemble", network.device_ensemble);
+        OPT_BOOL("group_forward", network.group_forward);
         else if (k == "cache_memory_mib") network.cache_memory_mib = static_cast<size_t>(std::stol(v));
         else if (k == "policy_buffer_offset") network.default_policy_offset = static_cast<PolicyBufferOffset>(std::stoi(v));
         OPT_INT("num_games", selfplay.num_games);

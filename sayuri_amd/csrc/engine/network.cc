@@ -235,6 +235,67 @@ Network::Result Network::GetOutput(const GameState& state, Ensemble ensemble, Qu
     return result;
 }
 
+bool Network::BeginOutput(const GameState& state, Ensemble ensemble, Query query, Rng& rng, PendingOutput* rec) {
+    if (ensemble == kAverage) {  // eight evaluations of its own, never cached: not part of a group
+        rec->result = GetOutput(state, ensemble, query, rng);
+        return true;
+    }
+    if (ensemble == kDirect) {
+        if (query.symmetry < 0 || query.symmetry >= SymmetryTables::kCount) query.symmetry = SymmetryTables::kIdentity;
+    } else {
+        query.symmetry = static_cast<int>(rng.Below(SymmetryTables::kCount));
+    }
+    if (opt_.no_cache) query.read_cache = query.write_cache = false;
+    if (query.read_cache && ProbeCache(state, rec->result)) {
+        ActivatePolicy(rec->result, query.temperature);
+        return true;
+    }
+    rec->query = query;
+    rec->symmetry = query.symmetry;
+    rec->hash = state.GetHash();
+    const PolicyBufferOffset offset = (query.offset == PolicyBufferOffset::kDefault) ? opt_.default_policy_offset : query.offset;
+    if (UsesPacked()) {
+        Encoder::Packed(state, query.symmetry, version_, &rec->planes);
+        rec->planes.offset = static_cast<int>(offset);
+        rec->input.reset();
+    } else {
+        rec->input = std::make_unique<InputData>();
+        InputData& in = *rec->input;
+        in.board_size = state.GetBoardSize();
+        in.side_to_move = state.GetToMove();
+        in.komi = state.GetKomi();
+        Encoder::Planes(state, query.symmetry, version_, in.planes.data());
+        in.offset = offset;
+    }
+    return false;
+}
+
+void Network::FinishOutputs(PendingOutput* const* recs, int n, Rng& rng) {
+    if (n <= 0) return;
+    const bool packed = recs[0]->input == nullptr;  // (every record of one facade took the same route)
+    if (packed && opt_.group_forward && pipe_->AcceptsGroup()) {
+        std::vector<sayuri_host::PackedPlanes> planes(static_cast<size_t>(n));
+        std::vector<Result> raw(static_cast<size_t>(n));
+        for (int i = 0; i < n; ++i) planes[static_cast<size_t>(i)] = recs[i]->planes;
+        pipe_->ForwardGroup(planes.data(), n, raw.data());
+        for (int i = 0; i < n; ++i) recs[i]->result = raw[static_cast<size_t>(i)];
+    } else {
+        for (int i = 0; i < n; ++i) {
+            if (packed) recs[i]->result = pipe_->ForwardPacked(recs[i]->planes);
+            else if (Valid()) recs[i]->result = pipe_->Forward(*recs[i]->input);
+            else recs[i]->result = DummyForward(*recs[i]->input, rng);
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        PendingOutput& r = *recs[i];
+        if (Valid()) num_queries_.fetch_add(1, std::memory_order_relaxed);
+        TransformResult(r.result, r.symmetry);
+        if (r.query.write_cache) cache_.Insert(r.hash, r.result); // stored before the policy softmax
+        ActivatePolicy(r.result, r.query.temperature);
+        r.input.reset();
+    }
+}
+
 void Network::TransformResult(Result& result, int symmetry) {
     const int bs = result.board_size, n = bs * bs;
     const SymmetryTables& t = SymmetryTables::Get();

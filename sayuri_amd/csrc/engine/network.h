@@ -88,6 +88,8 @@ struct NetworkOptions {
     bool packed_inputs{true};  // compact planes (packed_planes.h) when the pipe takes them; false = 43 fp32 planes as the reference
     bool device_ensemble{true};  // kAverage as ONE ensemble request when the pipe takes them (AcceptsEnsemble): one encode, one
                                  // trip, the symmetries expanded on the device; false = eight evaluations in a row.  Same result.
+    bool group_forward{true};    // FinishOutputs sends a round's evaluations as ONE group request when the pipe takes them
+                                 // (AcceptsGroup); false = one by one, in begin order.  Same results.
 };
 
 class Network {
@@ -99,6 +101,22 @@ public:
     void Initialize(std::shared_ptr<NetworkForwardPipe> pipe, int weights_version, const NetworkOptions& opt);
     bool Valid() const { return pipe_ && pipe_->Valid(); }
     Result GetOutput(const GameState& state, Ensemble ensemble, Query query, Rng& rng); // network.cc:237-291
+    // GetOutput in two steps, for a caller that begins several evaluations and finishes them together (the tree search
+    // with playouts_in_flight > 1).  BeginOutput chooses the symmetry (kRandom draws from `rng` here, in begin order) and
+    // probes the cache: true = rec->result is final; false = the record holds the encoded position and waits for
+    // FinishOutputs, which evaluates all records handed to it -- one ForwardGroup when the pipe accepts groups, else one
+    // by one -- and then, in the order given, post-processes each as GetOutput does (TransformResult, cache insert before
+    // the policy softmax, ActivatePolicy).  rec->result has the bits GetOutput gives for that state and symmetry alone.
+    struct PendingOutput {
+        Result result;
+        Query query;
+        int symmetry{0};
+        std::uint64_t hash{0};
+        sayuri_host::PackedPlanes planes;   // the compact route (the pipe takes packed planes) ...
+        std::unique_ptr<InputData> input;   // ... or the 43 fp32 planes
+    };
+    bool BeginOutput(const GameState& state, Ensemble ensemble, Query query, Rng& rng, PendingOutput* rec);
+    void FinishOutputs(PendingOutput* const* recs, int n, Rng& rng);
     int GetVertexWithPolicy(const GameState& state, float temperature, bool allow_pass, Rng& rng); // :431-468
     size_t SetCacheSize(size_t mib); // network.cc:102-122
     void ClearCache() { cache_.Clear(); }
@@ -107,6 +125,7 @@ public:
     PolicyBufferOffset GetDefaultPolicyOffset() const { return opt_.default_policy_offset; }
     int GetVersion() const { return version_; }
     void SetDeviceEnsemble(bool on) { opt_.device_ensemble = on; }
+    void SetGroupForward(bool on) { opt_.group_forward = on; }
     const ResultCache& cache() const { return cache_; }
     NetworkForwardPipe* pipe() const { return pipe_.get(); }
 
@@ -115,6 +134,7 @@ public:
 
 private:
     Result GetOutputInternal(const GameState& state, int symmetry, PolicyBufferOffset offset, Rng& rng);
+    bool UsesPacked() const { return Valid() && opt_.packed_inputs && pipe_->AcceptsPacked(); }
     Result GetAverage(const GameState& state, const Query& query, Rng& rng);
     bool ProbeCache(const GameState& state, Result& result); // network.cc:197-235
     Result DummyForward(const InputData& inputs, Rng& rng) const; // network.cc:144-165

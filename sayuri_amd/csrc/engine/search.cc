@@ -1,6 +1,7 @@
 #include "search.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -142,6 +143,134 @@ void Search::PlaySimulation(GameState& state, Node* node, int depth, PlayoutResu
 }
 
 // ---------------------------------------------------------------------------------------------
+// Several playouts in flight (search.h).  Descend is PlaySimulation unrolled into a loop that remembers its path: the same
+// steps in the same order, with the evaluation of an expandable node begun instead of waited for.
+bool Search::Descend(std::unique_ptr<Leaf>& leaf) {
+    if (!leaf) leaf = std::make_unique<Leaf>();
+    std::vector<Node*>& path = leaf->path;
+    GameState& state = leaf->state;
+    path.clear();
+    state = root_state_;
+    PlayoutResult result;
+    Node* node = root_.get();
+    for (int depth = 0;; ++depth) {
+        path.push_back(node);
+        node->IncrementInFlight();
+        const bool end_by_passes = state.GetPasses() >= 2;
+        const int scoring = state.GetScoringRule();
+        if (end_by_passes) {
+            if (scoring == kAreaScoring) {
+                GameOverEvals(state, result);
+            } else {
+                while (state.GetLastMove() == kPassMove) state.UndoMove();
+                const float komi = state.GetKomi();
+                const float offset = state.GetPenaltyOffset(kAreaScoring, kTerritoryScoring);
+                state.SetRule(kAreaScoring);
+                state.SetKomi(komi + offset);
+            }
+        }
+        if (node->IsPending()) {
+            // an earlier descent of this round waits for this node's evaluation: nothing to add (the reference's
+            // AcquireExpanding fails for the second thread, node.cc:173)
+            flight_collisions_ += 1;
+            break;
+        }
+        if (node->Expandable()) {
+            const int last_move = state.GetLastMove();
+            if (end_by_passes && scoring == kAreaScoring) {
+                if (result.valid) node->SetTerminal(&result.evals);
+            } else if (last_move != kPassMove && state.IsSuperko()) {
+                node->Invalidate();
+            } else if (network_.BeginOutput(state, Network::kRandom, node->ExpandQuery(network_, false), playout_rng_, &leaf->eval)) {
+                NodeEvals evals{};  // answered from the cache: expanded at once
+                if (node->BuildChildren(leaf->eval.result, state, evals, false)) {
+                    result.valid = true;
+                    result.evals = evals;
+                }
+            } else {
+                node->MarkPending();
+                return true;
+            }
+        }
+        if (!node->HasChildren() || result.valid) break;
+        const int color = state.GetToMove();
+        node = node->DescentSelectChild(color, depth == 0, playout_rng_);
+        state.PlayMove(node->GetVertex(), color);
+    }
+    if (result.valid) flight_direct_ += 1;
+    BackUp(path, result);
+    return false;
+}
+
+void Search::BackUp(const std::vector<Node*>& path, const PlayoutResult& result) {
+    for (auto it = path.rbegin(); it != path.rend(); ++it) {
+        if (result.valid) (*it)->Update(&result.evals);
+        (*it)->DecrementInFlight();
+    }
+    if (result.valid) {
+        playouts_ += 1;
+        total_playouts_.fetch_add(1, std::memory_order_relaxed);
+    }
+}
+
+void Search::RunRound(int cap, int tag) {
+    // collect: at most K descents, and never more leaves than the cap has room for
+    using Clock = std::chrono::steady_clock;
+    auto seconds = [](Clock::duration d) { return std::chrono::duration<double>(d).count(); };
+    const auto t0 = Clock::now();
+    const int flight = active_->playouts_in_flight;
+    for (int attempt = 0; attempt < flight && GetPlayoutsLeft(cap, tag) > static_cast<int>(round_.size()); ++attempt) {
+        if (Descend(spare_leaf_)) round_.push_back(std::move(spare_leaf_));
+    }
+    const auto t1 = Clock::now();
+    round_seconds_[0] += seconds(t1 - t0);
+    if (round_.empty()) return;
+    // evaluate: one request for the round's leaves
+    std::vector<Network::PendingOutput*> recs;
+    for (auto& leaf : round_) recs.push_back(&leaf->eval);
+    try {
+        network_.FinishOutputs(recs.data(), static_cast<int>(recs.size()), playout_rng_);
+    } catch (...) {
+        // the evaluation failed (the pipe's batch did): the tree goes back to what it was before the round
+        for (auto& leaf : round_) {
+            leaf->path.back()->ClearPending();
+            BackUp(leaf->path, PlayoutResult{});
+        }
+        round_.clear();
+        throw;
+    }
+    // apply, in collection order
+    const auto t2 = Clock::now();
+    round_seconds_[1] += seconds(t2 - t1);
+    for (auto& leaf : round_) {
+        PlayoutResult result;
+        NodeEvals evals{};
+        if (leaf->path.back()->BuildChildren(leaf->eval.result, leaf->state, evals, false)) {
+            result.valid = true;
+            result.evals = evals;
+        }
+        BackUp(leaf->path, result);
+    }
+    flight_rounds_ += 1;
+    flight_leaves_ += static_cast<long>(round_.size());
+    flight_largest_ = std::max(flight_largest_, static_cast<long>(round_.size()));
+    if (!spare_leaf_) spare_leaf_ = std::move(round_.back());
+    round_.clear();
+    round_seconds_[2] += seconds(Clock::now() - t2);
+}
+
+void Search::FlightStats(long out[8]) const {
+    out[0] = flight_rounds_;
+    out[1] = flight_leaves_;
+    out[2] = flight_largest_;
+    out[3] = flight_collisions_;
+    out[4] = root_ ? root_->CountInFlight() : 0;
+    out[5] = active_->playouts_in_flight;
+    out[6] = flight_direct_;
+    out[7] = 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 void Search::PrepareParam() {
     active_->recent_expected_black_score = root_->GetFinalScore(kBlack);
     active_->board_size = root_state_.GetBoardSize();
@@ -272,13 +401,18 @@ ComputationResult Search::Computation(int playouts, int tag) {
         single_candidate_searches_ += 1;
         last_single_candidate_ = true;
     }
+    const bool rounds = active_->playouts_in_flight > 1;
     while (running) {
-        GameState fork = root_state_;
-        PlayoutResult pr;
-        PlaySimulation(fork, root_.get(), 0, pr);
-        if (pr.valid) {
-            playouts_ += 1;
-            total_playouts_.fetch_add(1, std::memory_order_relaxed);
+        if (rounds) {
+            RunRound(playouts, tag);  // (every leaf it collected is applied when it returns: the rules below see a clean tree)
+        } else {
+            GameState fork = root_state_;
+            PlayoutResult pr;
+            PlaySimulation(fork, root_.get(), 0, pr);
+            if (pr.valid) {
+                playouts_ += 1;
+                total_playouts_.fetch_add(1, std::memory_order_relaxed);
+            }
         }
         if (AchieveCap(playouts, tag)) running = false;
         else if (abort_ && abort_->load(std::memory_order_relaxed)) running = false;

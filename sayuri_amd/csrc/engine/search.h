@@ -9,6 +9,14 @@
 // Randomness: the reference draws from two thread-local generators -- the calling thread's (root expansion,
 // Dirichlet noise, move pickers) and the search worker's (symmetry of each playout's evaluation).  The same
 // split is kept as two explicit streams so that a fixed-seed search reproduces the reference's moves.
+//
+// Several playouts in flight (option playouts_in_flight = K > 1): still one thread and no timers.  Computation runs
+// ROUNDS: up to K descents from the root, each leaving a virtual loss on the nodes it passes and ending at a leaf whose
+// evaluation is begun (Network::BeginOutput) and which stays pending; one Network::FinishOutputs for the round's leaves
+// -- one group request of the pipe, one device batch; then, in collection order, the children are built and the values
+// backed up.  The reference reaches the same batches with K threads inside the tree (search.cc:56-137); here the
+// order of everything is fixed by the seeds, so a search with K > 1 is as reproducible as one with K = 1.  K = 1 is
+// the loop over PlaySimulation it always was.
 #pragma once
 
 #include <atomic>
@@ -92,6 +100,14 @@ public:
     // searches that ended at once because the root had a single candidate (the reference stops those from a
     // polling thread, after a timing-dependent handful of playouts: search.cc:352-386, 1423-1441)
     int single_candidate_searches() const { return single_candidate_searches_; }
+    // Rounds of playouts in flight since construction: out[0] rounds that evaluated at least one leaf, [1] leaves evaluated
+    // in them, [2] the largest group, [3] collisions (a descent that ended at a leaf already pending in its round),
+    // [4] in flight NOW -- virtual-loss counters plus pending nodes over the whole tree, 0 outside Computation --,
+    // [5] K, [6] descents that ended with a result at once (terminal, cache hit), [7] 0.
+    void FlightStats(long out[8]) const;
+    // where the rounds' wall time went, seconds since construction: collecting (descents, encoding), waiting for the round's
+    // evaluation (Network::FinishOutputs: the device round trip and the post-processing), applying (children, back-up)
+    const double* round_seconds() const { return round_seconds_; }
     // indices (within the current training buffer, counting discarded samples) of the samples such searches produced
     const std::vector<int>& single_candidate_records() const { return single_candidate_records_; }
 
@@ -101,6 +117,15 @@ private:
         NodeEvals evals{};
     };
     void PlaySimulation(GameState& state, Node* node, int depth, PlayoutResult& result); // search.cc:60-137
+    // playouts_in_flight > 1
+    struct Leaf {  // a descent that ended at a node whose evaluation is on its way
+        std::vector<Node*> path;  // root .. leaf, each carrying this descent's virtual loss
+        GameState state;          // the position at the leaf
+        Network::PendingOutput eval;
+    };
+    void RunRound(int cap, int tag);
+    bool Descend(std::unique_ptr<Leaf>& leaf);  // true: the descent queued *leaf; false: it ended with a result, or invalid
+    void BackUp(const std::vector<Node*>& path, const PlayoutResult& result);
     void GameOverEvals(GameState& state, PlayoutResult& result);                        // search.h:33-60
     void TryRecoverOwnershipMap(GameState& state, std::vector<int>& ownership);          // search.h:62-105
     void PrepareRootNode(ComputationResult& result, int tag);                            // search.cc:139-181
@@ -136,6 +161,10 @@ private:
     int playouts_{0};
     std::atomic<size_t> total_playouts_{0};  // read by the self-play statistics while the game thread searches
     int single_candidate_searches_{0};
+    std::vector<std::unique_ptr<Leaf>> round_;  // the open round's leaves, in collection order
+    std::unique_ptr<Leaf> spare_leaf_;          // (a descent that queues nothing hands its Leaf back: no allocation per attempt)
+    double round_seconds_[3] = {0, 0, 0};
+    long flight_rounds_{0}, flight_leaves_{0}, flight_largest_{0}, flight_collisions_{0}, flight_direct_{0};
     bool last_single_candidate_{false};
     std::vector<int> single_candidate_records_;
     std::string last_comment_;

@@ -11,11 +11,14 @@
 
 namespace sayuri_engine {
 
+constexpr int kMaxPlayoutsInFlight = 64;  // SearchParams::playouts_in_flight is 1 .. this
+
 struct SearchParams {
     int threads{1};
     int batch_size{1};
     int playouts{400};
     int virtual_loss_count{1};
+    int playouts_in_flight{1};  // K: descents one thread keeps open in one tree, their leaves evaluated as one group (search.h)
     int random_min_visits{1};
     float random_min_ratio{0.f};
     float random_moves_factor{0.f};

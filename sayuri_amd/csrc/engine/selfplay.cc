@@ -74,6 +74,10 @@ float AdjustKomiToHalf(float komi) {
 // ---------------------------------------------------------------------------------------------
 SelfplayEngine::SelfplayEngine(std::shared_ptr<NetworkForwardPipe> pipe, int weights_version, const EngineOptions& opt)
     : opt_(opt) {
+    // self-play gets its batches from concurrent games, and its games may be fibers (ForwardGroup is for OS threads)
+    if (opt_.search.playouts_in_flight > 1)
+        throw std::runtime_error("self-play runs one playout per tree at a time: playouts_in_flight = " +
+                                 std::to_string(opt_.search.playouts_in_flight) + " is for a search of one tree (think, Computation, benchmark)");
     network_.Initialize(std::move(pipe), weights_version, opt_.network);
     const int games = std::max(1, opt_.selfplay.parallel_games);
     std::uint64_t seed = opt_.selfplay.seed;

@@ -29,15 +29,18 @@ inline float SafeLog(float v) { return static_cast<float>(std::log(static_cast<d
 
 // ---------------------------------------------------------------------------------------------
 // Expansion.
-Network::Result Node::GetNetOutput(Network& network, GameState& state, bool is_root, Rng& rng) {
+Network::Query Node::ExpandQuery(const Network& network, bool is_root) const {
     // The root always reads the normal policy head and bypasses the cache (its temperature may differ);
     // inner nodes use the default head through the cache.  (SetOffset overrides the SetCache flag, as in the
     // reference's builder chain, node.cc:136-146.)
     const bool default_is_normal = network.GetDefaultPolicyOffset() == PolicyBufferOffset::kNormal;
     const auto offset = is_root ? PolicyBufferOffset::kNormal : PolicyBufferOffset::kDefault;
     const float temp = is_root ? param_->root_policy_temp : param_->policy_temp;
-    const auto query = Network::Query::Get().SetTemperature(temp).SetCache(!default_is_normal).SetOffset(offset);
-    return network.GetOutput(state, Network::kRandom, query, rng);
+    return Network::Query::Get().SetTemperature(temp).SetCache(!default_is_normal).SetOffset(offset);
+}
+
+Network::Result Node::GetNetOutput(Network& network, GameState& state, bool is_root, Rng& rng) {
+    return network.GetOutput(state, Network::kRandom, ExpandQuery(network, is_root), rng);
 }
 
 void Node::FillNodeEvalsFromNet(const Network::Result& net, NodeEvals& evals, int color) const {
@@ -54,9 +57,14 @@ void Node::FillNodeEvalsFromNet(const Network::Result& net, NodeEvals& evals, in
 }
 
 bool Node::ExpandChildren(Network& network, GameState& state, NodeEvals& evals, bool is_root, Rng& rng) {
-    if (expanded_) return false;
-    color_ = static_cast<std::uint8_t>(state.GetToMove());
+    if (expand_state_ != kInitial) return false;
     const Network::Result net = GetNetOutput(network, state, is_root, rng);
+    return BuildChildren(net, state, evals, is_root);
+}
+
+bool Node::BuildChildren(const Network::Result& net, GameState& state, NodeEvals& evals, bool is_root) {
+    if (expand_state_ == kExpanded) return false;
+    color_ = static_cast<std::uint8_t>(state.GetToMove());
 
     FillNodeEvalsFromNet(net, evals, color_);
     black_wl_ = evals.black_wl;
@@ -157,7 +165,7 @@ bool Node::ExpandChildren(Network& network, GameState& state, NodeEvals& evals, 
             sorted_n_ = static_cast<std::int16_t>(list_n);
         }
     }
-    expanded_ = true;
+    expand_state_ = kExpanded;
     return true;
 }
 
@@ -176,11 +184,11 @@ void Node::SortTail() const {
 }
 
 bool Node::SetTerminal(const NodeEvals* evals) {
-    if (expanded_) return false;
+    if (expand_state_ != kInitial) return false;
     color_ = kWall; // no children
     black_wl_ = evals->black_wl;
     black_fs_ = evals->black_final_score;
-    expanded_ = true;
+    expand_state_ = kExpanded;
     return true;
 }
 
@@ -448,10 +456,15 @@ Node* Node::PuctSelectChild(int color, bool is_root) {
         if (n) {
             const int visits = n->GetVisits();
             if (visits > 0) {
-                // win/loss plus score utility steer the descent
+                // win/loss (with the virtual losses of the playouts in flight below it) plus score utility steer the descent
                 q = n->GetWL(color, true) + n->GetScoreEval(color);
                 const int forced = GetForcedVisits(psa, children_visits, is_root);
                 if (forced - visits > 0) q = static_cast<float>(q + (forced - visits) * 1e6);
+            } else if (n->GetVirtualLoss() > 0) {
+                // never visited, and a playout of this round ends in it (a pending leaf): its virtual losses are all the
+                // statistics it has, a certain loss.  (The reference gives a node under expansion min(fpu, -1), node.cc:546-549,
+                // whatever virtual_loss_count is; here virtual_loss_count = 0 leaves it at the FPU.)
+                q = n->GetWL(color, true);
             }
             cpuct *= GetDynamicCpuctFactor(n, visits, children_visits);
             denom += visits;
@@ -505,9 +518,9 @@ Node* Node::PuctSelectChild(int color, bool is_root) {
         if (!bare_seen && hi < size) consider(children_[static_cast<size_t>(hi)], best, best_value);  // the best of the bare edges beyond
     }
     // SAYURI_PUCT_CHECK=1 (tests): the reference's loop over ALL children must pick the same edge, and the two conditions the
-    // pruning rests on must hold -- children sorted by policy, nothing but bare edges beyond inflated_hi_.  For ONE playout per
-    // tree at a time (this engine's own search): with several threads in one tree (virtual loss) the statistics may change
-    // between the two loops and the comparison can abort a correct search.
+    // pruning rests on must hold -- children sorted by policy, nothing but bare edges beyond inflated_hi_.  For ONE thread per
+    // tree (this engine's own search, whatever playouts_in_flight is): with several threads in one tree the statistics may
+    // change between the two loops and the comparison can abort a correct search.
     static const bool check = std::getenv("SAYURI_PUCT_CHECK") != nullptr;
     if (check) {
         EnsureSorted();
@@ -570,9 +583,14 @@ float Node::GetFinalScore(int color) const {
     return color == kBlack ? static_cast<float>(score) : static_cast<float>(0.0f - score);
 }
 
-float Node::GetWL(int color, bool /*use_virtual_loss*/) const {
-    // one playout walks a tree at a time, so no virtual loss is ever pending below the node being scored
-    const double eval = acc_black_wl_ / GetVisits();
+float Node::GetWL(int color, bool use_virtual_loss) const {
+    // node.cc:1265-1286: every playout in flight below the node counts as virtual_loss_count visits that the side to move
+    // lost (none is in flight with playouts_in_flight = 1: the plain mean)
+    const int virtual_loss = use_virtual_loss ? GetVirtualLoss() : 0;
+    const int visits = GetVisits() + virtual_loss;
+    double acc = acc_black_wl_;
+    if (color == kWhite && use_virtual_loss) acc += static_cast<double>(virtual_loss);
+    const double eval = acc / visits;
     return color == kBlack ? static_cast<float>(eval) : static_cast<float>(1.0f - eval);
 }
 
@@ -666,6 +684,13 @@ std::unique_ptr<Node> Node::PopChild(int vertex) {
         }
     }
     return nullptr;
+}
+
+long Node::CountInFlight() const {
+    long n = in_flight_ + (expand_state_ == kPending ? 1 : 0);
+    for (const auto& c : children_)
+        if (c.Get()) n += c.Get()->CountInFlight();
+    return n;
 }
 
 size_t Node::CountNodes() const {

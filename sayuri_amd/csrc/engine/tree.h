@@ -7,6 +7,9 @@
 // one game and is walked by one playout at a time (the engine gets its parallelism from thousands of
 // concurrent games, not from threads inside a tree), so there are no atomics, spin-waits or tagged
 // pointers here, and children hold their node in a plain unique_ptr that is filled on first descent.
+// With playouts_in_flight > 1 the one thread that owns the tree has several descents open at a time (search.h):
+// a node counts them (the reference's running_threads_), the selection sees them as virtual losses, and a leaf
+// whose evaluation is on its way is `pending` until the round's results build its children.
 #pragma once
 
 #include <array>
@@ -62,6 +65,14 @@ public:
 
     // node.cc:127-357
     bool ExpandChildren(Network& network, GameState& state, NodeEvals& evals, bool is_root, Rng& rng);
+    // ExpandChildren in two steps, for a caller that evaluates several leaves together: the query the node's evaluation is
+    // asked with, and the children built from its answer (everything ExpandChildren does behind the evaluation).  Between
+    // the two the node is pending: MarkPending, undone by ClearPending when the evaluation failed.
+    Network::Query ExpandQuery(const Network& network, bool is_root) const;
+    bool BuildChildren(const Network::Result& net, GameState& state, NodeEvals& evals, bool is_root);
+    void MarkPending() { expand_state_ = kPending; }
+    void ClearPending() { if (expand_state_ == kPending) expand_state_ = kInitial; }
+    bool IsPending() const { return expand_state_ == kPending; }
     bool PrepareRootNode(Network& network, GameState& state, NodeEvals& evals, Rng& rng); // node.cc:30-66
     bool SetTerminal(const NodeEvals* evals);
 
@@ -82,11 +93,19 @@ public:
 
     EdgeList& GetChildren() { EnsureSorted(); return children_; }
     const EdgeList& GetChildren() const { EnsureSorted(); return children_; }
-    bool HasChildren() const { return expanded_ && color_ != sayuri_go::kWall; }
+    bool HasChildren() const { return expand_state_ == kExpanded && color_ != sayuri_go::kWall; }
     Node* GetChild(int vertex);
     std::unique_ptr<Node> PopChild(int vertex);
 
     int GetVisits() const { return visits_; }
+    // playouts in flight through this node (node.cc:1316-1322 IncrementThreads / DecrementThreads; plain integers: one
+    // thread owns the tree) and what the selection charges for them (node.cc:1222)
+    void IncrementInFlight() { ++in_flight_; }
+    void DecrementInFlight() { --in_flight_; }
+    int GetInFlight() const { return in_flight_; }
+    int GetVirtualLoss() const { return param_->virtual_loss_count * in_flight_; }
+    // counters and pending nodes of the subtree: 0 whenever no round is open
+    long CountInFlight() const;
     int GetVertex() const { return vertex_; }
     float GetPolicy() const { return policy_; }
     float GetNetWL(int color) const { return color == sayuri_go::kBlack ? black_wl_ : 1.0f - black_wl_; }
@@ -104,7 +123,7 @@ public:
     float GetScoreStddev() const;
     int GetChildrenVisits() const;
 
-    bool Expandable() const { return !expanded_; }
+    bool Expandable() const { return expand_state_ == kInitial; }
     bool IsActive() const { return status_ == kActive; }
     bool IsValid() const { return status_ != kInvalidNode; }
     void Invalidate() { status_ = kInvalidNode; }
@@ -112,6 +131,7 @@ public:
 
 private:
     enum Status : std::uint8_t { kInvalidNode, kPruned, kActive };
+    enum ExpandState : std::uint8_t { kInitial, kPending, kExpanded };  // node.h ExpandState, without kExpanding's spin-wait
 
     Network::Result GetNetOutput(Network& network, GameState& state, bool is_root, Rng& rng);
     void RecomputePolicy(Network& network, GameState& state, NodeEvals& evals, bool is_root, Rng& rng);
@@ -160,9 +180,10 @@ private:
         if (upto > sorted_n_ && sorted_n_ < static_cast<int>(children_.size())) SortTail();
     }
     void SortTail() const;
+    std::uint16_t in_flight_{0};  // (with expand_state_ in what was padding behind a bool: the node keeps its size class)
     std::uint8_t color_{sayuri_go::kWall}; // side to move here; kWall while there are no children
     Status status_{kActive};
-    bool expanded_{false};
+    ExpandState expand_state_{kInitial};
 };
 
 } // namespace sayuri_engine

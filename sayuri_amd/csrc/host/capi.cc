@@ -341,6 +341,51 @@ extern "C" int sayuri_pipe_forward_ensemble(void* hp, const float* planes, int b
     }
 }
 
+// Group requests (HipForwardPipe::ForwardGroup).  sayuri_pipe_group_eval: the arguments and the packing of sayuri_pipe_eval, the
+// planes packable (its mode 2), and ONE ForwardGroup call from the calling thread.
+extern "C" int sayuri_pipe_accepts_group(void* hp) { return static_cast<PipeHandle*>(hp)->pipe->AcceptsGroup() ? 1 : 0; }
+extern "C" int sayuri_pipe_group_eval(void* hp, int n, const float* planes, const int* board_sizes, const float* komi,
+                                      const int* offsets, float* out) {
+    auto* h = static_cast<PipeHandle*>(hp);
+    if (!h || n <= 0 || !planes || !board_sizes || !out) return -1;
+    const int PL = kInputChannels * kNumIntersections, OL = 2 * kNumIntersections + 9;
+    try {
+        const int C = h->weights->input_channels, nbin = PackedPlanes::BinaryPlanes(C);
+        std::vector<PackedPlanes> packed(static_cast<size_t>(n));
+        for (int i = 0; i < n; ++i) {
+            PackedPlanes& pk = packed[static_cast<size_t>(i)];
+            const int bs = board_sizes[i], cells = bs * bs;
+            if (bs < 2 || bs > kBoardSize) throw std::runtime_error("sayuri_pipe_group_eval: bad board size");
+            pk.Clear(nbin);
+            pk.board_size = bs;
+            pk.komi = komi ? komi[i] : 7.5f;
+            pk.offset = offsets ? offsets[i] : 0;
+            for (int c = 0; c < C; ++c) {
+                const float* pl = planes + static_cast<size_t>(i) * PL + static_cast<size_t>(c) * cells;
+                if (c >= nbin) { pk.scalars[c - nbin] = pl[0]; continue; }
+                for (int k = 0; k < cells; ++k)
+                    if (pl[k] != 0.f) pk.Set(c, k);
+            }
+        }
+        std::vector<OutputResult> outs(static_cast<size_t>(n));
+        h->pipe->ForwardGroup(packed.data(), n, outs.data());
+        for (int i = 0; i < n; ++i) {
+            float* o = out + static_cast<size_t>(i) * OL;
+            const OutputResult& r = outs[static_cast<size_t>(i)];
+            std::memcpy(o, r.probabilities.data(), sizeof(float) * kNumIntersections);
+            std::memcpy(o + kNumIntersections, r.ownership.data(), sizeof(float) * kNumIntersections);
+            float* t = o + 2 * kNumIntersections;
+            t[0] = r.pass_probability; t[1] = r.wdl[0]; t[2] = r.wdl[1]; t[3] = r.wdl[2];
+            t[4] = r.stm_winrate; t[5] = r.final_score; t[6] = r.q_error; t[7] = r.score_error;
+            t[8] = static_cast<float>(static_cast<int>(r.offset));
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+
 #include "fiber.h"
 // Ensemble, packed and fp32 requests side by side, from fibers and from OS threads at once (tests/test_ensemble_cpu.py).
 // Request i -- planes [n][43*361] and the other arrays as for sayuri_pipe_eval, packable -- is sent as kind[i]:

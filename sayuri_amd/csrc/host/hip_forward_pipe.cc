@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <exception>
 #include <stdexcept>
 
 #include <linux/futex.h>
@@ -281,8 +282,8 @@ void HipForwardPipe::Trace::Dump() const {
     row("\n[pipe trace] fibers, the game runs again -> its next request:", think);
     row("\n[pipe trace] tail rule (SAYURI_PIPE_TAIL), age of the running batch at the close:", tail);
     row("\n[pipe trace] batch sizes /16:", size);
-    std::fprintf(stderr, "\n[pipe trace] closed: full %ld, idle-wait %ld, 85%%-rule %ld, stray %ld\n", reason[kCloseFull].load(),
-                 reason[kCloseIdleWait].load(), reason[kCloseTail].load(), reason[kCloseStray].load());
+    std::fprintf(stderr, "\n[pipe trace] closed: full %ld, idle-wait %ld, 85%%-rule %ld, stray %ld, group flush %ld\n", reason[kCloseFull].load(),
+                 reason[kCloseIdleWait].load(), reason[kCloseTail].load(), reason[kCloseStray].load(), reason[kCloseFlush].load());
 }
 
 void HipForwardPipe::DestroyGraphs() {
@@ -460,6 +461,9 @@ void HipForwardPipe::FinishBatch(Graph* g, Staging* s, int n) {
     const PumpTimer t{this, kHandOut};
     // the previous batch of this set was handed out at least one batch time ago
     while (s->wakes_done.load(std::memory_order_acquire) < s->fin_count) std::this_thread::yield();
+    // (counted before anybody is told: a caller that has its result sees the batch in the counters)
+    batches_.fetch_add(1, std::memory_order_relaxed);
+    evals_.fetch_add(static_cast<size_t>(std::max(n, s->dev_n)), std::memory_order_relaxed);
     int count = 0, fibers = 0;
     for (int i = 0; i < n; ++i) {
         const Request& r = s->reqs[i];
@@ -476,8 +480,6 @@ void HipForwardPipe::FinishBatch(Graph* g, Staging* s, int n) {
             FutexWakeAll(r.done);
         }
     }
-    batches_.fetch_add(1, std::memory_order_relaxed);
-    evals_.fetch_add(static_cast<size_t>(std::max(n, s->dev_n)), std::memory_order_relaxed);
     s->fin_count = count;
     s->fin_fibers = fibers;
     s->wakes_done.store(0, std::memory_order_relaxed);
@@ -650,7 +652,15 @@ void HipForwardPipe::PumpLoop(Graph* g) {
             continue;
         }
         const unsigned c = s.count();
-        if (c >= WantNow() || (c > 0 && (cfg_.gpu_waittime_ms <= 0 || !running_.load()))) { CloseFillSet(p, kCloseFull); continue; }
+        if (c >= WantNow()) { CloseFillSet(p, kCloseFull); continue; }
+        if (c > 0 && group_filling_.load(std::memory_order_acquire) > 0) {
+            // a ForwardGroup caller is writing its requests (microseconds): the set stays open for them, whatever the rules below say
+            if (p.inflight.size > 0 && OldestIsDone(p)) FinishOldest(p);
+            else std::this_thread::yield();
+            continue;
+        }
+        if (c > 0 && group_flush_.load(std::memory_order_acquire) > 0) { CloseFillSet(p, kCloseFlush); continue; }
+        if (c > 0 && (cfg_.gpu_waittime_ms <= 0 || !running_.load())) { CloseFillSet(p, kCloseFull); continue; }
         if (c == 0 || p.inflight.size > 0) p.timing = false;  // the idle-wait clock runs for a partial set and an idle GPU only
         if (c > 0 && p.inflight.size == 0) {
             // partial batch and an idle GPU: give stragglers gpu_waittime_ms, then send what is there
@@ -670,6 +680,8 @@ void HipForwardPipe::PumpLoop(Graph* g) {
         if (p.inflight.size > 0 && OldestIsDone(p)) { FinishOldest(p); continue; }
         const PumpTimer nap{this, kNap};
         std::unique_lock<std::mutex> lk(g->mu);
+        // (a flush raised since the look above: its caller takes `mu` before it notifies, so it is seen here or it wakes the wait)
+        if (group_flush_.load(std::memory_order_acquire) > 0 && s.count() > 0) continue;
         g->cv.wait_for(lk, std::chrono::microseconds(p.inflight.size > 0 ? 50 : 200));
     }
 }
@@ -746,6 +758,53 @@ bool HipForwardPipe::ForwardEnsemble(const PackedPlanes& identity, OutputResult 
     const bool all = ForwardAny(nullptr, &identity, &out[0], out);
     if (!all) ens_fallbacks_.fetch_add(1, std::memory_order_relaxed);
     return all;
+}
+
+void HipForwardPipe::WakePumps() {
+    for (auto& g : graphs_) {
+        { std::lock_guard<std::mutex> lk(g->mu); }
+        g->cv.notify_one();
+    }
+}
+
+void HipForwardPipe::ForwardGroup(const PackedPlanes* in, int n, OutputResult* out) {
+    if (sayuri_fiber::InFiber())
+        throw std::runtime_error("HipForwardPipe::ForwardGroup is for OS-thread callers: a fiber sends its requests one by one (ForwardPacked)");
+    if (n <= 0) return;
+    if (graphs_.empty()) throw std::runtime_error("HipForwardPipe is not constructed");
+    // everything Reserve and StagePacked would refuse, BEFORE the first slot is taken: a group is sent whole or not at all
+    for (int i = 0; i < n; ++i) {
+        if (in[i].board_size < 2 || in[i].board_size > board_size_) throw std::runtime_error("PackedPlanes board size does not fit the NN board");
+        if (in[i].binary_planes != BinaryPlanes()) throw std::runtime_error("PackedPlanes: binary plane count does not match the network");
+    }
+    bool failed = false;
+    for (int base = 0; base < n;) {
+        const int m = std::min(n - base, std::max(1, static_cast<int>(WantNow())));
+        std::vector<std::atomic<int>> done(static_cast<size_t>(m));
+        int reserved = 0;
+        std::exception_ptr error;
+        group_filling_.fetch_add(1, std::memory_order_acq_rel);
+        try {
+            for (; reserved < m; ++reserved) Reserve(nullptr, &in[base + reserved], &out[base + reserved], &done[static_cast<size_t>(reserved)], false);
+        } catch (...) {  // (the pipe is shutting down) what was reserved is still waited for: the pump writes through these pointers
+            error = std::current_exception();
+        }
+        // the flush goes up before the hold comes down: the pumps see one of the two, never a gap in which the other rules apply
+        group_flush_.fetch_add(1, std::memory_order_acq_rel);
+        group_filling_.fetch_sub(1, std::memory_order_acq_rel);
+        WakePumps();
+        // the pump fills out[] and flips the flags in slot order: the last one first, the others are set by then
+        for (int i = reserved - 1; i >= 0; --i) {
+            std::atomic<int>& d = done[static_cast<size_t>(i)];
+            int st;
+            while ((st = d.load(std::memory_order_acquire)) == 0) FutexWait(&d, 0);
+            failed |= st < 0;
+        }
+        group_flush_.fetch_sub(1, std::memory_order_acq_rel);
+        if (error) std::rethrow_exception(error);
+        if (failed) ThrowBatchFailed();
+        base += m;
+    }
 }
 
 HipForwardPipe::Echo HipForwardPipe::EchoOf(const InputData* input, const PackedPlanes* packed) {

@@ -100,6 +100,14 @@ public:
     bool ForwardEnsemble(const PackedPlanes& identity, OutputResult out[8]) SAYURI_EXT_OVERRIDE;
     size_t num_ensemble_fallbacks() const { return ens_fallbacks_.load(std::memory_order_relaxed); }
 
+    // n >= 1 packed requests of ONE caller (an OS thread: a tree search with several playouts in flight) as one call: out[i] is
+    // what ForwardPacked(in[i]) returns, bit for bit.  The requests take slots like everybody's (other callers may share the
+    // set); the pump leaves the set alone while they are being written and closes it the moment they all are -- a group does
+    // not wait for gpu_waittime_ms or the tail rule, whatever else is going on.  A group larger than the forwarding size goes
+    // out in chunks of that size, one after the other.  Throws when a batch failed (the pipe stays usable), and from a fiber.
+    bool AcceptsGroup() const SAYURI_EXT_OVERRIDE { return true; }
+    void ForwardGroup(const PackedPlanes* in, int n, OutputResult* out) SAYURI_EXT_OVERRIDE;
+
     // batch_forward_pipe.h:27-28.  `inputs` are already re-padded into the NN grid.
     std::vector<OutputResult> BatchForward(int gpu, const std::vector<InputData>& inputs);
 
@@ -189,7 +197,7 @@ private:
     };
 
     struct Pump;  // the pump thread's own state and its two FIFOs (hip_forward_pipe.cc)
-    enum CloseReason { kCloseFull, kCloseIdleWait, kCloseTail, kCloseStray, kCloseReasons };
+    enum CloseReason { kCloseFull, kCloseIdleWait, kCloseTail, kCloseStray, kCloseFlush, kCloseReasons };
     // SAYURI_PIPE_TRACE=1 (read once at construction; a measuring aid, printed to stderr when the graphs are destroyed):
     // when do requests arrive relative to the last finished batch, how full are the batches and why were they closed
     struct Trace {
@@ -249,6 +257,10 @@ private:
     mutable std::atomic<long long> pump_stat_[kPumpCounters] = {};  // nanoseconds, but kPartialBatches: a count
     struct PumpTimer;  // adds its own lifetime to one of them
     std::atomic<int> epoch_parked_{0};  // fibers suspended in Reserve() until a staging set re-opens
+    // ForwardGroup callers that are writing their requests into the fill set (the pumps leave a partial set open meanwhile) and
+    // callers that wait for a group's results (the FLUSH: the pumps close a non-empty fill set at once while it is raised)
+    std::atomic<int> group_filling_{0}, group_flush_{0};
+    void WakePumps();
     Trace trace_;
     // SAYURI_PIPE_TAIL (measuring aid): the fraction of a batch's time after which a partial set is enqueued behind it
     double tail_frac_{0.93};

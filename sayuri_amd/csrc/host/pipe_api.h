@@ -103,6 +103,11 @@ public:
     // caller evaluates the other seven one by one.
     virtual bool AcceptsEnsemble() const { return false; }
     virtual bool ForwardEnsemble(const PackedPlanes&, OutputResult*) { throw std::runtime_error("this pipe does not take ensemble requests"); }
+    // Extension: n >= 1 packed requests of ONE caller as one call (a tree search with several playouts in flight): out[i]
+    // receives what ForwardPacked(in[i]) would return, and the call returns when all n are there.  The pipe does not wait
+    // for other callers' requests before it sends them.
+    virtual bool AcceptsGroup() const { return false; }
+    virtual void ForwardGroup(const PackedPlanes*, int, OutputResult*) { throw std::runtime_error("this pipe does not take group requests"); }
     std::string GetName() const;
     int GetVersion() const;
     std::shared_ptr<DNNWeights> weights_{nullptr};

@@ -167,6 +167,27 @@ class HipForwardPipe:
         """n concurrent blocking Forward() calls through the batching queue."""
         return self._eval(1, planes, board_sizes, komi, offsets)
 
+    def AcceptsGroup(self) -> bool:
+        return bool(_lib.host().sayuri_pipe_accepts_group(self._h))
+
+    def ForwardGroup(self, cases):
+        """cases: (planes, board_size[, komi[, offset]]) per position, packable as for ForwardPacked -> their results in
+        Forward()'s packing, from ONE HipForwardPipe::ForwardGroup call of this thread: the requests go out together, without
+        waiting for other callers or the pipe's timers."""
+        cases = [tuple(c) + (7.5, 0)[len(c) - 2:] for c in cases]
+        n = len(cases)
+        buf = np.zeros((n, PLANES_LEN), np.float32)
+        for i, c in enumerate(cases):
+            flat = np.ascontiguousarray(c[0], np.float32).ravel()
+            buf[i, :flat.size] = flat
+        bsz = np.asarray([c[1] for c in cases], np.int32)
+        km = np.asarray([c[2] for c in cases], np.float32)
+        off = np.asarray([c[3] for c in cases], np.int32)
+        out = np.zeros((n, OUT_LEN), np.float32)
+        if _lib.host().sayuri_pipe_group_eval(self._h, n, _lib.fp(buf), _lib.ip(bsz), _lib.fp(km), _lib.ip(off), _lib.fp(out)):
+            raise RuntimeError(_lib.host().sayuri_host_last_error().decode())
+        return [np.concatenate([out[i, :int(bsz[i]) ** 2], out[i, 361:361 + int(bsz[i]) ** 2], out[i, 722:]]) for i in range(n)]
+
     def AcceptsEnsemble(self) -> bool:
         return bool(_lib.host().sayuri_pipe_accepts_ensemble(self._h))
 

@@ -37,6 +37,9 @@ def lib() -> ctypes.CDLL:
         h.sayuri_engine_net_queries.argtypes = [vp]
         h.sayuri_engine_net_output.argtypes = [vp, vp, ci, ci, cf, ci, u64, vp]
         h.sayuri_engine_net_set_device_ensemble.argtypes = [vp, ci]
+        h.sayuri_engine_net_set_group_forward.argtypes = [vp, ci]
+        h.sayuri_engine_search_flight_stats.argtypes = [vp, vp]
+        h.sayuri_engine_search_round_seconds.argtypes = [vp, vp]
         h.sayuri_engine_search_new.restype = vp
         h.sayuri_engine_search_new.argtypes = [vp, vp, ctypes.c_char_p]
         h.sayuri_engine_search_free.argtypes = [vp]
@@ -103,6 +106,11 @@ class Network:
         created with ensemble=E, or as eight evaluations in a row.  The result is the same, bit for bit."""
         lib().sayuri_engine_net_set_device_ensemble(self._h, int(on))
 
+    def set_group_forward(self, on: bool):
+        """NetworkOptions::group_forward (also the option `group_forward`): the leaves of one round of a search with
+        playouts_in_flight > 1 as one ForwardGroup of the pipe, or one by one.  The results are the same, bit for bit."""
+        lib().sayuri_engine_net_set_group_forward(self._h, int(on))
+
     def output(self, game: Game, ensemble: int = 0, symmetry: int = 0, temperature: float = 1.0, use_cache: bool = False,
                seed: int = 0) -> np.ndarray:
         out = np.zeros(2 * game.n + 9, np.float32)
@@ -114,6 +122,8 @@ class Search:
     def __init__(self, game: Game, network: Network, options: dict | None = None, seeds=(1, 2)):
         self._game, self._net = game, network
         self._h = lib().sayuri_engine_search_new(game._h, network._h, options_text(options or {}))
+        if not self._h:
+            raise ValueError(lib().sayuri_engine_last_error().decode())
         lib().sayuri_engine_search_seed(self._h, seeds[0], seeds[1])
 
     def close(self):
@@ -134,6 +144,21 @@ class Search:
         out.update({k: float(fl[i]) for i, k in enumerate(RESULT_FLOATS)})
         out.update(root_visits=vis, estimated_q=eq, target_policy=tg, ownership=own)
         return out
+
+    FLIGHT_STATS = ("rounds", "leaves", "largest_group", "collisions", "in_flight", "playouts_in_flight", "direct")
+
+    def flight_stats(self) -> dict:
+        """Option playouts_in_flight = K > 1 (csrc/engine/search.h): rounds that evaluated leaves, leaves evaluated, the
+        largest group, collisions, what is in flight now (0 outside a computation), K, descents answered at once."""
+        out = (ctypes.c_long * 8)()
+        lib().sayuri_engine_search_flight_stats(self._h, out)
+        return {k: int(out[i]) for i, k in enumerate(self.FLIGHT_STATS)}
+
+    def round_seconds(self) -> dict:
+        """Wall seconds the rounds spent collecting leaves (descents, encoding), waiting for their evaluation, applying it."""
+        out = (ctypes.c_double * 3)()
+        lib().sayuri_engine_search_round_seconds(self._h, out)
+        return {"collect": out[0], "evaluate": out[1], "apply": out[2]}
 
     def selfplay_move(self, tag: int = 0) -> int:
         return int(lib().sayuri_engine_search_selfplay_move(self._h, self._game._h, tag))
