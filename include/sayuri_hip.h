@@ -95,9 +95,11 @@ sayuri_hip_ctx* sayuri_hip_create(int device, const sayuri_hip_netdesc* desc, in
  * (1 to 16 positions): every fp16 3x3 tower convolution whose padded output channels are a multiple of 64 is cut into many
  * small workgroups (csrc/hip/conv_split.h: 64 channels x a strip of board rows each), so that a lone board's layer runs on tens
  * of CUs instead of one to three.  Such a context takes that route for EVERY batch, whatever its size (a position's result
- * does not depend on its batch), has no persistent tower launch (sayuri_hip_tower_state = 0), runs no chains and runs its SE
- * units as separate kernels; its outputs are those of a default context created under SAYURI_TOWER=0 SAYURI_SE_FUSED=0
- * SAYURI_SE_SPLIT=0, bit for bit.  Full batches are what the default context is for (INTEGRATION.md says where they cross).
+ * does not depend on its batch), has no persistent tower launch (sayuri_hip_tower_state = 0), runs no chains and runs every SE
+ * unit as ONE launch behind its convolution (se_unit_kernel, csrc/hip/small_ops.h: the bits of se_pool / se_fc / se_scale, which
+ * SAYURI_SE_ONE=0 runs instead, as do batches of more than 85 full 19x19 boards on 256 channels and 51 on 384); its outputs are
+ * those of a default context created under SAYURI_TOWER=0 SAYURI_SE_FUSED=0 SAYURI_SE_SPLIT=0, bit for bit.  Full batches are what
+ * the default context is for (INTEGRATION.md says where they cross).
  * fp16 engine only: flags != 0 with use_fp16 == 0 returns NULL with a message.  sayuri_hip_create is create_ex(..., 0) --
  * unless SAYURI_LATENCY=1 is set in the environment, which gives an fp16 context the flag (for callers that cannot pass one).
  * SAYURI_LATENCY_SPLIT=n forces n strips per board instead of the engine's choice (measurements, tests). */
@@ -253,7 +255,8 @@ int sayuri_hip_test_last_conv_kind(void);
 /* One squeeze-and-excitation unit through the se_pool / se_fc / se_scale kernels (reference SEUnit::Forward,
  * src/neural/blas/se_unit.cc:70-128): x, res (or NULL), y are [n][channels][bs*bs] like sayuri_hip_test_conv's tensors,
  * w1 [se_size][3*channels], b1 [se_size], w2 [2*channels][se_size], b2 [2*channels];
- * gate (or NULL) receives [n][2*channels] = sigmoid(gamma) | beta, i.e. GlobalPooling<false> + both FullyConnects. */
+ * gate (or NULL) receives [n][2*channels] = sigmoid(gamma) | beta, i.e. GlobalPooling<false> + both FullyConnects.
+ * Honours SAYURI_SE_ONE, read per call: =1 runs the unit as one launch (se_unit_kernel), same bits. */
 int sayuri_hip_test_se_unit(int device, int use_fp16, int n, const int* board_sizes, int max_board, int channels,
                             int se_size, int act, const float* x, const float* res, const float* w1, const float* b1,
                             const float* w2, const float* b2, float* y, float* gate);

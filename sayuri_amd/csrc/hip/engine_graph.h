@@ -1279,9 +1279,33 @@ private:
         });
     }
 
-    // the unit on the samples [n0, n0 + ns) of the batch
-    int se_unit(Fwd& f, const FcLayerDev& sq, const FcLayerDev& ex, T* x, const T* res, int C, int cs, int act, int n0, int ns) {
+    // The unit on the samples [n0, n0 + ns) of the batch.  The one place that chooses its form: se_pool / se_fc / se_scale, or
+    // one launch (se_unit_kernel) of `parts` workgroups per sample (se_unit_parts: a piece per thread within one round of the
+    // CUs).  The rule decides speed only: the bits are the same either way.  SAYURI_SE_ONE=1 / 0 force a form; unset, a latency
+    // context takes the one launch when the scale phase of every workgroup is a single pass (kScaleUnroll x kSeFcThreads
+    // pieces) -- measured in DESIGN.md Kernel 1g: with more passes on one CU the unit loses more than its two launches save.
+    // For full 19x19 boards that is up to 85 boards on 256 channels (11552 pieces, parts >= 3) and up to 51 on 384 (17328
+    // pieces, parts >= 5); a call that cannot split (parts == 1: no residual, a sample range) qualifies up to 11x11 / 9x9.
+    // Several workgroups per sample cannot write x (a sibling still pools it): `into_res`, when the caller passes it, allows
+    // the result in the residual's buffer `res_rw` instead and says whether it went there; the forward's whole batch only.
+    int se_unit(Fwd& f, const FcLayerDev& sq, const FcLayerDev& ex, T* x, const T* res, int C, int cs, int act, int n0, int ns,
+                T* res_rw = nullptr, bool* into_res = nullptr) {
         const double px = geom_.off[n0 + ns] - geom_.off[n0];
+        if (into_res) *into_res = false;
+        if (flags_.se_one < 0 ? flags_.latency : flags_.se_one != 0) {
+            int max_pieces = 0;
+            for (int i = n0; i < n0 + ns; ++i) max_pieces = std::max(max_pieces, geom_.bsz[i] * geom_.bsz[i] * (cs / ElemTraits<T>::kPieceElems));
+            const bool may_split = into_res && res_rw && res_rw == res && n0 == 0 && ns == geom_.n;
+            const int parts = may_split ? se_unit_parts(max_pieces, ns) : 1;
+            const bool one_pass = (max_pieces + parts - 1) / parts <= kScaleUnroll * kSeFcThreads;
+            if (flags_.se_one > 0 || one_pass) {
+                const int rc = se_unit_one_launch<T>(f.stream, dgeom(f.io), px, (const T*)x, res, parts > 1 ? res_rw : x, parts, f.io.gate, sq.dev(),
+                                                     ex.dev(), C, cs, act, n0, ns,
+                                                     [&](const char* name, double flops, double bytes, auto&& launch) { return timed(f, name, flops, bytes, launch); });
+                if (rc == 0 && parts > 1) *into_res = true;
+                if (rc != 1) return rc;
+            }
+        }
         return se_unit_launches<T>(f.stream, dgeom(f.io), px, x, res, f.io.separt, f.io.gate, sq.dev(), ex.dev(), C, cs, act, n0, ns,
                                    [&](const char* name, double flops, double bytes, auto&& launch) { return timed(f, name, flops, bytes, launch); });
     }
@@ -1299,7 +1323,12 @@ private:
     //   `in` (packed input)       pack_bits / pack_input         input conv's cin_s (64) never inside the forward (kept to its end)
     //   pool buffers x, y, t0...  the convolution they are `out` the tower's cout_s      as soon as the layer that reads them is
     //                             of (epilogue, own tile's rows)  (256 / 384 / 128)        appended: give() -> take(), SAME stride only
+    //   ... the block's skip      se_unit_kernel with parts > 1   the same                 never by the unit: it becomes the block's
+    //                             (the unit's result, in place                             output (forward_graph's in_skip) and the
+    //                             of the residual it has read)                             convolution's buffer y goes back instead
     //   io.separt, io.gate        se_pool / se_fc, per sample     per-sample records      per sample, inside its chain
+    //                             (se_unit_kernel: io.gate only,
+    //                             its partials stay in LDS)
     //   se_xchg (384-ch SE)       the sibling channel tiles       per (tile, channel tile) next SE layer (tagged with the layer's epoch)
     //   io.prob ... io.own        the heads kernel                per sample              by the ticket's next submit
     //
@@ -1471,13 +1500,19 @@ private:
                 x = s2;
                 skip = s2;
             }
+            // skip == x in every block type here (the mixer sets both to s2), so a result left in the skip's buffer is a result in x
+            bool in_skip = false;  // the one-launch SE unit left the block's output in the skip's buffer (se_unit)
             if (se && !se_done) {
                 if (se_unit(f, fc(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE)), fc(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE)), buf[y], buf[skip], C, csC,
-                            act, f.n0, f.ns))
+                            act, f.n0, f.ns, buf[skip], &in_skip))
                     return -1;
             }
-            f.give(x);
-            x = y;
+            if (in_skip) {
+                f.give(y);
+            } else {
+                f.give(x);
+                x = y;
+            }
         }
         return heads(f, x);
     }

@@ -140,6 +140,7 @@ static void enable_big_lds_glds() {
 //   SAYURI_LATENCY=1              a plain sayuri_hip_create of the fp16 engine makes a latency context (sayuri_hip_create_ex's
 //                                 SAYURI_HIP_LATENCY; read in engine.hip, not here: the taps do not see it)
 //   SAYURI_LATENCY_SPLIT=n        latency context: n strips per board in every split convolution instead of the engine's choice
+//   SAYURI_SE_ONE=0 | 1           the SE unit outside a convolution as se_pool / se_fc / se_scale everywhere | as one launch everywhere
 // The other switches are described at their fields below.
 struct ConvOverride {
     bool v0 = false, no_board = false;
@@ -150,8 +151,13 @@ struct EngineFlags {
     bool tower = true, se_fused = true, heads_fused = true, arith = true;
     bool latency = false;              // a latency context (sayuri_hip_create_ex): every fp16 3x3 layer whose padded output channels are a
                                        // multiple of 64 runs as many small workgroups (conv_split.h), whatever the batch size; no persistent
-                                       // launch, no chains, SE units as separate kernels (for_latency())
+                                       // launch, no chains, every SE unit as one launch behind its convolution (for_latency(), se_one,
+                                       // Engine::se_unit())
     int latency_split = 0;             // SAYURI_LATENCY_SPLIT=n: strips per board (0: split_auto)
+    int se_one = -1;                   // SAYURI_SE_ONE: an SE unit that runs as kernels of its own is ONE launch (se_unit_kernel, small_ops.h)
+                                       // instead of se_pool / se_fc / se_scale -- unset (-1): in a latency context (Engine::se_unit()'s
+                                       // rule); 0: nowhere; 1: wherever Engine::se_unit() or the se_unit tap would run the three.  Same
+                                       // bits either way.
     bool tower_chain = true;           // a layer of the persistent run fetches the next layer's first weight group (SAYURI_TOWER_CHAIN=0: off)
     bool tower_gen_epi = true;         // Mish layers of the run take the generated epilogue (SAYURI_TOWER_GEN_EPI=0: the compiled one)
     bool se_split = true;              // SAYURI_SE_SPLIT=0: SE units of layers split over several channel tiles (384 channels) as
@@ -195,6 +201,7 @@ struct EngineFlags {
         f.tower_sync = getenv("SAYURI_TOWER_SYNC") != nullptr;
         f.fwdstat = getenv("SAYURI_HIP_FWDSTAT") != nullptr;
         if (const char* e = getenv("SAYURI_LATENCY_SPLIT")) f.latency_split = std::max(0, atoi(e));
+        if (const char* e = getenv("SAYURI_SE_ONE")) f.se_one = atoi(e) != 0;
 #ifdef SAYURI_EXPERIMENTS
         if (const char* e = getenv("SAYURI_BOARD_KOT")) f.board_kot = atoi(e);
         if (const char* e = getenv("SAYURI_ACT_OVERRIDE")) f.act_override = atoi(e);
@@ -204,8 +211,9 @@ struct EngineFlags {
 #endif
         return f;
     }
-    // The same switches for a latency context: one launch per layer, one chain, and the SE unit always as se_pool / se_fc /
-    // se_scale behind a split convolution -- the fused forms pool fp32 accumulators that no single workgroup holds here.
+    // The same switches for a latency context: one launch per layer, one chain, and the SE unit always as kernels of its own
+    // behind a split convolution -- the fused forms pool fp32 accumulators that no single workgroup holds here -- which
+    // Engine::se_unit() runs as one launch (se_unit_kernel) unless SAYURI_SE_ONE=0 asks for se_pool / se_fc / se_scale.
     EngineFlags for_latency() const {
         EngineFlags f = *this;
         f.latency = true;
@@ -215,8 +223,12 @@ struct EngineFlags {
 };
 
 // allow > 64 KiB of dynamic LDS on the current device
+template <typename T> static void se_unit_enable_lds() {
+    (void)hipFuncSetAttribute((const void*)&se_unit_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+}
 template <typename T> static void enable_big_lds() {
     register_all_convs<T>();
+    se_unit_enable_lds<T>();
     for (const auto& e : ConvKernelTable<T>::entries())
         (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
 }
@@ -754,6 +766,22 @@ static int se_unit_launches(hipStream_t s, const BatchGeom& g, double px, T* x, 
     const dim3 grid((g.slot_pix * (cs / EPP) + 256 * kScaleUnroll - 1) / (256 * kScaleUnroll), ns);
     return run("se_scale", 3.0 * px * C, sizeof(T) * px * C * 3,
                [&] { hipLaunchKernelGGL(se_scale_kernel<T>, grid, dim3(256), 0, s, (const T*)x, res, x, (const float*)gate, g, C, cs, act, n0); });
+}
+// The same unit as ONE launch (se_unit_kernel, small_ops.h: `parts` workgroups per sample, the three kernels as their phases,
+// the same bits), same run() protocol; its row carries the flops and bytes of the three rows it replaces.  The result goes to
+// `out`: x itself (in place) when parts == 1, else the residual's buffer -- never x, see the kernel.  Returns 1 when the form
+// does not apply -- more than 256 pieces per pixel row, its LDS does not fit, or parts > 1 without such a buffer -- and the
+// caller runs se_unit_launches.
+template <typename T, typename Run>
+static int se_unit_one_launch(hipStream_t s, const BatchGeom& g, double px, const T* x, const T* res, T* out, int parts, float* gate,
+                              const FcDev& sq, const FcDev& ex, int C, int cs, int act, int n0, int ns, Run&& run) {
+    constexpr int EPP = ElemTraits<T>::kPieceElems;
+    const size_t smem = se_unit_lds(C, cs, sq.out, EPP);
+    if (cs / EPP > 256 || smem > kMaxLds || parts < 1 || (parts > 1 && (out == x || out != res))) return 1;
+    const double fc = (double)sq.in * sq.out + (double)ex.in * ex.out;
+    return run("se_unit", 5.0 * px * C + 2.0 * ns * fc, sizeof(T) * px * C * 4 + 4.0 * ns * fc, [&] {
+        hipLaunchKernelGGL(se_unit_kernel<T>, dim3(ns * parts), dim3(kSeFcThreads), smem, s, x, res, out, gate, g, C, cs, sq, ex, act, n0, parts);
+    });
 }
 
 // ------------------------------------------------------------------ the input stage (small_ops.h), shared by the engine and its tap

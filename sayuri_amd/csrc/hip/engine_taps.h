@@ -218,12 +218,24 @@ static int test_se_unit_impl(int device, int n, const int* board_sizes, int max_
     float* separt = (float*)A.alloc(sizeof(float) * (size_t)n * kSeSplit * 2 * cs);
     float* gate = (float*)A.alloc(sizeof(float) * (size_t)n * 2 * cs);
     if (!dx || (res && !dres) || !dw1 || !dw2 || !db1 || !db2 || !separt || !gate) return fail("test_se_unit: hipMalloc failed");
-    if (se_unit_launches<T>(nullptr, tg.g, tg.hg.total, dx, dres, separt, gate, FcDev{dw1, db1, 3 * C, se}, FcDev{dw2, db2, se, 2 * C}, C, cs, act, 0, n,
-                            [](const char*, double, double, auto&& launch) { launch(); return 0; }))
-        return -1;
+    const FcDev sq{dw1, db1, 3 * C, se}, ex{dw2, db2, se, 2 * C};
+    const auto run = [](const char*, double, double, auto&& launch) { launch(); return 0; };
+    int rc = 1;  // SAYURI_SE_ONE=1 (read per call, as SAYURI_CONV is): the one-launch form where it applies
+    T* dy = dx;  // where the result is: with several workgroups per sample the one launch leaves it in the residual's buffer
+    if (EngineFlags::from_env().se_one == 1) {
+        se_unit_enable_lds<T>();
+        int max_pieces = 0;
+        for (int i = 0; i < n; ++i) max_pieces = std::max(max_pieces, board_sizes[i] * board_sizes[i] * (cs / ElemTraits<T>::kPieceElems));
+        const int parts = dres ? se_unit_parts(max_pieces, n) : 1;
+        rc = se_unit_one_launch<T>(nullptr, tg.g, tg.hg.total, (const T*)dx, (const T*)dres, parts > 1 ? dres : dx, parts, gate, sq, ex, C, cs, act, 0, n,
+                                   run);
+        if (rc == 0 && parts > 1) dy = dres;
+    }
+    if (rc == 1) rc = se_unit_launches<T>(nullptr, tg.g, tg.hg.total, dx, dres, separt, gate, sq, ex, C, cs, act, 0, n, run);
+    if (rc) return -1;
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
-    if (nhwc_to_nchw(tg, dx, C, cs, y)) return -1;
+    if (nhwc_to_nchw(tg, dy, C, cs, y)) return -1;
     if (gate_out) {
         std::vector<float> hg((size_t)n * 2 * cs);
         HIP_OK(hipMemcpy(hg.data(), gate, hg.size() * 4, hipMemcpyDeviceToHost));

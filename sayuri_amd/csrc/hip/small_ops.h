@@ -302,14 +302,13 @@ __device__ __forceinline__ void block_pool(const T* __restrict__ x, int npix, in
 // se_scale_kernel: out = act(gamma * x + beta + residual), 16-byte loads/stores, no index search
 constexpr int kSeSplit = 4;
 
+// One pixel slice of one sample's pooling: 256 threads (`tid`) sum / max the pixels [sp * per, (sp + 1) * per) of `xn` (the
+// sample's rows) with 16-byte loads, fold their rows through `red0` / `red1` ([256 * EPP] floats each, this slice's own) and
+// leave the per-channel partials in dst[2][cs].  Every thread of the workgroup calls it (one barrier inside).
 template <typename T>
-__global__ __launch_bounds__(256) void se_pool_kernel(const T* __restrict__ x, float* __restrict__ part, BatchGeom g,
-                                                      int cs, int n0 = 0) {  // n0: first sample of the launch
+__device__ __forceinline__ void se_pool_slice(const T* __restrict__ xn, float* red0, float* red1, float* dst, int npix, int cs, int sp,
+                                              int tid) {
     constexpr int EPP = ElemTraits<T>::kPieceElems;
-    __shared__ float red[2][256 * 8 / 8 * 8];  // [sum|max][thread][EPP<=8]
-    const int n = n0 + blockIdx.x / kSeSplit, sp = blockIdx.x % kSeSplit;
-    const int tid = threadIdx.x;
-    const int bs = g.bsz[n], npix = bs * bs;
     const int ppr = cs / EPP;                 // 16-byte pieces per pixel row
     const int prows = 256 / ppr;              // pixel rows handled concurrently (>=1 when cs <= 256*EPP)
     const int piece = tid % ppr, prow = tid / ppr;
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(256) void se_pool_kernel(const T* __restrict__ x, f
 #pragma unroll
     for (int e = 0; e < EPP; ++e) { sum[e] = 0.f; mx[e] = -5000.f; }
     if (prow < prows) {
-        const T* xs = x + (size_t)n * g.slot_pix * cs + piece * EPP;
+        const T* xs = xn + piece * EPP;
 #pragma unroll 4
         for (int p = p0 + prow; p < p1; p += prows) {
             T v[EPP];
@@ -333,40 +332,47 @@ __global__ __launch_bounds__(256) void se_pool_kernel(const T* __restrict__ x, f
         }
     }
 #pragma unroll
-    for (int e = 0; e < EPP; ++e) { red[0][tid * EPP + e] = sum[e]; red[1][tid * EPP + e] = mx[e]; }
+    for (int e = 0; e < EPP; ++e) { red0[tid * EPP + e] = sum[e]; red1[tid * EPP + e] = mx[e]; }
     __syncthreads();
     if (prow == 0 && piece < ppr) {
         for (int q = 1; q < prows; ++q) {
 #pragma unroll
             for (int e = 0; e < EPP; ++e) {
-                sum[e] += red[0][(q * ppr + piece) * EPP + e];
-                mx[e] = fmaxf(mx[e], red[1][(q * ppr + piece) * EPP + e]);
+                sum[e] += red0[(q * ppr + piece) * EPP + e];
+                mx[e] = fmaxf(mx[e], red1[(q * ppr + piece) * EPP + e]);
             }
         }
-        float* dst = part + ((size_t)(n * kSeSplit + sp) * 2) * cs + piece * EPP;
 #pragma unroll
-        for (int e = 0; e < EPP; ++e) { dst[e] = sum[e]; dst[cs + e] = mx[e]; }
+        for (int e = 0; e < EPP; ++e) { dst[piece * EPP + e] = sum[e]; dst[cs + piece * EPP + e] = mx[e]; }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void se_pool_kernel(const T* __restrict__ x, float* __restrict__ part, BatchGeom g,
+                                                      int cs, int n0 = 0) {  // n0: first sample of the launch
+    __shared__ float red[2][256 * 8 / 8 * 8];  // [sum|max][thread][EPP<=8]
+    const int n = n0 + blockIdx.x / kSeSplit, sp = blockIdx.x % kSeSplit;
+    const int bs = g.bsz[n];
+    se_pool_slice<T>(x + (size_t)n * g.slot_pix * cs, red[0], red[1], part + ((size_t)(n * kSeSplit + sp) * 2) * cs, bs * bs, cs, sp,
+                     threadIdx.x);
 }
 
 // kSeFcThreads threads per workgroup: the kernel is a chain of dependent L2 loads per thread (the squeeze FC's 3C rows split over the row
 // groups of the workgroup), so its time is the length of that chain -- 115 rows per thread with 256 threads (27 us for a 384-channel
 // layer), 28 with 1024.
 constexpr int kSeFcThreads = 1024;
-__global__ __launch_bounds__(kSeFcThreads) void se_fc_kernel(const float* __restrict__ part, float* __restrict__ gate,
-                                                    BatchGeom g, int C, int cs, FcDev squeeze, FcDev excite, int act, int n0 = 0) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* pool = (float*)smem;          // [3C]
-    float* mid = pool + 3 * C;           // [se_size]
-    float* scratch = mid + squeeze.out;  // [NT]
+static_assert(kSeFcThreads == kSeSplit * 256, "se_unit_kernel: the FC's workgroup is the pooling's kSeSplit workgroups side by side");
+// One sample's FCs on kSeFcThreads threads: folds the partials part[kSeSplit][2][cs] into (mean, scaled mean, max), squeeze FC,
+// excite FC -> gate[0][c] = sigmoid(gamma), gate[1][c] = beta (channel stride cs, the pads are not written), and the same into
+// `gate2` when the caller keeps a second copy.  pool [3C], mid [squeeze.out], scratch [kSeFcThreads]: LDS.
+__device__ __forceinline__ void se_fc_sample(const float* part, float* gate, float* gate2, float* pool, float* mid, float* scratch, int bs,
+                                             int C, int cs, const FcDev squeeze, const FcDev excite, int act, int tid) {
     constexpr int NT = kSeFcThreads;
-    const int n = n0 + blockIdx.x, tid = threadIdx.x;
-    const int bs = g.bsz[n];
     const float npix = (float)(bs * bs), bd = (float)bs - 14.f;
     for (int c = tid; c < C; c += NT) {
         float s = 0.f, m = -5000.f;
         for (int sp = 0; sp < kSeSplit; ++sp) {
-            const float* src = part + ((size_t)(n * kSeSplit + sp) * 2) * cs;
+            const float* src = part + ((size_t)sp * 2) * cs;
             s += src[c];
             m = fmaxf(m, src[cs + c]);
         }
@@ -410,32 +416,43 @@ __global__ __launch_bounds__(kSeFcThreads) void se_fc_kernel(const float* __rest
         const float* w = excite.wt + o;
 #pragma unroll 16
         for (int i = 0; i < excite.in; ++i) s += mid[i] * w[(size_t)i * excite.out];
-        // gate[n][0][c] = sigmoid(gamma_c), gate[n][1][c] = beta_c; channel stride cs, pads stay 0
-        gate[(size_t)n * 2 * cs + (o < C ? o : cs + (o - C))] = o < C ? 1.0f / (1.0f + fast_exp(-s)) : s;
+        // gate[0][c] = sigmoid(gamma_c), gate[1][c] = beta_c; channel stride cs, pads stay 0
+        const int at = o < C ? o : cs + (o - C);
+        const float v = o < C ? 1.0f / (1.0f + fast_exp(-s)) : s;
+        gate[at] = v;
+        if (gate2) gate2[at] = v;
     }
+}
+
+__global__ __launch_bounds__(kSeFcThreads) void se_fc_kernel(const float* __restrict__ part, float* __restrict__ gate,
+                                                    BatchGeom g, int C, int cs, FcDev squeeze, FcDev excite, int act, int n0 = 0) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* pool = (float*)smem;          // [3C]
+    float* mid = pool + 3 * C;           // [se_size]
+    float* scratch = mid + squeeze.out;  // [NT]
+    const int n = n0 + blockIdx.x;
+    se_fc_sample(part + ((size_t)n * kSeSplit * 2) * cs, gate + (size_t)n * 2 * cs, nullptr, pool, mid, scratch, g.bsz[n], C, cs, squeeze,
+                 excite, act, threadIdx.x);
 }
 
 // out = act(gate_gamma[n][c] * x + beta[n][c] + res).  grid (ceil(slot_pix*ppr / (256*4)), n);
 // each thread owns 4 16-byte pieces (all loads issued before the math).
 constexpr int kScaleUnroll = 4;
+// kScaleUnroll pieces of one sample, `first`, `first + step`, ... of its `total`: xn / rn / on its rows (rn may be null, on may be
+// xn), gm its gate [2][cs] with 0 in the pad channels.
 template <typename T>
-__global__ __launch_bounds__(256) void se_scale_kernel(const T* __restrict__ x, const T* __restrict__ res,
-                                                       T* __restrict__ out, const float* __restrict__ gate,
-                                                       BatchGeom g, int C, int cs, int act, int n0 = 0) {
+__device__ __forceinline__ void se_scale_pieces(const T* xn, const T* rn, T* on, const float* gm, int first, int step, int total, int cs,
+                                                int act) {
     constexpr int EPP = ElemTraits<T>::kPieceElems;
-    const int n = n0 + blockIdx.y;
-    const int bs = g.bsz[n], npix = bs * bs;
-    const int ppr = cs / EPP, total = npix * ppr;
-    const size_t base = (size_t)n * g.slot_pix * cs;
-    const float* gm = gate + (size_t)n * 2 * cs;  // [2][cs], pad channels hold 0
+    const int ppr = cs / EPP;
     uint4 vx[kScaleUnroll], vr[kScaleUnroll];
     int idx[kScaleUnroll];
 #pragma unroll
     for (int u = 0; u < kScaleUnroll; ++u) {
-        idx[u] = (blockIdx.x * kScaleUnroll + u) * 256 + threadIdx.x;
+        idx[u] = first + u * step;
         if (idx[u] < total) {
-            vx[u] = *(const uint4*)(x + base + (size_t)idx[u] * EPP);
-            if (res) vr[u] = *(const uint4*)(res + base + (size_t)idx[u] * EPP);
+            vx[u] = *(const uint4*)(xn + (size_t)idx[u] * EPP);
+            if (rn) vr[u] = *(const uint4*)(rn + (size_t)idx[u] * EPP);
         }
     }
 #pragma unroll
@@ -454,11 +471,74 @@ __global__ __launch_bounds__(256) void se_scale_kernel(const T* __restrict__ x, 
 #pragma unroll
         for (int e = 0; e < EPP; ++e) {
             float v = ga[e] * to_float(px[e]) + be[e];  // pad channels: 0 * 0 + 0
-            if (res) v += to_float(pr[e]);
+            if (rn) v += to_float(pr[e]);
             vo[e] = from_float<T>(activate(v, act));
         }
-        *(uint4*)(out + base + (size_t)idx[u] * EPP) = *(uint4*)vo;
+        *(uint4*)(on + (size_t)idx[u] * EPP) = *(uint4*)vo;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void se_scale_kernel(const T* __restrict__ x, const T* __restrict__ res,
+                                                       T* __restrict__ out, const float* __restrict__ gate,
+                                                       BatchGeom g, int C, int cs, int act, int n0 = 0) {
+    constexpr int EPP = ElemTraits<T>::kPieceElems;
+    const int n = n0 + blockIdx.y;
+    const int bs = g.bsz[n], npix = bs * bs;
+    const size_t base = (size_t)n * g.slot_pix * cs;
+    se_scale_pieces<T>(x + base, res ? res + base : nullptr, out + base, gate + (size_t)n * 2 * cs,  // gate [2][cs], pad channels hold 0
+                       blockIdx.x * kScaleUnroll * 256 + threadIdx.x, 256, npix * (cs / EPP), cs, act);
+}
+
+// ---- SE unit, one launch (a latency context's form; SAYURI_SE_ONE) ------------------------------
+// se_unit_kernel : grid n * parts, kSeFcThreads threads: the three kernels above as three phases of a workgroup, on the sample's
+//                  rows of x.  Each phase is the body of the kernel it replaces -- the same thread -> (slice, piece, pixel row)
+//                  mapping, the same serial sums and folds -- so the outputs carry the bits of the three launches:
+//                    pool   the 1024 threads act as se_pool_kernel's kSeSplit workgroups (tid >> 8 = slice); partials to LDS
+//                    fc     se_fc_kernel's body on the LDS partials; the gate to LDS and (part 0) to `gate` (the tap returns it)
+//                    scale  se_scale_kernel's pieces, kScaleUnroll per thread per pass, gate read from LDS
+//                  `parts` workgroups per sample: EVERY one pools the whole sample and runs both FCs -- the same bits in each,
+//                  nothing is exchanged and no workgroup waits for another -- and scales its own range of the sample's
+//                  pieces, so that a large board's scale phase runs on `parts` CUs instead of one.  With parts > 1 a sibling
+//                  may still pool x while this workgroup scales, so the result must not land in x: out = the residual's
+//                  buffer (a piece of it is read and then written by one thread, and read by nobody else).  parts == 1 may
+//                  run in place (out == x).  LDS (floats, se_unit_lds): part [4][2][cs] | gate [2][cs] | pool [3C] | mid [se]
+//                  | scratch [1024] | red [4][2][256 * EPP] -- 90 KB for 384 fp16 channels: above 64 KB, se_unit_enable_lds.
+static inline size_t se_unit_lds(int C, int cs, int se, int epp) {
+    return sizeof(float) * ((size_t)(kSeSplit * 2 + 2) * cs + (size_t)((3 * C + 3) & ~3) + ((se + 3) & ~3) + kSeFcThreads + (size_t)kSeSplit * 2 * 256 * epp);
+}
+// Workgroups per sample for `ns` samples whose largest has `max_pieces` 16-byte pieces: a piece per thread where the launch
+// stays within one round of the CUs (256), never fewer than one workgroup.
+static inline int se_unit_parts(int max_pieces, int ns) {
+    const int want = (max_pieces + kSeFcThreads - 1) / kSeFcThreads, room = 256 / (ns > 0 ? ns : 1);
+    return std::max(1, std::min(want, room));
+}
+template <typename T>
+__global__ __launch_bounds__(kSeFcThreads) void se_unit_kernel(const T* x, const T* res, T* out, float* __restrict__ gate, BatchGeom g,
+                                                               int C, int cs, FcDev squeeze, FcDev excite, int act, int n0, int parts) {
+    constexpr int EPP = ElemTraits<T>::kPieceElems;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* part = (float*)smem;                          // [kSeSplit][2][cs]
+    float* gl = part + kSeSplit * 2 * cs;                // [2][cs]
+    float* pool = gl + 2 * cs;                           // [3C]
+    float* mid = pool + ((3 * C + 3) & ~3);               // [se_size]
+    float* scratch = mid + ((squeeze.out + 3) & ~3);     // [kSeFcThreads]
+    float* red = scratch + kSeFcThreads;                 // [kSeSplit][2][256 * EPP]
+    const int n = n0 + blockIdx.x / parts, mine = blockIdx.x % parts, tid = threadIdx.x;
+    const int bs = g.bsz[n], npix = bs * bs;
+    const size_t base = (size_t)n * g.slot_pix * cs;
+    // the LDS gate's pad channels [C, cs) of both halves hold 0 as the global one's do (se_scale_pieces: 0 * 0 + 0)
+    for (int c = tid; c < 2 * cs; c += kSeFcThreads) gl[c] = 0.f;
+    const int sp = tid >> 8;
+    se_pool_slice<T>(x + base, red + sp * 2 * 256 * EPP, red + (sp * 2 + 1) * 256 * EPP, part + sp * 2 * cs, npix, cs, sp, tid & 255);
+    __syncthreads();
+    if (mine == 0) se_fc_sample(part, gate + (size_t)n * 2 * cs, gl, pool, mid, scratch, bs, C, cs, squeeze, excite, act, tid);
+    else se_fc_sample(part, gl, nullptr, pool, mid, scratch, bs, C, cs, squeeze, excite, act, tid);
+    __syncthreads();
+    const int total = npix * (cs / EPP), chunk = (total + parts - 1) / parts;
+    const int beg = mine * chunk, end = min(total, beg + chunk);
+    for (int first = beg + tid; first < end; first += kScaleUnroll * kSeFcThreads)
+        se_scale_pieces<T>(x + base, res ? res + base : nullptr, out + base, gl, first, kSeFcThreads, end, cs, act);
 }
 
 // Depthwise k x k convolution.  wt = [k*k][cs] fp32 (transposed), bias [cs].

@@ -10,9 +10,13 @@ by a few percent).  At n = 1 of 19x19 the per-kernel-class device time of one fo
 where a latency context's time goes: heads and pack_input stay one workgroup per sample.
 
 --mode default measures the default context alone: it uses nothing newer than the first ABI, so it runs on older trees.
+--se-one measures two LATENCY contexts against each other instead: the SE unit as one launch (`latency`, se_unit_kernel, the
+default) and as se_pool / se_fc / se_scale (`latency_se_three`, SAYURI_SE_ONE=0), interleaved in the same way, with
+se_one_device_ratio / se_one_rt_ratio = one / three per point and the per-kernel-class rows of a lone board for both.
 Prints ONE JSON object.
 
     python tools/latency_bench.py > profiles/r07_latency_small_batch.json
+    python tools/latency_bench.py --se-one > profiles/r10_latency_se_one.json
 """
 import argparse
 import ctypes
@@ -36,6 +40,7 @@ B = 19
 WORDS = 37 * 12 + 8
 NETS = {"20b256": (W.spec_20b256, 22), "40b384": (W.spec_40b384, 23)}
 POINTS = [(n, 19) for n in (1, 2, 4, 8, 16, 32, 64)] + [(1, 9), (1, 13)]
+SMALL_POINTS = [(16, 9)]  # --se-one: also a batch of small boards
 
 
 def weights_path(net):
@@ -77,6 +82,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--split", default="", help="also time latency contexts with these forced strips per board at n = 1 (e.g. 4,7,10)")
+    ap.add_argument("--se-one", action="store_true", help="two latency contexts: one launch per SE unit against SAYURI_SE_ONE=0")
     args = ap.parse_args()
     lib = _lib.hip()
     try:
@@ -85,11 +91,21 @@ def main():
         commit = ""
     out = {"tool": "tools/latency_bench.py", "box": socket.gethostname(), "commit": commit or "unknown", "mode": args.mode,
            "iters": args.iters, "rounds": args.rounds, "warmup": args.warmup, "statistic": "median of rounds", "nets": {}}
-    kinds = ["default"] + (["latency"] if args.mode == "both" else [])
+    kinds = [] if args.se_one else ["default"] + (["latency"] if args.mode == "both" else [])
+    if args.se_one:
+        out["se_one"] = True
+        os.environ.pop("SAYURI_SE_ONE", None)  # the two arms say which form they run
     for net in args.nets.split(","):
         path = weights_path(net)
         pipes = {k: HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, **({"latency": True} if k == "latency" else {})) for k in kinds}
-        for s in (int(x) for x in args.split.split(",") if x and args.mode == "both"):
+        if args.se_one:
+            pipes["latency"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
+            os.environ["SAYURI_SE_ONE"] = "0"
+            try:
+                pipes["latency_se_three"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
+            finally:
+                del os.environ["SAYURI_SE_ONE"]
+        for s in (int(x) for x in args.split.split(",") if x and args.mode == "both" and not args.se_one):
             os.environ["SAYURI_LATENCY_SPLIT"] = str(s)
             try:
                 pipes[f"latency_split{s}"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
@@ -98,7 +114,7 @@ def main():
         stage = hipraw.PinnedSet(64, B, WORDS)
         res = {"points": [], "tower_state": {k: lib.sayuri_hip_tower_state(p.ctx(0)) for k, p in pipes.items()}}
         try:
-            for n, bs in POINTS:
+            for n, bs in POINTS + (SMALL_POINTS if args.se_one else []):
                 planes = W.synthetic_planes(n, [bs] * n, seed=100 + n)
                 grid = np.zeros((n, 43, B * B), np.float32)
                 for i, p in enumerate(planes):
@@ -122,7 +138,10 @@ def main():
                 pt = {"n": n, "board": bs}
                 for k in use:
                     pt[k] = {"device_ms": round(float(np.median(dev[k])), 5), "rt_ms": round(float(np.median(rt[k])), 5)}
-                if "latency" in use:
+                if args.se_one:
+                    pt["se_one_device_ratio"] = round(pt["latency"]["device_ms"] / pt["latency_se_three"]["device_ms"], 4)
+                    pt["se_one_rt_ratio"] = round(pt["latency"]["rt_ms"] / pt["latency_se_three"]["rt_ms"], 4)
+                elif "latency" in use:
                     pt["device_ratio"] = round(pt["latency"]["device_ms"] / pt["default"]["device_ms"], 4)
                     pt["rt_ratio"] = round(pt["latency"]["rt_ms"] / pt["default"]["rt_ms"], 4)
                 if n == 1 and bs == 19:
@@ -136,7 +155,7 @@ def main():
             stage.close()
             for p in pipes.values():
                 p.Destroy()
-        if args.mode == "both":
+        if args.mode == "both" and not args.se_one:
             # the batch size of 19x19 boards from which the default context's device time is the smaller one
             cross = [pt["n"] for pt in res["points"] if pt["board"] == 19 and pt["device_ratio"] > 1.0]
             res["default_wins_from_n"] = min(cross) if cross else None
