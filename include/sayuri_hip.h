@@ -226,6 +226,21 @@ int sayuri_hip_tower_state(const sayuri_hip_ctx* ctx);
  * take the split route; 0 for a default context. */
 int sayuri_hip_latency_state(const sayuri_hip_ctx* ctx);
 
+/* The weight ring of a latency context's split convolutions (csrc/hip/conv_split.h: conv_split_kernel<NJ, ST>).  A strip's K
+ * loop takes its weights through a ring of ST groups in LDS; the thin strips of a small batch (NJ = 1, 2, 3 column tiles per
+ * wave) have a deep ring beside the three-stage one, and the engine's rule (csrc/hip/engine_plan.h: split_ring) picks by NJ.
+ * The ring decides speed only: the K order, and so every bit of the output, is the same.  SAYURI_LATENCY_RING=n forces n stages
+ * (3: the three-stage kernel everywhere); a depth that the chosen variant does not have, or whose LDS does not fit, is an error
+ * of the forward.
+ * sayuri_hip_split_ring_plan is host arithmetic (no device is touched): the stages a latency context gives a batch of n boards
+ * and a 3x3 layer of `cout` output channels under `strips` strips per board and `ring` stages, 0 meaning the engine's choice
+ * for either; -1 with a message where no split applies -- weight rows that are not whole 64-channel tiles, a forced ring that
+ * does not exist or does not fit.
+ * sayuri_hip_last_split_ring is the deepest ring any split convolution of the ctx's last forward ran with, 0 if none ran (a
+ * default context); with ctx == NULL, the ring of the calling thread's last sayuri_hip_test_conv_split launch. */
+int sayuri_hip_split_ring_plan(int n, const int* board_sizes, int max_board, int cout, int strips, int ring);
+int sayuri_hip_last_split_ring(const sayuri_hip_ctx* ctx);
+
 /* Release everything (replaces NNGraph::DestroyGraph, cuda_forward_pipe.cc:1092-1130). */
 void sayuri_hip_destroy(sayuri_hip_ctx* ctx);
 

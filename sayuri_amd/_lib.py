@@ -70,6 +70,8 @@ HIP_ABI = {
     "sayuri_hip_last_chains": (_I, [_V]),
     "sayuri_hip_tower_state": (_I, [_V]),
     "sayuri_hip_latency_state": (_I, [_V]),
+    "sayuri_hip_split_ring_plan": (_I, [_I, _IP, _I, _I, _I, _I]),
+    "sayuri_hip_last_split_ring": (_I, [_V]),
     "sayuri_hip_destroy": (None, [_V]),
     "sayuri_hip_last_error": (ctypes.c_char_p, []),
     # the layer taps: device, (use_fp16,) n, board_sizes, max_board, shape ..., tensors

@@ -19,6 +19,8 @@
 // two groups ahead and waited for with a counted vmcnt) and two halo chunks (64 bytes per halo position); ~60 KiB for a
 // strip of five rows of a 19x19 board.  The fragment reads are plain LDS loads that hipcc schedules and counts; only the
 // DMA is inline asm (glds16_s), so only vmcnt is counted by hand.
+// The thin variants (a strip of at most six column tiles) also exist with a ring of four weight groups (+12 KiB) whose K loop
+// holds no wait but the counted ones (see the bias below); engine_plan.h's split_ring says who runs which.
 #pragma once
 #include "conv_board.h"
 
@@ -27,8 +29,14 @@ namespace sayuri {
 constexpr int kSplitKO = 64;        // output channels per workgroup
 constexpr int kSplitMaxCols = 24;   // column tiles a strip may have (12 per wave in the widest variant)
 constexpr int kSplitMaxPos = 512;   // halo positions a strip may have (DMA blocks of 64)
-constexpr int kSplitStages = 3;     // weight groups in the ring
+constexpr int kSplitStages = 3;     // weight groups in the ring: every variant has this form
+constexpr int kSplitDeepStages = 4; // ... and the thin variants (NJ = 1, 2, 3: a K group of 6 to 18 MFMAs per wave) a deeper one.  Measured
+                                    // (DESIGN.md Kernel 1h): every stage beyond four costs more at the start than it hides later
 constexpr int kSplitABytes = 3 * kSplitKO * 64;  // one K group of weights: 3 taps x 64 rows x 32 channels
+// Halo chunks a ring of `stages` weight groups keeps in LDS: the chunk in use and the ceil((stages - 2) / 3) chunks asked for
+// ahead of it (the K loop's comment derives the lead).  Two up to five stages; the rings of six and eight stages that Kernel 1h
+// measured ran with three.
+constexpr int split_halo_slots(int stages) { return 1 + (stages - 2 + 2) / 3; }
 
 struct SplitParams {
     ConvParams c;  // npos = halo positions per strip of this launch (multiple of 64: the largest strip's), num_pix_tiles unused
@@ -45,7 +53,9 @@ __host__ __device__ inline int split_rows(int bs, int strips) {
     const int rp = (bs + s - 1) / s, cap = kSplitMaxCols * 16 / bs;
     return rp < cap ? rp : cap;
 }
-constexpr size_t split_lds_bytes(int npos) { return (size_t)kSplitStages * kSplitABytes + 2 * (size_t)npos * 64; }
+constexpr size_t split_lds_bytes(int npos, int stages = kSplitStages) {
+    return (size_t)stages * kSplitABytes + (size_t)split_halo_slots(stages) * (size_t)npos * 64;
+}
 
 template <int NJ, int ACT>
 __device__ __forceinline__ void split_epilogue(const ConvParams& p, f32x4 (&acc)[2][NJ], const f16x8 (&rr)[NJ], const int (&orow)[NJ], int nj,
@@ -64,8 +74,14 @@ __device__ __forceinline__ void split_epilogue(const ConvParams& p, f32x4 (&acc)
     }
 }
 
-template <int NJ>  // column tiles per wave: a strip has up to 2 NJ
+// NJ: column tiles per wave (a strip has up to 2 NJ).  ST: weight groups in the ring -- kSplitStages is the kernel as it was
+// before the ring had a depth; a deeper ring (kSplitDeepStages, the thin variants) asks for weights ST - 1 groups ahead and for
+// halo chunks split_halo_slots(ST) - 1 chunks ahead, waits for the bias in front of the K loop instead of inside it, and changes
+// nothing else: not the K order, not the epilogue.  Any ST from 3 to 22 is a valid kernel (an entry in kSplitEntries builds it).
+template <int NJ, int ST>
 __global__ __launch_bounds__(256) void conv_split_kernel(const SplitParams sp) {
+    static_assert(ST >= 3 && 3 * (ST - 2) < 64, "the counted wait is a 6-bit vmcnt");
+    constexpr int HS = split_halo_slots(ST), HL = HS - 1;  // halo slots, and how many chunks ahead a halo chunk is asked for
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const ConvParams& p = sp.c;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -82,7 +98,7 @@ __global__ __launch_bounds__(256) void conv_split_kernel(const SplitParams sp) {
     const int wave_m = wave & 1, wave_n = wave >> 1;
     const int nj0 = (ncols + 1) >> 1, col0 = wave_n ? nj0 : 0, nj = wave_n ? ncols - nj0 : nj0;
     const int kg = lane >> 4, px = lane & 15;
-    const uint32_t a_ring = (uint32_t)(uintptr_t)smem, b_ring = a_ring + kSplitStages * kSplitABytes;
+    const uint32_t a_ring = (uint32_t)(uintptr_t)smem, b_ring = a_ring + ST * kSplitABytes;
     const int first_row = sample * p.g.slot_pix + row0 * bs;  // activation row of the strip's first pixel
 
     // x / n as (int)((x + 0.5) * rcp(n)): x < 1024, n >= 2 -- the quotient is never within 0.015 of an integer boundary
@@ -134,44 +150,87 @@ __global__ __launch_bounds__(256) void conv_split_kernel(const SplitParams sp) {
         const bool in = r < nrows + 2 && y >= 0 && y < bs && xc >= 1 && xc <= bs;
         boff[i] = (in ? (uint32_t)kZeroPrefix + (uint32_t)(sample * p.g.slot_pix + y * bs + xc - 1) * (uint32_t)(p.cin_s * 2) : 0u) + wave * 16;
     }
-    auto issue_b = [&](int chunk) {
+    auto issue_b = [&](int chunk, int slot) {  // slot = chunk mod HS: with two slots the chunk's parity, else the caller's count
 #pragma unroll
         for (int i = 0; i < kSplitMaxPos / 64; ++i)
-            if (i < npb) glds16_s(boff[i], gin0 + chunk * (kChunk * 2), b_ring + (chunk & 1) * b_bytes + (wave * npos + i * 64) * 16);
+            if (i < npb)
+                glds16_s(boff[i], gin0 + chunk * (kChunk * 2), b_ring + (HS == 2 ? chunk & 1 : slot) * b_bytes + (wave * npos + i * 64) * 16);
     };
+    // The prologue: A(0), the halo chunks 0 .. HL - 1, A(1) .. A(ST - 2) -- never beyond the layer.  A layer has at least one
+    // chunk and three groups, which is all the three-stage ring asks for here; a 32-channel layer has no more than that, and
+    // the input convolution two chunks and six groups: fewer than the deep ring, which therefore asks before it issues.
     issue_a(0, 0);
-    issue_b(0);
-    issue_a(1, 1);  // (a layer has at least three groups)
+    issue_b(0, 0);
+    if constexpr (HL > 1) {
+#pragma unroll
+        for (int h = 1; h < HL; ++h)
+            if (h < nchunks) issue_b(h, h);
+    }
+    issue_a(1, 1);
+    if constexpr (ST > 3) {
+#pragma unroll
+        for (int g = 2; g <= ST - 2; ++g)
+            if (g == 2 || g < ngroups) issue_a(g, g);  // (a layer has at least three groups)
+    }
 
     // accumulators start at the bias: D rows 4 * (lane >> 4) + r of row tile i are 4 consecutive output channels
-    f32x4 acc[2][NJ];
+    f32x4 acc[2][NJ], b4[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) b4[i] = *(const f32x4*)(p.bias + kt * kSplitKO + wave_m * 32 + i * 16 + 4 * kg);
+    // The bias is the one load of hipcc's own that the K loop consumes.  Left alone, hipcc waits for it where the loop first uses
+    // an accumulator -- an s_waitcnt vmcnt(0) INSIDE the loop, in the first group of every chunk, which also waits for every
+    // DMA piece in flight: the ring is drained once per chunk, whatever its depth (the three-stage kernel has that wait; it
+    // stays as it is).  A deeper ring uses the values here, so that the wait is in front of the loop, where group 0 needs A(0)
+    // and the first halo chunk anyway; the loop then holds no vmcnt but the counted ones.  That wait also covers the rest of
+    // the prologue, A(1) ... A(ST - 2): the price of every further stage (DESIGN.md Kernel 1h).
+    if constexpr (ST > kSplitStages) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]));
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const f32x4 b4 = *(const f32x4*)(p.bias + kt * kSplitKO + wave_m * 32 + i * 16 + 4 * kg);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = b4;
+        for (int j = 0; j < NJ; ++j) acc[i][j] = b4[i];
     }
     // per-lane fragment offsets: A = (k-group plane, this wave's rows), B = (k-group plane, the pixel's tap (0, 0))
     const uint32_t a_off = (uint32_t)((kg * kSplitKO + wave_m * 32 + px) * 16);
     uint32_t b_off[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) b_off[j] = (uint32_t)(kSplitStages * kSplitABytes) + (uint32_t)(kg * npos + lp[j]) * 16u;
+    for (int j = 0; j < NJ; ++j) b_off[j] = (uint32_t)(ST * kSplitABytes) + (uint32_t)(kg * npos + lp[j]) * 16u;
 
-    // ---- K loop.  At the head of group G the memory queue of every wave ends with ... A(G) | [halo of the next chunk] |
-    // A(G + 1): "at most three outstanding" = A(G), and the halo chunk asked for one group earlier, have landed.  The barrier
-    // then says so for all four waves, and that all of them are done with the stage and the halo slot that are refilled next.
-    int G = 0, stage = 0;
+    // ---- K loop.  Group G (of chunk c = G / 3) issues, behind its barrier, the halo of chunk c + HL (in a chunk's first group
+    // only) and then A(G + ST - 1), so every wave's memory queue is, oldest first,
+    //     ... A(G) | A(G + 1) ... A(G + ST - 2)        with halo chunks between some of them,
+    // three pieces per wave and weight group, the same number of pieces from every wave.  The wait at the head of group G lets
+    // the 3 (ST - 2) youngest pieces be outstanding -- and nothing at all in a layer's last ST - 2 groups, where fewer groups
+    // are left than the count assumes: vmcnt is an immediate, and one two-way choice keeps the loop the shape it had (what
+    // those groups wait for in excess was asked for at least three groups earlier):
+    //   weights  A(G) is older than A(G + 1) ... A(G + ST - 2), and than any halo piece between them: it has landed.  A halo
+    //            chunk among the youngest only makes the wait ask for more than it needs, by at most that chunk's pieces.
+    //   halo     chunk c is first read in group 3c and was asked for in group 3 (c - HL), in front of that group's weights
+    //            (chunks below HL: in the prologue, in front of A(1)).  Younger than it at the head of group 3c are the 3 HL
+    //            weight groups issued since, A(3 (c - HL) + ST - 1) ... A(3c + ST - 2), less those beyond the layer's end.  The
+    //            wait lets A(3c + 1) ... A(3c + ST - 2) be outstanding (or nothing): a subset of them as long as
+    //            3 (c - HL) + ST - 1 <= 3c + 1, which is ST - 2 <= 3 HL.  Hence HL = ceil((ST - 2) / 3): one chunk ahead and two
+    //            slots up to five stages (the rings in use), two ahead and three slots from six to eight.
+    // The barrier then says the same for all four waves, and that all of them are done with group G - 1: its weight stage,
+    // (G - 1) mod ST, is where A(G + ST - 1) goes, and the halo slot of chunk c - 1, (c - 1) mod HS, is where chunk c + HL goes.
+    int G = 0, stage = 0, slot = 0;
     for (int chunk = 0; chunk < nchunks; ++chunk) {
 #pragma unroll
         for (int row = 0; row < 3; ++row) {
-            if (G + 1 < ngroups) wait_vmcnt<3>();
+            if (G + ST - 2 < ngroups) wait_vmcnt<3 * (ST - 2)>();
             else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");  // no fragment read of this group moves above the barrier
-            if (row == 0 && chunk + 1 < nchunks) issue_b(chunk + 1);
-            if (G + 2 < ngroups) issue_a(G + 2, stage >= 1 ? stage - 1 : kSplitStages - 1);
+            if (row == 0 && chunk + HL < nchunks) issue_b(chunk + HL, slot >= 1 ? slot - 1 : HS - 1);
+            const int refill = stage >= 1 ? stage - 1 : ST - 1;
+            if constexpr (ST > kSplitStages) {
+                // (the hint keeps hipcc from laying this group's head out behind the loop as a small loop of its own, which
+                // tests/test_latency_cpu.py's reading of the code object would take for a wait on global memory)
+                if (__builtin_expect(G + ST - 1 < ngroups, 1)) issue_a(G + ST - 1, refill);
+            } else {
+                if (G + ST - 1 < ngroups) issue_a(G + ST - 1, refill);
+            }
             const unsigned char* as = smem + stage * kSplitABytes + a_off;
-            const unsigned char* bsl = smem + (chunk & 1) * b_bytes + row * (w2 * 16);
+            const unsigned char* bsl = smem + (HS == 2 ? chunk & 1 : slot) * b_bytes + row * (w2 * 16);
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
                 const f16x8 a0 = *(const f16x8*)(as + dx * (4 * kSplitKO * 16));
@@ -186,8 +245,9 @@ __global__ __launch_bounds__(256) void conv_split_kernel(const SplitParams sp) {
                 }
             }
             ++G;
-            stage = stage + 1 == kSplitStages ? 0 : stage + 1;
+            stage = stage + 1 == ST ? 0 : stage + 1;
         }
+        slot = slot + 1 == HS ? 0 : slot + 1;
     }
 
     switch (p.act) {

@@ -190,6 +190,28 @@ size_t sayuri_hip_device_bytes(const sayuri_hip_ctx* ctx) { return ctx ? ctx->en
 int sayuri_hip_last_chains(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_chains() : 0; }
 int sayuri_hip_tower_state(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->tower_state() : -1; }
 int sayuri_hip_latency_state(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->latency_state() : -1; }
+int sayuri_hip_last_split_ring(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_split_ring() : sayuri::g_test_split_ring; }
+// host arithmetic only: the geometry, the layer's weight rows and split_plan, as a latency context and the conv_split tap run them
+int sayuri_hip_split_ring_plan(int n, const int* board_sizes, int max_board, int cout, int strips, int ring) {
+    using namespace sayuri;
+    if (n <= 0 || !board_sizes || max_board < 2 || cout <= 0 || strips < 0) return fail("split_ring_plan: bad argument");
+    HostGeom hg;
+    hg.n = n;
+    hg.bsz.assign(board_sizes, board_sizes + n);
+    hg.off.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        if (hg.bsz[i] < 2 || hg.bsz[i] > max_board) return fail("split_ring_plan: bad board size");
+        hg.off[i + 1] = hg.off[i] + hg.bsz[i] * hg.bsz[i];
+    }
+    hg.total = hg.off[n];
+    int wmt, ko_pad;
+    conv_tile(round_up(cout, 32), true, &wmt, &ko_pad);
+    if (route_conv(true, 3, ko_pad, hg, BoardPlan{}, ConvOverride{}, 0, /*latency=*/true).family != kConvSplit)
+        return fail("split_ring_plan: a layer of " + std::to_string(ko_pad) + " weight rows is not whole 64-channel tiles: it keeps the default route");
+    const SplitPlan sp = split_plan(hg, 0, n, ko_pad, strips, ring);
+    if (!sp.ok) return fail("split_ring_plan: " + split_refusal(sp));
+    return sp.stages;
+}
 // debugging tap (not part of the ABI, not in the header): activation buffer `buf` (0..5) of ticket 0 as it stands after the last forward
 extern "C" int sayuri_hip_debug_read_activations(sayuri_hip_ctx* ctx, int buf, void* host, size_t bytes) {
     return ctx ? ctx->eng->debug_read(buf, host, bytes) : -1;

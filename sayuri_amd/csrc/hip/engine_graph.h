@@ -27,6 +27,7 @@ public:
     virtual int timed_stat(sayuri_hip_kernel_stat* row) = 0;
     virtual size_t device_bytes() const = 0;
     virtual int last_chains() const = 0;
+    virtual int last_split_ring() const = 0;  // the deepest weight ring of the last forward's split convolutions (0: none ran)
     virtual int tower_state() const = 0;  // 1: the persistent tower kernel is loaded, 0: one launch per layer (fallback)
     virtual int latency_state() const = 0;  // 1: a latency context (conv_split.h), 0: the default engine
     virtual int debug_read(int buf, void* host, size_t bytes) = 0;  // debugging tap: activation buffer `buf` of ticket 0
@@ -102,6 +103,7 @@ public:
     hipStream_t chain_stream_[kMaxChains] = {};
     hipEvent_t chain_fork_ = nullptr, chain_join_[kMaxChains] = {};
     int last_chains_ = 1;
+    int last_split_ring_ = 0;
     int chain_setup(int G) {
         if (!chain_fork_) HIP_OK(hipEventCreateWithFlags(&chain_fork_, hipEventDisableTiming));
         for (int g = 0; g < G; ++g) {
@@ -586,6 +588,7 @@ public:
 
     size_t device_bytes() const override { return dev_bytes_; }
     int last_chains() const override { return last_chains_; }
+    int last_split_ring() const override { return last_split_ring_; }
     int tower_state() const override { return tower_fn_[0] != nullptr ? 1 : 0; }
     int latency_state() const override { return flags_.latency ? 1 : 0; }
     int debug_read(int buf, void* host, size_t bytes) override {
@@ -1199,9 +1202,10 @@ private:
     // split chosen from the batch geometry (split_plan; cached like the routes: it depends on the geometry only).
     int conv_split(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
         auto it = split_cache_.find(L.ko_pad);
-        if (it == split_cache_.end()) it = split_cache_.emplace(L.ko_pad, split_plan(geom_, f.n0, f.ns, L.ko_pad, flags_.latency_split)).first;
+        if (it == split_cache_.end()) it = split_cache_.emplace(L.ko_pad, split_plan(geom_, f.n0, f.ns, L.ko_pad, flags_.latency_split, flags_.latency_ring)).first;
         const SplitPlan& sp = it->second;
-        if (!sp.ok) return fail(std::string("latency context: no split of layer ") + name + " fits this batch geometry");
+        if (!sp.ok) return fail(std::string("latency context, layer ") + name + ": " + split_refusal(sp));
+        last_split_ring_ = std::max(last_split_ring_, sp.stages);
         SplitParams q;
         std::memset(&q, 0, sizeof(q));
         conv_params(q.c, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
@@ -1368,6 +1372,7 @@ private:
     int forward(int t, float* zc_pass = nullptr, float* zc_misc = nullptr) {
         const int G = chains_for_batch();
         last_chains_ = G;
+        last_split_ring_ = 0;
         rows_reset();
         IoSlot& io = io_[t];
         Fwd f{t, io, compute_[t]};

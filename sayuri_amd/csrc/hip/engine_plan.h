@@ -8,6 +8,7 @@ namespace sayuri {
 static thread_local std::string g_err;
 static std::atomic<unsigned> g_host_free_gen{0};  // sayuri_hip_host_free calls so far (Engine::zc_device_pointer)
 static thread_local int g_test_conv_kind = 0;  // kernel family (ConvFamily) the last sayuri_hip_test_conv call ran
+static thread_local int g_test_split_ring = 0; // weight stages of the last sayuri_hip_test_conv_split launch (0: none yet)
 static int fail(const std::string& m) { g_err = m; return -1; }
 
 #define HIP_OK(expr)                                                                      \
@@ -99,11 +100,16 @@ static const BoardEntry kBoardEntries[] = {
     {192, &conv_board_kernel<3>, nullptr, &BoardCfg<3>::lds_bytes},
     {128, &conv_board_kernel<2>, &conv_board_se_kernel<2>, &BoardCfg<2>::lds_bytes},
 };
-// many-small-workgroups kernels of the latency mode (conv_split.h), by column tiles per wave
+// many-small-workgroups kernels of the latency mode (conv_split.h), by column tiles per wave and weight stages: the
+// three-stage ring for every width (ascending: split_plan takes the first that is wide enough), the deeper one for the thin ones
 typedef void (*SplitFn)(const SplitParams);
-struct SplitEntry { int nj; SplitFn fn; };
+struct SplitEntry { int nj, stages; SplitFn fn; };
 static const SplitEntry kSplitEntries[] = {
-    {1, &conv_split_kernel<1>}, {2, &conv_split_kernel<2>}, {3, &conv_split_kernel<3>}, {6, &conv_split_kernel<6>}, {12, &conv_split_kernel<12>},
+    {1, kSplitStages, &conv_split_kernel<1, kSplitStages>}, {2, kSplitStages, &conv_split_kernel<2, kSplitStages>},
+    {3, kSplitStages, &conv_split_kernel<3, kSplitStages>}, {6, kSplitStages, &conv_split_kernel<6, kSplitStages>},
+    {12, kSplitStages, &conv_split_kernel<12, kSplitStages>},
+    {1, kSplitDeepStages, &conv_split_kernel<1, kSplitDeepStages>}, {2, kSplitDeepStages, &conv_split_kernel<2, kSplitDeepStages>},
+    {3, kSplitDeepStages, &conv_split_kernel<3, kSplitDeepStages>},
 };
 // head_board_kernel variants: {row tiles, trunk chunks in flight}; the first that fits the LDS is used (head_board_fits)
 typedef void (*HeadFn)(const HeadBoardParams);
@@ -140,6 +146,8 @@ static void enable_big_lds_glds() {
 //   SAYURI_LATENCY=1              a plain sayuri_hip_create of the fp16 engine makes a latency context (sayuri_hip_create_ex's
 //                                 SAYURI_HIP_LATENCY; read in engine.hip, not here: the taps do not see it)
 //   SAYURI_LATENCY_SPLIT=n        latency context: n strips per board in every split convolution instead of the engine's choice
+//   SAYURI_LATENCY_RING=n         latency context: n weight stages in every split convolution instead of the engine's choice (split_ring);
+//                                 3 is the three-stage ring everywhere; a depth the chosen variant does not have is refused
 //   SAYURI_SE_ONE=0 | 1           the SE unit outside a convolution as se_pool / se_fc / se_scale everywhere | as one launch everywhere
 // The other switches are described at their fields below.
 struct ConvOverride {
@@ -154,6 +162,7 @@ struct EngineFlags {
                                        // launch, no chains, every SE unit as one launch behind its convolution (for_latency(), se_one,
                                        // Engine::se_unit())
     int latency_split = 0;             // SAYURI_LATENCY_SPLIT=n: strips per board (0: split_auto)
+    int latency_ring = 0;              // SAYURI_LATENCY_RING=n: weight stages of the split kernels (0: split_ring)
     int se_one = -1;                   // SAYURI_SE_ONE: an SE unit that runs as kernels of its own is ONE launch (se_unit_kernel, small_ops.h)
                                        // instead of se_pool / se_fc / se_scale -- unset (-1): in a latency context (Engine::se_unit()'s
                                        // rule); 0: nowhere; 1: wherever Engine::se_unit() or the se_unit tap would run the three.  Same
@@ -201,6 +210,7 @@ struct EngineFlags {
         f.tower_sync = getenv("SAYURI_TOWER_SYNC") != nullptr;
         f.fwdstat = getenv("SAYURI_HIP_FWDSTAT") != nullptr;
         if (const char* e = getenv("SAYURI_LATENCY_SPLIT")) f.latency_split = std::max(0, atoi(e));
+        if (const char* e = getenv("SAYURI_LATENCY_RING")) f.latency_ring = atoi(e);  // (split_plan refuses what no kernel has)
         if (const char* e = getenv("SAYURI_SE_ONE")) f.se_one = atoi(e) != 0;
 #ifdef SAYURI_EXPERIMENTS
         if (const char* e = getenv("SAYURI_BOARD_KOT")) f.board_kot = atoi(e);
@@ -405,15 +415,26 @@ static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, 
 // The split rule (strips == 0): as many strips per board as keep the launch near ONE round of the 256 CUs -- 256 / (samples x
 // channel tiles), at least one, at most kSplitAutoMax and never more than a board has rows (split_rows) -- so a lone board is
 // cut finely and a batch of 64 not at all.  It decides the speed only: the results do not depend on the split.
+// The ring rule (ring == 0): the weight stages of the variant with `nj` column tiles per wave.  Like the split it decides the
+// speed only, and it looks at nothing but nj -- which the batch geometry decides, as it decides the split.  Measured (DESIGN.md
+// Kernel 1h, profiles/r11_latency_ring.json): the four-stage ring is 5 to 8 % of a forward ahead at nj = 1 (one or two 19x19
+// boards, a lone small board, sixteen 9x9 boards on 256 channels) and level or up to 1.4 % behind at nj = 2 and 3, so only
+// nj = 1 takes it; the wide variants have no deeper ring.  ring == n forces n stages: where the chosen variant has no such
+// instantiation, or its LDS does not fit, the plan is not ok (bad_ring says why).
 constexpr int kSplitAutoMax = 19;
 struct SplitPlan {
     bool ok = false;
-    int strips = 0, smax = 0, kts = 0, npos = 0, grid = 0;
+    int strips = 0, smax = 0, kts = 0, npos = 0, grid = 0, stages = 0, bad_ring = 0;
     const SplitEntry* e = nullptr;
     size_t lds = 0;
 };
 static int split_auto(int ns, int kts) { return std::max(1, std::min(kSplitAutoMax, kNumCU / std::max(1, ns * kts))); }
-static SplitPlan split_plan(const HostGeom& geom, int n0, int ns, int ko_pad, int strips) {
+static int split_ring(int nj) { return nj == 1 ? kSplitDeepStages : kSplitStages; }
+static std::string split_refusal(const SplitPlan& sp) {
+    return sp.bad_ring ? "no split kernel with a ring of " + std::to_string(sp.bad_ring) + " weight stages fits this batch geometry (SAYURI_LATENCY_RING)"
+                       : std::string("no split fits this batch geometry");
+}
+static SplitPlan split_plan(const HostGeom& geom, int n0, int ns, int ko_pad, int strips, int ring) {
     SplitPlan sp;
     if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || ko_pad <= 0 || ko_pad % kSplitKO) return sp;
     sp.kts = ko_pad / kSplitKO;
@@ -428,10 +449,20 @@ static SplitPlan split_plan(const HostGeom& geom, int n0, int ns, int ko_pad, in
     sp.npos = round_up(max_pos, 64);
     if (sp.npos > kSplitMaxPos || max_cols > kSplitMaxCols) return sp;
     for (const auto& e : kSplitEntries)
-        if (!sp.e && 2 * e.nj >= max_cols) sp.e = &e;
-    sp.lds = split_lds_bytes(sp.npos);
+        if (!sp.e && e.stages == kSplitStages && 2 * e.nj >= max_cols) sp.e = &e;
+    if (!sp.e) return sp;
+    const int want = ring ? ring : split_ring(sp.e->nj);
+    if (want != kSplitStages) {  // the same width with the ring asked for; the rule keeps three stages where a deeper ring does not fit
+        const SplitEntry* deep = nullptr;
+        for (const auto& e : kSplitEntries)
+            if (e.nj == sp.e->nj && e.stages == want && split_lds_bytes(sp.npos, want) <= kMaxLds) deep = &e;
+        if (deep) sp.e = deep;
+        else if (ring) { sp.bad_ring = ring; return sp; }
+    }
+    sp.stages = sp.e->stages;
+    sp.lds = split_lds_bytes(sp.npos, sp.stages);
     sp.grid = ns * sp.smax * sp.kts;
-    sp.ok = sp.e != nullptr && sp.lds <= kMaxLds;
+    sp.ok = sp.lds <= kMaxLds;
     return sp;
 }
 // The split kernels' part of a launch (conv_params fills q.c before): the halo bound, the split and the first sample.

@@ -165,6 +165,7 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
 // The same fp16 3x3 layer as many small workgroups (conv_split.h, the latency context's route): the engine's image in natural
 // row order, split_plan's launch.  strips: strips per board (0: the engine's choice for this batch); channel_tiles: 0, or
 // the number of 64-channel tiles the layer has -- the kernel has one channel tile size, any other count is refused.
+// SAYURI_LATENCY_RING=n (read per call, as SAYURI_CONV is) forces the weight ring; sayuri_hip_last_split_ring(NULL) says what ran.
 static int test_conv_split_impl(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act, const float* x,
                                 const float* w, const float* bias, const float* res, float* y, int channel_tiles, int strips) {
     typedef f16 T;
@@ -181,8 +182,8 @@ static int test_conv_split_impl(int device, int n, const int* board_sizes, int m
     if (channel_tiles && channel_tiles != ko_pad / kSplitKO)
         return fail("test_conv_split: the split kernel's channel tile is 64: this layer has " + std::to_string(ko_pad / kSplitKO) + " channel tiles");
     if (strips < 0) return fail("test_conv_split: bad strip count");
-    const SplitPlan sp = split_plan(tg.hg, 0, n, ko_pad, strips);
-    if (!sp.ok) return fail("test_conv_split: no split fits this batch geometry");
+    const SplitPlan sp = split_plan(tg.hg, 0, n, ko_pad, strips, EngineFlags::from_env().latency_ring);
+    if (!sp.ok) return fail("test_conv_split: " + split_refusal(sp));
     const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, cin, cin_s));
     const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, cout, cout_s)) : nullptr;
     T* dy = (T*)A.alloc((size_t)n * tg.slot * cout_s * sizeof(T));
@@ -190,6 +191,7 @@ static int test_conv_split_impl(int device, int n, const int* board_sizes, int m
     const float* db = A.upload(padded_bias(bias, cout, ko_pad));
     if (!dx || !dy || (res && !dres) || !dw || !db) return fail("test_conv_split: hipMalloc failed");
     g_test_conv_kind = kConvSplit;
+    g_test_split_ring = sp.stages;
     SplitParams q;
     std::memset(&q, 0, sizeof(q));
     conv_params(q.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 9, act);

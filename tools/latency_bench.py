@@ -13,10 +13,16 @@ where a latency context's time goes: heads and pack_input stay one workgroup per
 --se-one measures two LATENCY contexts against each other instead: the SE unit as one launch (`latency`, se_unit_kernel, the
 default) and as se_pool / se_fc / se_scale (`latency_se_three`, SAYURI_SE_ONE=0), interleaved in the same way, with
 se_one_device_ratio / se_one_rt_ratio = one / three per point and the per-kernel-class rows of a lone board for both.
+--ring measures the weight ring of the split convolutions in the same way: `latency` (the engine's rule, split_ring) against
+`latency_ring3` (SAYURI_LATENCY_RING=3, the three-stage kernel everywhere) with ring_device_ratio / ring_rt_ratio = rule / three,
+and a second =3 context, `latency_ring3_again`, whose ratio to the first (same_config_device_ratio) is the spread of the method:
+a depth belongs in the rule only where its ratio is below 1 by more than that.  --ring-depths 8,5 adds a context per forced
+depth, timed at the points whose strips have a variant of that depth (sayuri_hip_split_ring_plan says).  Every arm's point names the ring that ran (sayuri_hip_last_split_ring).
 Prints ONE JSON object.
 
     python tools/latency_bench.py > profiles/r07_latency_small_batch.json
     python tools/latency_bench.py --se-one > profiles/r10_latency_se_one.json
+    python tools/latency_bench.py --ring --ring-depths 8 > profiles/r11_latency_ring.json
 """
 import argparse
 import ctypes
@@ -40,7 +46,7 @@ B = 19
 WORDS = 37 * 12 + 8
 NETS = {"20b256": (W.spec_20b256, 22), "40b384": (W.spec_40b384, 23)}
 POINTS = [(n, 19) for n in (1, 2, 4, 8, 16, 32, 64)] + [(1, 9), (1, 13)]
-SMALL_POINTS = [(16, 9)]  # --se-one: also a batch of small boards
+SMALL_POINTS = [(16, 9)]  # --se-one, --ring: also a batch of small boards
 
 
 def weights_path(net):
@@ -83,7 +89,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--split", default="", help="also time latency contexts with these forced strips per board at n = 1 (e.g. 4,7,10)")
     ap.add_argument("--se-one", action="store_true", help="two latency contexts: one launch per SE unit against SAYURI_SE_ONE=0")
+    ap.add_argument("--ring", action="store_true", help="latency contexts: the ring rule against SAYURI_LATENCY_RING=3, and =3 against =3")
+    ap.add_argument("--ring-depths", default="", help="--ring: also time latency contexts with these forced weight stages where the batch has such a variant (e.g. 8)")
     args = ap.parse_args()
+    if args.ring and args.se_one:
+        ap.error("--ring and --se-one are two measurements")
     lib = _lib.hip()
     try:
         commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
@@ -91,12 +101,16 @@ def main():
         commit = ""
     out = {"tool": "tools/latency_bench.py", "box": socket.gethostname(), "commit": commit or "unknown", "mode": args.mode,
            "iters": args.iters, "rounds": args.rounds, "warmup": args.warmup, "statistic": "median of rounds", "nets": {}}
-    kinds = [] if args.se_one else ["default"] + (["latency"] if args.mode == "both" else [])
+    kinds = [] if args.se_one or args.ring else ["default"] + (["latency"] if args.mode == "both" else [])
+    if args.ring:
+        out["ring"] = True
+        os.environ.pop("SAYURI_LATENCY_RING", None)  # the arms say which ring they run
     if args.se_one:
         out["se_one"] = True
         os.environ.pop("SAYURI_SE_ONE", None)  # the two arms say which form they run
     for net in args.nets.split(","):
         path = weights_path(net)
+        channels = int(net.split("b")[1])
         pipes = {k: HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, **({"latency": True} if k == "latency" else {})) for k in kinds}
         if args.se_one:
             pipes["latency"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
@@ -105,7 +119,15 @@ def main():
                 pipes["latency_se_three"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
             finally:
                 del os.environ["SAYURI_SE_ONE"]
-        for s in (int(x) for x in args.split.split(",") if x and args.mode == "both" and not args.se_one):
+        if args.ring:
+            pipes["latency"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
+            for k, depth in [("latency_ring3", 3), ("latency_ring3_again", 3)] + [(f"latency_forced_ring{d}", int(d)) for d in args.ring_depths.split(",") if d]:
+                os.environ["SAYURI_LATENCY_RING"] = str(depth)
+                try:
+                    pipes[k] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
+                finally:
+                    del os.environ["SAYURI_LATENCY_RING"]
+        for s in (int(x) for x in args.split.split(",") if x and args.mode == "both" and not args.se_one and not args.ring):
             os.environ["SAYURI_LATENCY_SPLIT"] = str(s)
             try:
                 pipes[f"latency_split{s}"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
@@ -114,7 +136,7 @@ def main():
         stage = hipraw.PinnedSet(64, B, WORDS)
         res = {"points": [], "tower_state": {k: lib.sayuri_hip_tower_state(p.ctx(0)) for k, p in pipes.items()}}
         try:
-            for n, bs in POINTS + (SMALL_POINTS if args.se_one else []):
+            for n, bs in POINTS + (SMALL_POINTS if args.se_one or args.ring else []):
                 planes = W.synthetic_planes(n, [bs] * n, seed=100 + n)
                 grid = np.zeros((n, 43, B * B), np.float32)
                 for i, p in enumerate(planes):
@@ -123,6 +145,10 @@ def main():
                 stage.records[:n * WORDS] = np.stack([pack_planes(p, 37) for p in planes]).astype(np.uint32).ravel()
                 stage.bsz[:n] = bsz
                 use = {k: p for k, p in pipes.items() if n == 1 or "split" not in k}
+                for k in [k for k in use if "forced_ring" in k]:  # a forced depth only where this batch's variant has it
+                    depth = int(k.rsplit("ring", 1)[1])
+                    if lib.sayuri_hip_split_ring_plan(n, _lib.ip(bsz), B, channels, 0, depth) != depth:
+                        del use[k]
                 dev = {k: [] for k in use}
                 rt = {k: [] for k in use}
                 for r in range(-1, args.rounds):  # round -1: the warm-up
@@ -138,7 +164,15 @@ def main():
                 pt = {"n": n, "board": bs}
                 for k in use:
                     pt[k] = {"device_ms": round(float(np.median(dev[k])), 5), "rt_ms": round(float(np.median(rt[k])), 5)}
-                if args.se_one:
+                if args.ring:
+                    three = pt["latency_ring3"]
+                    for k, p in use.items():
+                        pt[k]["ring"] = int(lib.sayuri_hip_last_split_ring(p.ctx(0)))
+                        if k != "latency_ring3":
+                            tag = {"latency": "ring", "latency_ring3_again": "same_config"}.get(k, k[len("latency_"):])
+                            pt[f"{tag}_device_ratio"] = round(pt[k]["device_ms"] / three["device_ms"], 4)
+                            pt[f"{tag}_rt_ratio"] = round(pt[k]["rt_ms"] / three["rt_ms"], 4)
+                elif args.se_one:
                     pt["se_one_device_ratio"] = round(pt["latency"]["device_ms"] / pt["latency_se_three"]["device_ms"], 4)
                     pt["se_one_rt_ratio"] = round(pt["latency"]["rt_ms"] / pt["latency_se_three"]["rt_ms"], 4)
                 elif "latency" in use:
@@ -146,7 +180,7 @@ def main():
                     pt["rt_ratio"] = round(pt["latency"]["rt_ms"] / pt["default"]["rt_ms"], 4)
                 if n == 1 and bs == 19:
                     for k, p in use.items():
-                        if "split" in k:
+                        if "split" in k or "forced" in k or "again" in k:
                             continue
                         lib.sayuri_hip_upload(p.ctx(0), n, _lib.fp(grid), _lib.ip(bsz))
                         pt[k]["kernel_classes_one_forward"] = kernel_classes(lib, p.ctx(0))
@@ -155,7 +189,7 @@ def main():
             stage.close()
             for p in pipes.values():
                 p.Destroy()
-        if args.mode == "both" and not args.se_one:
+        if args.mode == "both" and not args.se_one and not args.ring:
             # the batch size of 19x19 boards from which the default context's device time is the smaller one
             cross = [pt["n"] for pt in res["points"] if pt["board"] == 19 and pt["device_ratio"] > 1.0]
             res["default_wins_from_n"] = min(cross) if cross else None
