@@ -241,6 +241,22 @@ int sayuri_hip_latency_state(const sayuri_hip_ctx* ctx);
 int sayuri_hip_split_ring_plan(int n, const int* board_sizes, int max_board, int cout, int strips, int ring);
 int sayuri_hip_last_split_ring(const sayuri_hip_ctx* ctx);
 
+/* The tower's 1x1 convolutions of bottleneck-family networks (csrc/hip/conv_pw.h: conv_pw_kernel<NJ>).  In the fp16 engine a
+ * block's PRE_BTL / POST_BTL layer and a mixer block's CONV1 / CONV2, when they map whole 32-channel chunks onto whole 64-channel
+ * tiles, run as many small independent workgroups -- one per (sample, piece of that sample's pixels, 64 output channels) -- in a
+ * default and in a latency context alike -- where the engine's speed rule says it pays --, with the bits of the generic kernel.
+ * SAYURI_PW=0 keeps the generic kernel everywhere, SAYURI_PW=1 takes conv_pw.h wherever it applies;
+ * SAYURI_PW_PIECES=n forces n pieces per sample.  The cut decides speed only.
+ * sayuri_hip_pw_plan is host arithmetic (no device is touched): out = {pieces asked for per sample, grid, NJ (column tiles per
+ * wave of the variant), LDS bytes} of a batch of n boards and a cin -> cout layer under `pieces` pieces per sample, 0 meaning the
+ * engine's choice; -1 with a message where no plan applies -- cout % 64, cin % 32, a forced cut whose pieces are wider than the
+ * kernel holds.  (Whether a context takes the plan is the speed rule's business: csrc/hip/engine_plan.h, pw_pays; SAYURI_PW=1
+ * takes it wherever it applies.)
+ * sayuri_hip_last_pw_launches counts the conv_pw launches of the ctx's last forward: 0 under SAYURI_PW=0 and for every network
+ * without such layers. */
+int sayuri_hip_pw_plan(int n, const int* board_sizes, int max_board, int cin, int cout, int pieces, int out[4]);
+int sayuri_hip_last_pw_launches(const sayuri_hip_ctx* ctx);
+
 /* Release everything (replaces NNGraph::DestroyGraph, cuda_forward_pipe.cc:1092-1130). */
 void sayuri_hip_destroy(sayuri_hip_ctx* ctx);
 
@@ -263,9 +279,16 @@ int sayuri_hip_test_conv(int device, int use_fp16, int n, const int* board_sizes
 int sayuri_hip_test_conv_split(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act,
                                const float* x, const float* w, const float* bias, const float* res, float* y,
                                int channel_tiles, int strips);
+/* The fp16 1x1 case of sayuri_hip_test_conv through conv_pw.h, the route of a tower 1x1 layer: pieces = pieces per sample (0: the
+ * engine's choice for this batch).  -1 with a message for a layer outside the route (cout % 64, cin % 32) and for a forced cut
+ * that does not fit (a piece wider than 24 column tiles).  y's device buffer is pre-set to NaN.  Same results as
+ * sayuri_hip_test_conv's generic kernel, bit for bit; sayuri_hip_test_last_conv_kind reports 6. */
+int sayuri_hip_test_conv_pw(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act, const float* x,
+                            const float* w, const float* bias, const float* res, float* y, int pieces);
 /* Kernel family the calling thread's last sayuri_hip_test_conv / sayuri_hip_test_conv_split / sayuri_hip_test_conv_sx ran:
  * 0 generic implicit GEMM (conv_mfma.h), 1 LDS-DMA tiles across samples (conv_glds.h), 2 one workgroup per board
- * (conv_board.h), 3 depthwise, 4 many small workgroups (conv_split.h), 5 the split-channel SE convolution (conv_board_sx.h). */
+ * (conv_board.h), 3 depthwise, 4 many small workgroups (conv_split.h), 5 the split-channel SE convolution (conv_board_sx.h),
+ * 6 the pointwise tower kernel (conv_pw.h; sayuri_hip_test_conv_pw only). */
 int sayuri_hip_test_last_conv_kind(void);
 /* One squeeze-and-excitation unit through the se_pool / se_fc / se_scale kernels (reference SEUnit::Forward,
  * src/neural/blas/se_unit.cc:70-128): x, res (or NULL), y are [n][channels][bs*bs] like sayuri_hip_test_conv's tensors,

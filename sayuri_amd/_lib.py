@@ -72,6 +72,8 @@ HIP_ABI = {
     "sayuri_hip_latency_state": (_I, [_V]),
     "sayuri_hip_split_ring_plan": (_I, [_I, _IP, _I, _I, _I, _I]),
     "sayuri_hip_last_split_ring": (_I, [_V]),
+    "sayuri_hip_pw_plan": (_I, [_I, _IP, _I, _I, _I, _I, _IP]),
+    "sayuri_hip_last_pw_launches": (_I, [_V]),
     "sayuri_hip_destroy": (None, [_V]),
     "sayuri_hip_last_error": (ctypes.c_char_p, []),
     # the layer taps: device, (use_fp16,) n, board_sizes, max_board, shape ..., tensors
@@ -92,7 +94,11 @@ HIP_ABI = {
     "sayuri_hip_test_pack_input": (_I, [_I] * 3 + [_IP] + [_I] * 2 + [_F, _V, _I, _I] + [_IP] * 3 + [_I] * 4 + [ctypes.c_float, _I, _F]),
     "sayuri_hip_test_last_pack": (_I, [_IP]),
 }
-HIP_SYMBOLS = list(HIP_ABI)
+# A layer tap whose one Python caller is in the package (hipraw.conv_pw_layer), not in tests/_taps.py: same header, same binder.
+HIP_PACKAGE_TAPS = {
+    "sayuri_hip_test_conv_pw": (_I, [_I] * 2 + [_IP] + [_I] * 4 + [_F] * 5 + [_I]),
+}
+HIP_SYMBOLS = list(HIP_ABI) + list(HIP_PACKAGE_TAPS)
 
 _hip = None
 _host = None
@@ -120,7 +126,7 @@ def hip() -> ctypes.CDLL:
             path = fake
         lib = ctypes.CDLL(_require(path), mode=ctypes.RTLD_GLOBAL)
         # a device library may lack entry points (the stand-in knows the ABI it was written against and has no kernels to tap)
-        for name, (restype, argtypes) in HIP_ABI.items():
+        for name, (restype, argtypes) in {**HIP_ABI, **HIP_PACKAGE_TAPS}.items():
             if hasattr(lib, name):
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

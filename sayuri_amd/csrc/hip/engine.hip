@@ -1,5 +1,6 @@
 // engine.hip -- the C-ABI of include/sayuri_hip.h: one translation unit in three parts
-//   (conv_split.h: the many-small-workgroups convolution of a latency context, sayuri_hip_create_ex)
+//   (conv_split.h: the many-small-workgroups convolution of a latency context, sayuri_hip_create_ex;
+//    conv_pw.h: the tower's 1x1 convolutions of bottleneck-family networks as many small workgroups)
 //   engine_plan.h   kernel registries, environment switches, batch geometry, tile plans and the routing of a convolution to its
 //                   kernel family, the device images of the layers and the launch parameters the engine and the taps share
 //   engine_graph.h  Engine<T>: the per-GPU forward graph -- counterpart of the reference's CudaForwardPipe::NNGraph
@@ -28,6 +29,7 @@
 #include "conv_board.h"
 #include "conv_board_sx.h"
 #include "conv_split.h"
+#include "conv_pw.h"
 #include "conv_tower.h"
 #include "head_board.h"
 #include "small_ops.h"
@@ -211,6 +213,31 @@ int sayuri_hip_split_ring_plan(int n, const int* board_sizes, int max_board, int
     const SplitPlan sp = split_plan(hg, 0, n, ko_pad, strips, ring);
     if (!sp.ok) return fail("split_ring_plan: " + split_refusal(sp));
     return sp.stages;
+}
+int sayuri_hip_last_pw_launches(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_pw_launches() : 0; }
+// host arithmetic only: the geometry, the layer's weight rows and route_conv's plan, as a context and the conv_pw tap run them
+int sayuri_hip_pw_plan(int n, const int* board_sizes, int max_board, int cin, int cout, int pieces, int out[4]) {
+    using namespace sayuri;
+    if (n <= 0 || !board_sizes || max_board < 2 || cin <= 0 || cout <= 0 || pieces < 0 || !out) return fail("pw_plan: bad argument");
+    HostGeom hg;
+    hg.n = n;
+    hg.bsz.assign(board_sizes, board_sizes + n);
+    hg.off.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        if (hg.bsz[i] < 2 || hg.bsz[i] > max_board) return fail("pw_plan: bad board size");
+        hg.off[i + 1] = hg.off[i] + hg.bsz[i] * hg.bsz[i];
+    }
+    hg.total = hg.off[n];
+    int wmt, ko_pad;
+    conv_tile(round_up(cout, 32), true, &wmt, &ko_pad);
+    if (cout % kPwKO || cin % kChunk)
+        return fail("pw_plan: a layer of " + std::to_string(cin) + " -> " + std::to_string(cout) +
+                    " channels is not whole 32-channel chunks into whole 64-channel tiles: it keeps the generic kernel");
+    const PwAsk ask{cin, cout, round_up(cin, 32), 0, n, pieces, /*force=*/true};  // the plan itself: whether a context takes it is the speed rule's business (pw_pays)
+    const ConvRoute r = route_conv(true, 1, ko_pad, hg, BoardPlan{}, ConvOverride{}, 0, false, &ask);
+    if (!r.pw.ok) return fail("pw_plan: " + pw_refusal(r.pw));
+    out[0] = r.pw.pieces; out[1] = r.pw.grid; out[2] = r.pw.e->nj; out[3] = (int)r.pw.lds;
+    return 0;
 }
 // debugging tap (not part of the ABI, not in the header): activation buffer `buf` (0..5) of ticket 0 as it stands after the last forward
 extern "C" int sayuri_hip_debug_read_activations(sayuri_hip_ctx* ctx, int buf, void* host, size_t bytes) {

@@ -27,6 +27,7 @@ public:
     virtual int timed_stat(sayuri_hip_kernel_stat* row) = 0;
     virtual size_t device_bytes() const = 0;
     virtual int last_chains() const = 0;
+    virtual int last_pw_launches() const = 0;  // conv_pw.h launches of the last forward (0: none -- SAYURI_PW=0, or no such layer)
     virtual int last_split_ring() const = 0;  // the deepest weight ring of the last forward's split convolutions (0: none ran)
     virtual int tower_state() const = 0;  // 1: the persistent tower kernel is loaded, 0: one launch per layer (fallback)
     virtual int latency_state() const = 0;  // 1: a latency context (conv_split.h), 0: the default engine
@@ -104,6 +105,7 @@ public:
     hipEvent_t chain_fork_ = nullptr, chain_join_[kMaxChains] = {};
     int last_chains_ = 1;
     int last_split_ring_ = 0;
+    int last_pw_launches_ = 0;
     int chain_setup(int G) {
         if (!chain_fork_) HIP_OK(hipEventCreateWithFlags(&chain_fork_, hipEventDisableTiming));
         for (int g = 0; g < G; ++g) {
@@ -589,6 +591,7 @@ public:
     size_t device_bytes() const override { return dev_bytes_; }
     int last_chains() const override { return last_chains_; }
     int last_split_ring() const override { return last_split_ring_; }
+    int last_pw_launches() const override { return last_pw_launches_; }
     int tower_state() const override { return tower_fn_[0] != nullptr ? 1 : 0; }
     int latency_state() const override { return flags_.latency ? 1 : 0; }
     int debug_read(int buf, void* host, size_t bytes) override {
@@ -1048,11 +1051,21 @@ private:
     // The one-workgroup-per-board kernel applies to fp16 3x3 layers whenever the batch's boards fit its tiles, however empty
     // the tiles are: which convolution kernel a sample meets must not depend on its batch mates (a lone 9x9 board fills a fifth
     // of its tile; with the across-sample kernel it came out ~1e-4 away from the same position inside a larger batch).
-    const ConvRoute& route(const ConvLayerDev& L) {
+    // `tower_pw`: L is a tower 1x1 of forward f (block slots PRE_BTL / POST_BTL, mixer CONV1 / CONV2): the one kind of layer that
+    // may take conv_pw.h.  Its plan is for f's samples, so their range is part of the cache key (today a network with such a layer
+    // runs as one chain, chains_for_batch(): one range per geometry).
+    const ConvRoute& route(const ConvLayerDev& L, const Fwd* f = nullptr, bool tower_pw = false) {
         const BoardPlan& bp = plan();
-        auto it = route_cache_.find(L.k * 65536 + L.ko_pad);
-        if (it == route_cache_.end())
-            it = route_cache_.emplace(L.k * 65536 + L.ko_pad, route_conv(sizeof(T) == 2, L.k, L.ko_pad, geom_, bp, flags_.conv, flags_.board_kot, flags_.latency)).first;
+        const bool pw = tower_pw && f && L.k == 1 && flags_.pw != 0 && sizeof(T) == 2;
+        const long long key = pw ? (1ll << 62) | ((long long)(L.cin & 0x3fff) << 46) | ((long long)(L.cout & 0x3fff) << 32) |
+                                       ((long long)(f->n0 & 0xffff) << 16) | (f->ns & 0xffff)
+                                 : (long long)L.k * 65536 + L.ko_pad;
+        auto it = route_cache_.find(key);
+        if (it == route_cache_.end()) {
+            const PwAsk ask{L.cin, L.cout, L.cin_s, pw ? f->n0 : 0, pw ? f->ns : 0, flags_.pw_pieces, flags_.pw == 1};
+            it = route_cache_.emplace(key, route_conv(sizeof(T) == 2, L.k, L.ko_pad, geom_, bp, flags_.conv, flags_.board_kot, flags_.latency,
+                                                      pw ? &ask : nullptr)).first;
+        }
         return it->second;
     }
 
@@ -1214,8 +1227,21 @@ private:
         return timed(f, name, cost.flops, cost.bytes, [&] { split_launch(sp, q, f.stream); });
     }
 
-    int conv(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
-        const ConvRoute& r = route(L);
+    // A tower 1x1 layer as many small workgroups (conv_pw.h): one launch over the forward's samples, the cut chosen from the batch
+    // geometry (the route's PwPlan).  The bits of the generic kernel.
+    int conv_pw(Fwd& f, const char* name, const ConvLayerDev& L, const PwPlan& pp, const T* in, T* out, const T* res, int act) {
+        PwParams q;
+        std::memset(&q, 0, sizeof(q));
+        conv_params(q.c, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 1, act);
+        pw_params(q, pp, f.n0);
+        ++last_pw_launches_;
+        const ConvCost cost = conv_cost(f.px, L.cin, L.cout, 1, res, sizeof(T));
+        return timed(f, name, cost.flops, cost.bytes, [&] { pw_launch(pp, q, f.stream); });
+    }
+
+    int conv(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act, bool tower_pw = false) {
+        const ConvRoute& r = route(L, &f, tower_pw);
+        if (r.family == kConvPw) return conv_pw(f, name, L, r.pw, in, out, res, act);
         if (r.family == kConvSplit) return conv_split(f, name, L, in, out, res, act);
         if (const BoardEntry* be = r.board) {
             const int bkt = r.tiles;
@@ -1373,6 +1399,7 @@ private:
         const int G = chains_for_batch();
         last_chains_ = G;
         last_split_ring_ = 0;
+        last_pw_launches_ = 0;
         rows_reset();
         IoSlot& io = io_[t];
         Fwd f{t, io, compute_[t]};
@@ -1481,25 +1508,25 @@ private:
                 f.give(t0);
             } else if (bd.type == SAYURI_BLOCK_BOTTLENECK) {
                 const int t0 = f.take(), t1 = f.take();
-                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), buf[x], buf[t0], nullptr, act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), buf[x], buf[t0], nullptr, act, true)) return -1;
                 if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[t0], buf[t1], nullptr, act)) return -1;
                 if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t1], buf[t0], nullptr, act)) return -1;
-                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), buf[t0], buf[y], se ? nullptr : buf[x], last_act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), buf[t0], buf[y], se ? nullptr : buf[x], last_act, true)) return -1;
                 f.give(t0); f.give(t1);
             } else if (bd.type == SAYURI_BLOCK_NESTED_BOTTLENECK) {
                 const int r1 = f.take(), t0 = f.take(), t1 = f.take();
-                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), buf[x], buf[r1], nullptr, act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_PRE_BTL)), buf[x], buf[r1], nullptr, act, true)) return -1;
                 if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[r1], buf[t0], nullptr, act)) return -1;
                 if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t0], buf[t1], buf[r1], act)) return -1;
                 if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV3)), buf[t1], buf[t0], nullptr, act)) return -1;
                 if (conv(f, "conv3x3_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV4)), buf[t0], buf[r1], buf[t1], act)) return -1;
-                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), buf[r1], buf[y], se ? nullptr : buf[x], last_act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL)), buf[r1], buf[y], se ? nullptr : buf[x], last_act, true)) return -1;
                 f.give(r1); f.give(t0); f.give(t1);
             } else {  // mixer: x' = act(dw(x)+b) + x is the new skip
                 const int s2 = f.take(), t1 = f.take();
                 if (depthwise(f, "depthwise", cv(SAYURI_L_BLOCK(b, SAYURI_S_DW_CONV)), buf[x], buf[s2], buf[x], act)) return -1;
-                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[s2], buf[t1], nullptr, act)) return -1;
-                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t1], buf[y], se ? nullptr : buf[s2], last_act)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1)), buf[s2], buf[t1], nullptr, act, true)) return -1;
+                if (conv(f, "conv1x1_tower", cv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2)), buf[t1], buf[y], se ? nullptr : buf[s2], last_act, true)) return -1;
                 f.give(t1);
                 f.give(x);
                 x = s2;
@@ -1692,7 +1719,7 @@ private:
     hipEvent_t tick_ev_[2] = {nullptr, nullptr};
     HostGeom geom_;
     std::vector<int> prev_bsz_;
-    std::map<int, ConvRoute> route_cache_;  // by (k, ko_pad), for the current batch geometry
+    std::map<long long, ConvRoute> route_cache_;  // by (k, ko_pad) -- a tower 1x1 that may take conv_pw.h: by (cin, cout, first sample, samples) --, for the current batch geometry
     std::map<int, SplitPlan> split_cache_;  // latency context: by ko_pad, for the current batch geometry
     BoardPlan board_plan_;
     HeadFn head_fn_ = nullptr;

@@ -111,6 +111,13 @@ static const SplitEntry kSplitEntries[] = {
     {1, kSplitDeepStages, &conv_split_kernel<1, kSplitDeepStages>}, {2, kSplitDeepStages, &conv_split_kernel<2, kSplitDeepStages>},
     {3, kSplitDeepStages, &conv_split_kernel<3, kSplitDeepStages>},
 };
+// the tower's 1x1 convolutions of bottleneck-family networks as many small workgroups (conv_pw.h), by column tiles per wave
+// (ascending: pw_plan takes the first that is wide enough; a piece has at most kPwMaxCols = 24 column tiles)
+typedef void (*PwFn)(const PwParams);
+struct PwEntry { int nj; PwFn fn; };
+static const PwEntry kPwEntries[] = {
+    {1, &conv_pw_kernel<1>}, {2, &conv_pw_kernel<2>}, {3, &conv_pw_kernel<3>}, {6, &conv_pw_kernel<6>}, {12, &conv_pw_kernel<12>},
+};
 // head_board_kernel variants: {row tiles, trunk chunks in flight}; the first that fits the LDS is used (head_board_fits)
 typedef void (*HeadFn)(const HeadBoardParams);
 struct HeadEntry { int rt, depth; HeadFn fn; };
@@ -126,6 +133,7 @@ static void enable_big_lds_glds() {
     for (const auto& e : kHeadEntries) (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)&conv_board_sx_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     for (const auto& e : kSplitEntries) (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    for (const auto& e : kPwEntries) (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     for (const auto& e : kBoardEntries) {
         (void)hipFuncSetAttribute((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
         if (e.fn_se) (void)hipFuncSetAttribute((const void*)e.fn_se, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
@@ -149,6 +157,9 @@ static void enable_big_lds_glds() {
 //   SAYURI_LATENCY_RING=n         latency context: n weight stages in every split convolution instead of the engine's choice (split_ring);
 //                                 3 is the three-stage ring everywhere; a depth the chosen variant does not have is refused
 //   SAYURI_SE_ONE=0 | 1           the SE unit outside a convolution as se_pool / se_fc / se_scale everywhere | as one launch everywhere
+//   SAYURI_PW=0 | 1               the tower's 1x1 convolutions on the generic kernel everywhere | on conv_pw.h wherever it applies,
+//                                 instead of where the speed rule says it pays (pw_pays; same bits either way)
+//   SAYURI_PW_PIECES=n            conv_pw.h: n pieces per sample in every launch instead of the engine's choice (pw_plan)
 // The other switches are described at their fields below.
 struct ConvOverride {
     bool v0 = false, no_board = false;
@@ -163,6 +174,9 @@ struct EngineFlags {
                                        // Engine::se_unit())
     int latency_split = 0;             // SAYURI_LATENCY_SPLIT=n: strips per board (0: split_auto)
     int latency_ring = 0;              // SAYURI_LATENCY_RING=n: weight stages of the split kernels (0: split_ring)
+    int pw = -1;                       // SAYURI_PW: unset (-1) a tower 1x1 takes conv_pw.h where the rule says it pays (route_conv, pw_pays);
+                                       // 0: nowhere; 1: wherever the kernel applies
+    int pw_pieces = 0;                 // SAYURI_PW_PIECES=n: pieces per sample (0: pw_auto)
     int se_one = -1;                   // SAYURI_SE_ONE: an SE unit that runs as kernels of its own is ONE launch (se_unit_kernel, small_ops.h)
                                        // instead of se_pool / se_fc / se_scale -- unset (-1): in a latency context (Engine::se_unit()'s
                                        // rule); 0: nowhere; 1: wherever Engine::se_unit() or the se_unit tap would run the three.  Same
@@ -212,6 +226,8 @@ struct EngineFlags {
         if (const char* e = getenv("SAYURI_LATENCY_SPLIT")) f.latency_split = std::max(0, atoi(e));
         if (const char* e = getenv("SAYURI_LATENCY_RING")) f.latency_ring = atoi(e);  // (split_plan refuses what no kernel has)
         if (const char* e = getenv("SAYURI_SE_ONE")) f.se_one = atoi(e) != 0;
+        if (const char* e = getenv("SAYURI_PW")) f.pw = atoi(e) != 0;
+        if (const char* e = getenv("SAYURI_PW_PIECES")) f.pw_pieces = std::max(0, atoi(e));
 #ifdef SAYURI_EXPERIMENTS
         if (const char* e = getenv("SAYURI_BOARD_KOT")) f.board_kot = atoi(e);
         if (const char* e = getenv("SAYURI_ACT_OVERRIDE")) f.act_override = atoi(e);
@@ -391,16 +407,89 @@ static const BoardEntry* pick_board(const BoardPlan& bp, int ko_pad, int* kot_ti
 // (`glds`, `tiles` pixel tiles), everything else the generic conv_mfma kernel (pick_tile).  The values are what
 // sayuri_hip_test_last_conv_kind reports (kConvBoardSx: never a route -- a block's last convolution with its SE unit inside,
 // Engine::conv_sx; the tap sayuri_hip_test_conv_sx reports it).
-enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4, kConvBoardSx = 5 };
+// kConvPw: a TOWER 1x1 layer of the fp16 engine (conv_pw.h), in a default and in a latency context alike.
+enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4, kConvBoardSx = 5, kConvPw = 6 };
+
+// The many-small-workgroups plan of a tower 1x1 layer (conv_pw.h) for the samples [n0, n0 + ns): how many pieces a sample's
+// pixels are cut into, the grid, the kernel variant and its LDS.  Host arithmetic only.
+// The rule (pieces == 0): as many pieces per sample as keep the launch near ONE round of the chip -- kPwRound / (samples x channel
+// tiles), at least one, a piece never smaller than one column tile (pw_cols) nor wider than the widest variant -- so a lone 19x19
+// board on 128 output channels is cut into one piece per column tile and a batch of 256 gets one piece per sample.  A round is
+// counted as three workgroups per CU: the thin variants (NJ <= 3, at most 48 KiB of LDS) are co-resident three to a CU.  The
+// constant is a supposition -- no measurement compares this cut with 256 / (samples x channel tiles) -- in the direction the rows
+// show: few wide pieces are what the kernel is bad at (DESIGN.md Kernel 1i: at 256 boards one piece per sample takes 1.15 to 1.30
+// of the generic kernel's forward where four pieces take 0.78 to 0.81).  It decides the speed only: the
+// results do not depend on the cut.  pieces == n forces n (SAYURI_PW_PIECES, the tap): a cut whose pieces
+// would be wider than the widest variant holds is refused, not narrowed.
+struct PwPlan {
+    bool ok = false;
+    int pieces = 0, pmax = 0, kts = 0, grid = 0, wide = 0;  // wide: the column tiles of the piece that did not fit (refusal)
+    const PwEntry* e = nullptr;
+    size_t lds = 0;
+};
+constexpr int kPwRound = 3 * kNumCU;
+static int pw_auto(int ns, int kts) { return std::max(1, kPwRound / std::max(1, ns * kts)); }
+static std::string pw_refusal(const PwPlan& pp) {
+    return pp.wide ? "a piece of " + std::to_string(pp.wide) + " column tiles is wider than the kernel's " + std::to_string(kPwMaxCols) +
+                         " (SAYURI_PW_PIECES / pieces too small for this board)"
+                   : std::string("no pointwise plan for this layer or batch geometry");
+}
+static PwPlan pw_plan(const HostGeom& geom, int n0, int ns, int ko_pad, int cin_s, int pieces) {
+    PwPlan pp;
+    if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || ko_pad <= 0 || ko_pad % kPwKO || cin_s <= 0 || cin_s % kChunk || pieces < 0) return pp;
+    pp.kts = ko_pad / kPwKO;
+    pp.pieces = pieces > 0 ? pieces : pw_auto(ns, pp.kts);
+    int max_cols = 0;
+    for (int s = n0; s < n0 + ns; ++s) {
+        const int bs = geom.bsz[s], ncol = (bs * bs + 15) / 16, cp = pw_cols(bs, pp.pieces, /*cap=*/pieces == 0);
+        if (cp > kPwMaxCols) { pp.wide = cp; return pp; }
+        pp.pmax = std::max(pp.pmax, (ncol + cp - 1) / cp);
+        max_cols = std::max(max_cols, cp);
+    }
+    for (const auto& e : kPwEntries)
+        if (!pp.e && 2 * e.nj >= max_cols) pp.e = &e;
+    if (!pp.e) return pp;
+    pp.lds = pw_lds_bytes(pp.e->nj);
+    pp.grid = ns * pp.pmax * pp.kts;
+    pp.ok = pp.lds <= kMaxLds;
+    return pp;
+}
+// The kernel's part of a launch (conv_params fills q.c before).  (The kernel caps a piece at the widest variant as the rule does;
+// a forced cut that the cap would change was refused above.)
+static void pw_params(PwParams& q, const PwPlan& pp, int n0) {
+    q.c.npos = 0; q.c.num_pix_tiles = 0;
+    q.pieces = pp.pieces; q.pmax = pp.pmax; q.kts = pp.kts; q.n0 = n0;
+}
+static void pw_launch(const PwPlan& pp, const PwParams& q, hipStream_t s) {
+    hipLaunchKernelGGL(pp.e->fn, dim3(pp.grid), dim3(256), pp.lds, s, q);
+}
+// What route_conv needs to know of a 1x1 layer to give it conv_pw.h: null for every layer that is not a tower 1x1 (block slots
+// PRE_BTL, POST_BTL, mixer CONV1 / CONV2) and under SAYURI_PW=0.
+struct PwAsk { int cin, cout, cin_s, n0, ns, pieces; bool force; };  // force: SAYURI_PW=1, the taps -- the speed rule is not asked
+// The speed rule of the route: the regimes where conv_pw.h is ahead of the generic kernel beyond the method's spread -- a launch
+// whose samples get at least three pieces each, samples x channel tiles <= 256.  Measured (DESIGN.md Kernel 1i,
+// profiles/r12_pw_conv.json): up to 64 boards of 19x19 every tower 1x1 of the 256 / 128 and 256-channel mixer networks qualifies
+// and a forward takes 0.41 to 0.88 of its time on the generic kernel; with one or two pieces a sample (128 boards on three or more
+// channel tiles, 256 boards) the kernel is level or 10 to 30 % of a forward behind.  Decides speed only.
+static bool pw_pays(int ns, int kts) { return pw_auto(ns, kts) >= 3; }
+
 struct ConvRoute {
     ConvFamily family = kConvGeneric;
     const BoardEntry* board = nullptr;
     const GldsEntry* glds = nullptr;
     int tiles = 0;
+    PwPlan pw;  // kConvPw
 };
 static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, const BoardPlan& plan, const ConvOverride& ov, int force_kot = 0,
-                            bool latency = false) {
+                            bool latency = false, const PwAsk* pw = nullptr) {
     ConvRoute r;
+    // a tower 1x1 of whole 64-channel tiles over whole 32-channel chunks: many small workgroups (conv_pw.h) where the plan fits
+    // and the rule says it pays
+    if (fp16 && k == 1 && pw && pw->cout % kPwKO == 0 && pw->cin % kChunk == 0 && ko_pad % kPwKO == 0) {
+        r.pw = pw_plan(geom, pw->n0, pw->ns, ko_pad, pw->cin_s, pw->pieces);
+        if (r.pw.ok && (pw->force || pw_pays(pw->ns, r.pw.kts))) r.family = kConvPw;
+        return r;
+    }
     if (!fp16 || k != 3) return r;
     // a latency context: many small workgroups (`split`; the plan is split_plan's) for every batch; a layer whose weight rows
     // are not whole 64-channel tiles keeps the route below

@@ -202,6 +202,46 @@ static int test_conv_split_impl(int device, int n, const int* board_sizes, int m
     return nhwc_to_nchw(tg, dy, cout, cout_s, y);
 }
 
+// The fp16 1x1 case of test_conv_impl through conv_pw.h (the route of a tower 1x1 layer): the engine's image, route_conv's plan.
+// pieces: pieces per sample (0: the engine's choice for this batch).  y's device buffer starts as NaN: what comes back finite was
+// written.
+static int test_conv_pw_impl(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act, const float* x,
+                             const float* w, const float* bias, const float* res, float* y, int pieces) {
+    typedef f16 T;
+    HIP_OK(hipSetDevice(device));
+    enable_big_lds_glds();
+    if (cin <= 0 || cout <= 0 || pieces < 0) return fail("test_conv_pw: bad argument");
+    TestArena A;
+    TestGeom tg;
+    if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
+    const int cin_s = round_up(cin, 32), cout_s = round_up(cout, 32);
+    int wmt, ko_pad;
+    conv_tile(cout_s, true, &wmt, &ko_pad);
+    const PwAsk ask{cin, cout, cin_s, 0, n, pieces, /*force=*/true};
+    const ConvRoute r = route_conv(true, 1, ko_pad, tg.hg, BoardPlan{}, ConvOverride{}, 0, false, &ask);
+    if (cout % kPwKO || cin % kChunk)
+        return fail("test_conv_pw: a layer of " + std::to_string(cin) + " -> " + std::to_string(cout) +
+                    " channels is not whole 32-channel chunks into whole 64-channel tiles: it keeps the generic kernel");
+    if (!r.pw.ok) return fail("test_conv_pw: " + pw_refusal(r.pw));
+    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, cin, cin_s));
+    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, cout, cout_s)) : nullptr;
+    const size_t y_bytes = (size_t)n * tg.slot * cout_s * sizeof(T);
+    T* dy = (T*)A.alloc(y_bytes);
+    const T* dw = A.upload(conv_image<T>(w, cin, cout, 1, ko_pad));
+    const float* db = A.upload(padded_bias(bias, cout, ko_pad));
+    if (!dx || !dy || (res && !dres) || !dw || !db) return fail("test_conv_pw: hipMalloc failed");
+    HIP_OK(hipMemset(dy, 0xff, y_bytes));  // fp16 0xffff: a NaN
+    g_test_conv_kind = kConvPw;
+    PwParams q;
+    std::memset(&q, 0, sizeof(q));
+    conv_params(q.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 1, act);
+    pw_params(q, r.pw, 0);
+    pw_launch(r.pw, q, nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    return nhwc_to_nchw(tg, dy, cout, cout_s, y);
+}
+
 template <typename T>
 static int test_se_unit_impl(int device, int n, const int* board_sizes, int max_board, int C, int se, int act, const float* x,
                              const float* res, const float* w1, const float* b1, const float* w2, const float* b2, float* y,
@@ -819,6 +859,12 @@ extern "C" int sayuri_hip_test_conv_split(int device, int n, const int* board_si
                                           const float* w, const float* bias, const float* res, float* y, int channel_tiles, int strips) {
     if (!board_sizes || !x || !w || !y || n <= 0) return fail("test_conv_split: bad argument");
     return test_conv_split_impl(device, n, board_sizes, max_board, cin, cout, act, x, w, bias, res, y, channel_tiles, strips);
+}
+
+extern "C" int sayuri_hip_test_conv_pw(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act, const float* x,
+                                       const float* w, const float* bias, const float* res, float* y, int pieces) {
+    if (!board_sizes || !x || !w || !y || n <= 0) return fail("test_conv_pw: bad argument");
+    return test_conv_pw_impl(device, n, board_sizes, max_board, cin, cout, act, x, w, bias, res, y, pieces);
 }
 
 extern "C" int sayuri_hip_test_last_conv_kind(void) { return sayuri::g_test_conv_kind; }

@@ -152,3 +152,21 @@ def hip_forward_packed_symm_raw(ctx: int, records, binary: int, board_sizes, src
     _ok(_lib.hip().sayuri_hip_forward_packed_symm(ctx, sym.shape[0], addr, n_records, binary, ip(bsz), None if sr is None else ip(sr),
                                                   ip(sym), *map(fp, out)))
     return out
+
+
+def conv_pw_layer(board_sizes, cin: int, cout: int, act: int, xs, w, bias=None, res=None, pieces: int = 0, max_board: int = 19):
+    """The layer tap of the tower's pointwise kernel (sayuri_hip_test_conv_pw, csrc/hip/conv_pw.h): one fp16 1x1 layer on host
+    tensors, no context.  xs / res: per-sample [C][b*b] arrays (res None: no residual), w [cout][cin], pieces per sample (0: the
+    engine's choice).  -> (rc, per-sample [cout][b*b] outputs that start as NaN, sayuri_hip_test_last_conv_kind); rc -1 is a
+    refusal whose message sayuri_hip_last_error holds."""
+    lib = _lib.hip()
+    bsz = np.asarray(board_sizes, np.int32)
+    cat = lambda arrs: None if arrs is None else fp(np.concatenate([np.ascontiguousarray(a, np.float32).ravel() for a in arrs]))
+    one = lambda a: None if a is None else fp(np.ascontiguousarray(a, np.float32))
+    y = np.full(cout * int((bsz.astype(np.int64) ** 2).sum()), np.nan, np.float32)
+    rc = lib.sayuri_hip_test_conv_pw(0, len(bsz), ip(bsz), max_board, cin, cout, act, cat(xs), one(w), one(bias), cat(res), fp(y), pieces)
+    outs, off = [], 0
+    for b in bsz:
+        outs.append(y[off:off + cout * b * b].reshape(cout, b * b))
+        off += cout * b * b
+    return rc, outs, lib.sayuri_hip_test_last_conv_kind()
