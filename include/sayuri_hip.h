@@ -257,6 +257,21 @@ int sayuri_hip_last_split_ring(const sayuri_hip_ctx* ctx);
 int sayuri_hip_pw_plan(int n, const int* board_sizes, int max_board, int cin, int cout, int pieces, int out[4]);
 int sayuri_hip_last_pw_launches(const sayuri_hip_ctx* ctx);
 
+/* The depthwise k x k convolutions (a mixer block's DW_CONV, the RepLK policy head's P_DW_CONV) on LDS (csrc/hip/conv_dw.h:
+ * conv_dw_kernel<k>, k = 3, 5, 7).  In the fp16 engine such a layer runs as many small independent workgroups -- one per (sample,
+ * slice of 64 or 32 channels, strip of rows) that stages its rows, the halo rows inside the board and the slice's weights into LDS
+ * once -- where the engine's speed rule says it pays (csrc/hip/engine_plan.h, dw_pays), with the bits of depthwise_kernel.
+ * SAYURI_DW=0 keeps depthwise_kernel everywhere, SAYURI_DW=1 takes conv_dw.h wherever it applies; SAYURI_DW_STRIPS=n forces n strips
+ * per sample.  The cut decides speed only.
+ * sayuri_hip_dw_plan is host arithmetic (no device is touched): out = {channels of a slice, strips asked for per sample (a board
+ * with fewer rows has one strip per row), grid, LDS bytes} of a batch of n boards and a layer of `channels` channels (stride: the
+ * next multiple of 32) under `strips` strips per sample, 0 meaning the engine's choice; -1 with a message where no plan applies --
+ * k other than 3, 5, 7, more strips than the largest board has rows, an item beyond the kernel's 64 KiB of LDS.
+ * sayuri_hip_last_dw_launches counts the conv_dw launches of the ctx's last forward: 0 under SAYURI_DW=0 and for every network
+ * without a depthwise layer. */
+int sayuri_hip_dw_plan(int n, const int* board_sizes, int max_board, int channels, int k, int strips, int out[4]);
+int sayuri_hip_last_dw_launches(const sayuri_hip_ctx* ctx);
+
 /* Release everything (replaces NNGraph::DestroyGraph, cuda_forward_pipe.cc:1092-1130). */
 void sayuri_hip_destroy(sayuri_hip_ctx* ctx);
 
@@ -285,10 +300,23 @@ int sayuri_hip_test_conv_split(int device, int n, const int* board_sizes, int ma
  * sayuri_hip_test_conv's generic kernel, bit for bit; sayuri_hip_test_last_conv_kind reports 6. */
 int sayuri_hip_test_conv_pw(int device, int n, const int* board_sizes, int max_board, int cin, int cout, int act, const float* x,
                             const float* w, const float* bias, const float* res, float* y, int pieces);
+/* One fp16 depthwise k x k layer through conv_dw.h: x, res (or NULL: no residual; given, it is added BEHIND the activation, as
+ * sayuri_hip_test_conv's post_residual = 1 does), y are [n][channels][bs*bs]; w [channels][k*k]; strips = strips per sample (0:
+ * the engine's choice for this batch).  use_fp16 must be 1: the fp32 engine keeps depthwise_kernel.  -1 with a message for what
+ * the route does not cover (k other than 3, 5, 7, fp32, a forced cut that does not fit).  y's device buffer is pre-set to NaN.
+ * Same results as sayuri_hip_test_conv(depthwise = 1), bit for bit; sayuri_hip_test_last_conv_kind reports 7. */
+int sayuri_hip_test_conv_dw(int device, int use_fp16, int n, const int* board_sizes, int max_board, int channels, int k, int act,
+                            const float* x, const float* w, const float* bias, const float* res, int strips, float* y);
+/* The pad channels [channels, stride) of every board pixel after the calling thread's last sayuri_hip_test_conv_dw, as raw fp16
+ * bits in sample-major, pixel-major order: which = 0 what conv_dw_kernel stored into its NaN-pre-set buffer, which = 1 what
+ * depthwise_kernel stores on the same operands (the tap runs it into a NaN-pre-set buffer of its own).  Copies up to cap values;
+ * returns how many there are (0: channels is a multiple of 32), -1 on a bad argument. */
+int sayuri_hip_test_last_dw_pad(int which, unsigned short* bits, int cap);
 /* Kernel family the calling thread's last sayuri_hip_test_conv / sayuri_hip_test_conv_split / sayuri_hip_test_conv_sx ran:
  * 0 generic implicit GEMM (conv_mfma.h), 1 LDS-DMA tiles across samples (conv_glds.h), 2 one workgroup per board
  * (conv_board.h), 3 depthwise, 4 many small workgroups (conv_split.h), 5 the split-channel SE convolution (conv_board_sx.h),
- * 6 the pointwise tower kernel (conv_pw.h; sayuri_hip_test_conv_pw only). */
+ * 6 the pointwise tower kernel (conv_pw.h; sayuri_hip_test_conv_pw only), 7 the depthwise kernel on LDS (conv_dw.h;
+ * sayuri_hip_test_conv_dw only). */
 int sayuri_hip_test_last_conv_kind(void);
 /* One squeeze-and-excitation unit through the se_pool / se_fc / se_scale kernels (reference SEUnit::Forward,
  * src/neural/blas/se_unit.cc:70-128): x, res (or NULL), y are [n][channels][bs*bs] like sayuri_hip_test_conv's tensors,

@@ -74,6 +74,8 @@ HIP_ABI = {
     "sayuri_hip_last_split_ring": (_I, [_V]),
     "sayuri_hip_pw_plan": (_I, [_I, _IP, _I, _I, _I, _I, _IP]),
     "sayuri_hip_last_pw_launches": (_I, [_V]),
+    "sayuri_hip_dw_plan": (_I, [_I, _IP, _I, _I, _I, _I, _IP]),
+    "sayuri_hip_last_dw_launches": (_I, [_V]),
     "sayuri_hip_destroy": (None, [_V]),
     "sayuri_hip_last_error": (ctypes.c_char_p, []),
     # the layer taps: device, (use_fp16,) n, board_sizes, max_board, shape ..., tensors
@@ -97,6 +99,8 @@ HIP_ABI = {
 # A layer tap whose one Python caller is in the package (hipraw.conv_pw_layer), not in tests/_taps.py: same header, same binder.
 HIP_PACKAGE_TAPS = {
     "sayuri_hip_test_conv_pw": (_I, [_I] * 2 + [_IP] + [_I] * 4 + [_F] * 5 + [_I]),
+    "sayuri_hip_test_conv_dw": (_I, [_I] * 3 + [_IP] + [_I] * 4 + [_F] * 4 + [_I, _F]),
+    "sayuri_hip_test_last_dw_pad": (_I, [_I, ctypes.POINTER(ctypes.c_uint16), _I]),
 }
 HIP_SYMBOLS = list(HIP_ABI) + list(HIP_PACKAGE_TAPS)
 

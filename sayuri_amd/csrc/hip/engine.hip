@@ -1,6 +1,7 @@
 // engine.hip -- the C-ABI of include/sayuri_hip.h: one translation unit in three parts
 //   (conv_split.h: the many-small-workgroups convolution of a latency context, sayuri_hip_create_ex;
-//    conv_pw.h: the tower's 1x1 convolutions of bottleneck-family networks as many small workgroups)
+//    conv_pw.h: the tower's 1x1 convolutions of bottleneck-family networks as many small workgroups;
+//    conv_dw.h: the depthwise convolutions of mixer blocks and the RepLK head on LDS)
 //   engine_plan.h   kernel registries, environment switches, batch geometry, tile plans and the routing of a convolution to its
 //                   kernel family, the device images of the layers and the launch parameters the engine and the taps share
 //   engine_graph.h  Engine<T>: the per-GPU forward graph -- counterpart of the reference's CudaForwardPipe::NNGraph
@@ -30,6 +31,7 @@
 #include "conv_board_sx.h"
 #include "conv_split.h"
 #include "conv_pw.h"
+#include "conv_dw.h"
 #include "conv_tower.h"
 #include "head_board.h"
 #include "small_ops.h"
@@ -237,6 +239,25 @@ int sayuri_hip_pw_plan(int n, const int* board_sizes, int max_board, int cin, in
     const ConvRoute r = route_conv(true, 1, ko_pad, hg, BoardPlan{}, ConvOverride{}, 0, false, &ask);
     if (!r.pw.ok) return fail("pw_plan: " + pw_refusal(r.pw));
     out[0] = r.pw.pieces; out[1] = r.pw.grid; out[2] = r.pw.e->nj; out[3] = (int)r.pw.lds;
+    return 0;
+}
+int sayuri_hip_last_dw_launches(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_dw_launches() : 0; }
+// host arithmetic only: the geometry and dw_plan, as a context and the conv_dw tap run them
+int sayuri_hip_dw_plan(int n, const int* board_sizes, int max_board, int channels, int k, int strips, int out[4]) {
+    using namespace sayuri;
+    if (n <= 0 || !board_sizes || max_board < 2 || channels <= 0 || strips < 0 || !out) return fail("dw_plan: bad argument");
+    HostGeom hg;
+    hg.n = n;
+    hg.bsz.assign(board_sizes, board_sizes + n);
+    hg.off.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        if (hg.bsz[i] < 2 || hg.bsz[i] > max_board) return fail("dw_plan: bad board size");
+        hg.off[i + 1] = hg.off[i] + hg.bsz[i] * hg.bsz[i];
+    }
+    hg.total = hg.off[n];
+    const DwPlan dp = dw_plan(hg, 0, n, round_up(channels, 32), k, strips);
+    if (!dp.ok) return fail("dw_plan: " + dp.why);
+    out[0] = dp.sp * 8; out[1] = dp.strips; out[2] = dp.grid; out[3] = (int)dp.lds;
     return 0;
 }
 // debugging tap (not part of the ABI, not in the header): activation buffer `buf` (0..5) of ticket 0 as it stands after the last forward

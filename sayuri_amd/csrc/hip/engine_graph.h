@@ -28,6 +28,7 @@ public:
     virtual size_t device_bytes() const = 0;
     virtual int last_chains() const = 0;
     virtual int last_pw_launches() const = 0;  // conv_pw.h launches of the last forward (0: none -- SAYURI_PW=0, or no such layer)
+    virtual int last_dw_launches() const = 0;  // conv_dw.h launches of the last forward (0: none -- SAYURI_DW=0, or no depthwise layer)
     virtual int last_split_ring() const = 0;  // the deepest weight ring of the last forward's split convolutions (0: none ran)
     virtual int tower_state() const = 0;  // 1: the persistent tower kernel is loaded, 0: one launch per layer (fallback)
     virtual int latency_state() const = 0;  // 1: a latency context (conv_split.h), 0: the default engine
@@ -106,6 +107,8 @@ public:
     int last_chains_ = 1;
     int last_split_ring_ = 0;
     int last_pw_launches_ = 0;
+    int last_dw_launches_ = 0;
+    bool dw_refusal_said_ = false;  // the one-time note of a forced SAYURI_DW_STRIPS that dw_plan refused
     int chain_setup(int G) {
         if (!chain_fork_) HIP_OK(hipEventCreateWithFlags(&chain_fork_, hipEventDisableTiming));
         for (int g = 0; g < G; ++g) {
@@ -371,6 +374,7 @@ public:
             tile_cache_.clear();
             route_cache_.clear();
             split_cache_.clear();
+            dw_cache_.clear();
             board_plan_valid_ = false;
         }
         IoSlot& io = io_[t];
@@ -592,6 +596,7 @@ public:
     int last_chains() const override { return last_chains_; }
     int last_split_ring() const override { return last_split_ring_; }
     int last_pw_launches() const override { return last_pw_launches_; }
+    int last_dw_launches() const override { return last_dw_launches_; }
     int tower_state() const override { return tower_fn_[0] != nullptr ? 1 : 0; }
     int latency_state() const override { return flags_.latency ? 1 : 0; }
     int debug_read(int buf, void* host, size_t bytes) override {
@@ -1297,7 +1302,33 @@ private:
         return timed(f, name, cost.flops, cost.bytes, [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(512), lds, f.stream, p); });
     }
 
+    // A depthwise layer (a mixer block's DW_CONV, the RepLK head's P_DW_CONV).  The one place that chooses its kernel: conv_dw.h
+    // (LDS staging, many small workgroups; the plan is dw_plan's for the forward's samples) in the fp16 engine for k = 3, 5, 7
+    // where the plan fits and dw_pays says it pays, depthwise_kernel otherwise -- the fp32 engine, another k, a plan that does
+    // not fit.  SAYURI_DW=0 / 1 force a kernel.  The rule decides speed only: the bits are the same either way.
     int depthwise(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
+        const double flops = 2.0 * f.px * L.cout * L.k * L.k, bytes = sizeof(T) * f.px * L.cout * (res ? 3 : 2);
+        if constexpr (sizeof(T) == 2) {
+            if (flags_.dw != 0) {
+                const long long key = ((long long)L.cout_s << 40) | ((long long)L.k << 32) | ((long long)(f.n0 & 0xffff) << 16) | (f.ns & 0xffff);
+                auto it = dw_cache_.find(key);
+                if (it == dw_cache_.end()) it = dw_cache_.emplace(key, dw_plan(geom_, f.n0, f.ns, L.cout_s, L.k, flags_.dw_strips)).first;
+                const DwPlan& dp = it->second;
+                if (!dp.ok && flags_.dw_strips && !dw_refusal_said_) {  // a forced cut that is refused must not pass for a measurement of it
+                    dw_refusal_said_ = true;
+                    std::fprintf(stderr, "[sayuri_hip] SAYURI_DW_STRIPS=%d: %s: the layer keeps depthwise_kernel\n", flags_.dw_strips, dp.why.c_str());
+                }
+                if (dp.ok && (flags_.dw == 1 || dw_pays())) {
+                    DwParams q;
+                    std::memset(&q, 0, sizeof(q));
+                    q.x = in; q.res = res; q.out = out; q.wt = (const float*)L.w; q.bias = L.bias;
+                    q.g = dgeom(f.io); q.C = L.cout; q.cs = L.cout_s; q.act = act;
+                    dw_params(q, dp, f.n0);
+                    ++last_dw_launches_;
+                    return timed(f, name, flops, bytes, [&] { dw_launch(dp, q, f.stream); });
+                }
+            }
+        }
         const int EPP = ElemTraits<T>::kPieceElems;
         const size_t total = (size_t)geom_.total * (L.cout_s / EPP);
         const int grid = (int)((total + 255) / 256);
@@ -1400,6 +1431,7 @@ private:
         last_chains_ = G;
         last_split_ring_ = 0;
         last_pw_launches_ = 0;
+        last_dw_launches_ = 0;
         rows_reset();
         IoSlot& io = io_[t];
         Fwd f{t, io, compute_[t]};
@@ -1720,6 +1752,7 @@ private:
     HostGeom geom_;
     std::vector<int> prev_bsz_;
     std::map<long long, ConvRoute> route_cache_;  // by (k, ko_pad) -- a tower 1x1 that may take conv_pw.h: by (cin, cout, first sample, samples) --, for the current batch geometry
+    std::map<long long, DwPlan> dw_cache_;  // by (cs, k, first sample, samples), for the current batch geometry
     std::map<int, SplitPlan> split_cache_;  // latency context: by ko_pad, for the current batch geometry
     BoardPlan board_plan_;
     HeadFn head_fn_ = nullptr;

@@ -118,6 +118,10 @@ struct PwEntry { int nj; PwFn fn; };
 static const PwEntry kPwEntries[] = {
     {1, &conv_pw_kernel<1>}, {2, &conv_pw_kernel<2>}, {3, &conv_pw_kernel<3>}, {6, &conv_pw_kernel<6>}, {12, &conv_pw_kernel<12>},
 };
+// the depthwise k x k convolution on LDS (conv_dw.h), by k
+typedef void (*DwFn)(const DwParams);
+struct DwEntry { int k; DwFn fn; };
+static const DwEntry kDwEntries[] = {{3, &conv_dw_kernel<3>}, {5, &conv_dw_kernel<5>}, {7, &conv_dw_kernel<7>}};
 // head_board_kernel variants: {row tiles, trunk chunks in flight}; the first that fits the LDS is used (head_board_fits)
 typedef void (*HeadFn)(const HeadBoardParams);
 struct HeadEntry { int rt, depth; HeadFn fn; };
@@ -160,6 +164,9 @@ static void enable_big_lds_glds() {
 //   SAYURI_PW=0 | 1               the tower's 1x1 convolutions on the generic kernel everywhere | on conv_pw.h wherever it applies,
 //                                 instead of where the speed rule says it pays (pw_pays; same bits either way)
 //   SAYURI_PW_PIECES=n            conv_pw.h: n pieces per sample in every launch instead of the engine's choice (pw_plan)
+//   SAYURI_DW=0 | 1               the depthwise convolutions on depthwise_kernel everywhere | on conv_dw.h wherever it applies,
+//                                 instead of where the speed rule says it pays (dw_pays; same bits either way)
+//   SAYURI_DW_STRIPS=n            conv_dw.h: n strips per sample in every launch instead of the engine's choice (dw_plan)
 // The other switches are described at their fields below.
 struct ConvOverride {
     bool v0 = false, no_board = false;
@@ -177,6 +184,9 @@ struct EngineFlags {
     int pw = -1;                       // SAYURI_PW: unset (-1) a tower 1x1 takes conv_pw.h where the rule says it pays (route_conv, pw_pays);
                                        // 0: nowhere; 1: wherever the kernel applies
     int pw_pieces = 0;                 // SAYURI_PW_PIECES=n: pieces per sample (0: pw_auto)
+    int dw = -1;                       // SAYURI_DW: unset (-1) a depthwise layer takes conv_dw.h where the rule says it pays
+                                       // (Engine::depthwise, dw_pays); 0: nowhere; 1: wherever the kernel applies
+    int dw_strips = 0;                 // SAYURI_DW_STRIPS=n: strips per sample (0: dw_auto)
     int se_one = -1;                   // SAYURI_SE_ONE: an SE unit that runs as kernels of its own is ONE launch (se_unit_kernel, small_ops.h)
                                        // instead of se_pool / se_fc / se_scale -- unset (-1): in a latency context (Engine::se_unit()'s
                                        // rule); 0: nowhere; 1: wherever Engine::se_unit() or the se_unit tap would run the three.  Same
@@ -228,6 +238,8 @@ struct EngineFlags {
         if (const char* e = getenv("SAYURI_SE_ONE")) f.se_one = atoi(e) != 0;
         if (const char* e = getenv("SAYURI_PW")) f.pw = atoi(e) != 0;
         if (const char* e = getenv("SAYURI_PW_PIECES")) f.pw_pieces = std::max(0, atoi(e));
+        if (const char* e = getenv("SAYURI_DW")) f.dw = atoi(e) != 0;
+        if (const char* e = getenv("SAYURI_DW_STRIPS")) f.dw_strips = std::max(0, atoi(e));
 #ifdef SAYURI_EXPERIMENTS
         if (const char* e = getenv("SAYURI_BOARD_KOT")) f.board_kot = atoi(e);
         if (const char* e = getenv("SAYURI_ACT_OVERRIDE")) f.act_override = atoi(e);
@@ -408,7 +420,9 @@ static const BoardEntry* pick_board(const BoardPlan& bp, int ko_pad, int* kot_ti
 // sayuri_hip_test_last_conv_kind reports (kConvBoardSx: never a route -- a block's last convolution with its SE unit inside,
 // Engine::conv_sx; the tap sayuri_hip_test_conv_sx reports it).
 // kConvPw: a TOWER 1x1 layer of the fp16 engine (conv_pw.h), in a default and in a latency context alike.
-enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4, kConvBoardSx = 5, kConvPw = 6 };
+// kConvDwLds: a depthwise layer of the fp16 engine on conv_dw.h (Engine::depthwise chooses; kConvDepthwise is depthwise_kernel).
+enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4, kConvBoardSx = 5, kConvPw = 6,
+                  kConvDwLds = 7 };
 
 // The many-small-workgroups plan of a tower 1x1 layer (conv_pw.h) for the samples [n0, n0 + ns): how many pieces a sample's
 // pixels are cut into, the grid, the kernel variant and its LDS.  Host arithmetic only.
@@ -472,6 +486,82 @@ struct PwAsk { int cin, cout, cin_s, n0, ns, pieces; bool force; };  // force: S
 // and a forward takes 0.41 to 0.88 of its time on the generic kernel; with one or two pieces a sample (128 boards on three or more
 // channel tiles, 256 boards) the kernel is level or 10 to 30 % of a forward behind.  Decides speed only.
 static bool pw_pays(int ns, int kts) { return pw_auto(ns, kts) >= 3; }
+
+// The plan of a depthwise k x k layer on LDS (conv_dw.h) for the samples [n0, n0 + ns): the channel slice, how many strips of
+// rows a sample is cut into, the grid, the kernel variant (one per k) and its LDS.  Host arithmetic only.
+// The slice is 64 channels where cs % 64 == 0 (a pixel's slice is one 128-byte line), 32 otherwise.
+// The rule (strips == 0), split_plan's and pw_plan's: as many strips per sample as keep the launch near ONE round of the chip --
+// kDwRound / (samples x slices), at least one, never more than a board has rows -- so a lone 19x19 board is cut into one strip per
+// row and 256 boards are not cut at all (a strip re-reads its k - 1 halo rows: cutting a full batch only adds traffic).  A
+// round is counted as two workgroups per CU, what kDwMaxLds leaves room for: a supposition, not A/B-measured.  A batch of boards
+// so large that an uncut sample exceeds kDwMaxLds is cut until it fits.  strips == n forces n (SAYURI_DW_STRIPS, the tap): more
+// strips than the largest board of the range has rows, or a cut whose item exceeds kDwMaxLds, is refused, not changed (a smaller
+// board of a mixed batch has one strip per row at most: dw_rows).  The cut decides speed only.
+struct DwPlan {
+    bool ok = false;
+    int strips = 0, smax = 0, sp = 0, slices = 0, grid = 0, rows = 0;  // rows: the largest board's rows (refusal)
+    const DwEntry* e = nullptr;
+    size_t lds = 0;
+    std::string why;  // the refusal
+};
+// Where a follow-up should look (DESIGN.md Kernel 1j, profiles/r13_dw_conv.json): at small batches the constant cuts too FINELY --
+// four forced strips beat the plan's eight at 16 boards (0.918 against 0.942 of the old kernel's forward) and its nineteen at 8
+// boards in a latency context (0.904 against 0.923), one strip beats nine on a lone 9x9 board (0.883 against 0.903); from 32 boards
+// on the plan's cut is the best measured.
+constexpr int kDwRound = 2 * kNumCU;
+static int dw_auto(int ns, int slices) { return std::max(1, kDwRound / std::max(1, ns * slices)); }
+static size_t dw_plan_lds(const HostGeom& geom, int n0, int ns, int k, int sp, int strips) {
+    size_t lds = 0;
+    for (int s = n0; s < n0 + ns; ++s) {
+        const int bs = geom.bsz[s], rp = dw_rows(bs, strips);
+        for (int r0 = 0; r0 < bs; r0 += rp)  // the kernel's own arithmetic: a strip and the halo rows inside the board
+            lds = std::max(lds, dw_lds_bytes(k, sp, (std::min(bs, std::min(bs, r0 + rp) + k / 2) - std::max(0, r0 - k / 2)) * bs));
+    }
+    return lds;
+}
+static DwPlan dw_plan(const HostGeom& geom, int n0, int ns, int cs, int k, int strips) {
+    DwPlan dp;
+    if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || cs <= 0 || strips < 0) { dp.why = "bad argument"; return dp; }
+    for (const auto& e : kDwEntries)
+        if (e.k == k) dp.e = &e;
+    if (!dp.e) { dp.why = "a depthwise layer of k = " + std::to_string(k) + " keeps depthwise_kernel (conv_dw.h has k = 3, 5, 7)"; return dp; }
+    if (cs % 32) { dp.why = "a channel stride of " + std::to_string(cs) + " is not whole 32-channel slices"; return dp; }
+    dp.sp = cs % 64 == 0 ? 8 : 4;
+    dp.slices = cs / (8 * dp.sp);
+    for (int s = n0; s < n0 + ns; ++s) dp.rows = std::max(dp.rows, geom.bsz[s]);
+    if (strips > dp.rows) {
+        dp.why = std::to_string(strips) + " strips are more than the " + std::to_string(dp.rows) + " rows of the largest board (SAYURI_DW_STRIPS / strips)";
+        return dp;
+    }
+    dp.strips = strips > 0 ? strips : std::min(dp.rows, dw_auto(ns, dp.slices));
+    dp.lds = dw_plan_lds(geom, n0, ns, k, dp.sp, dp.strips);
+    while (strips == 0 && dp.lds > kDwMaxLds && dp.strips < dp.rows) dp.lds = dw_plan_lds(geom, n0, ns, k, dp.sp, ++dp.strips);
+    if (dp.lds > kDwMaxLds) {
+        dp.why = "an item of " + std::to_string(dp.lds) + " bytes of LDS is more than the kernel's " + std::to_string(kDwMaxLds) +
+                 " (SAYURI_DW_STRIPS / strips too small for this board)";
+        return dp;
+    }
+    for (int s = n0; s < n0 + ns; ++s) {
+        const int bs = geom.bsz[s], rp = dw_rows(bs, dp.strips);
+        dp.smax = std::max(dp.smax, (bs + rp - 1) / rp);
+    }
+    dp.grid = ns * dp.smax * dp.slices;
+    dp.ok = true;
+    return dp;
+}
+static void dw_params(DwParams& q, const DwPlan& dp, int n0) {
+    q.sp = dp.sp; q.slices = dp.slices; q.strips = dp.strips; q.smax = dp.smax; q.n0 = n0;
+}
+static void dw_launch(const DwPlan& dp, const DwParams& q, hipStream_t s) {
+    hipLaunchKernelGGL(dp.e->fn, dim3(dp.grid), dim3(kDwThreads), dp.lds, s, q);
+}
+// The speed rule of Engine::depthwise.  Measured (DESIGN.md Kernel 1j, profiles/r13_dw_conv.json): on ten 7x7 mixer blocks at 256
+// channels a forward under the plan's cut takes 0.73 to 0.94 of its time on depthwise_kernel at every point -- default contexts at 1,
+// 16, 32, 64, 128, 256 boards of 19x19 (ratios 0.89, 0.94, 0.82, 0.78, 0.73, 0.74), latency contexts at 1, 8, 32 boards and one 9x9
+// board (0.89, 0.92, 0.82, 0.90) -- each beyond the spread of the method (at most 0.008); a launch takes 21.6 us instead of 35.7 at
+// 32 boards and 89.5 instead of 222.1 at 256; the RepLK head's one layer moves a residual network's forward by 0.2 to 1.8 %.  No regime loses, so the rule takes the kernel wherever its plan fits.  (What loses is
+// a forced cut: one or two strips a sample at up to 32 boards, 1.10 to 1.47 -- SAYURI_DW_STRIPS, not the plan.)  Decides speed only.
+static bool dw_pays() { return true; }
 
 struct ConvRoute {
     ConvFamily family = kConvGeneric;

@@ -242,6 +242,64 @@ static int test_conv_pw_impl(int device, int n, const int* board_sizes, int max_
     return nhwc_to_nchw(tg, dy, cout, cout_s, y);
 }
 
+// The pad channels [C, cs) of every board pixel (sample-major, pixel-major) as the last sayuri_hip_test_conv_dw call found them, raw
+// fp16 bits: [0] conv_dw_kernel's output, [1] depthwise_kernel's on the same operands (sayuri_hip_test_last_dw_pad).
+static thread_local std::vector<uint16_t> g_test_dw_pad[2];
+static int read_dw_pad(const TestGeom& tg, const f16* dev, int C, int cs, std::vector<uint16_t>* pad) {
+    std::vector<uint16_t> h((size_t)tg.hg.n * tg.slot * cs);
+    HIP_OK(hipMemcpy(h.data(), dev, h.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    pad->clear();
+    for (int i = 0; i < tg.hg.n; ++i)
+        for (int p = 0; p < tg.hg.bsz[i] * tg.hg.bsz[i]; ++p)
+            for (int c = C; c < cs; ++c) pad->push_back(h[((size_t)i * tg.slot + p) * cs + c]);
+    return 0;
+}
+
+// One fp16 depthwise layer through conv_dw.h: the engine's [tap][cs] image and bias, dw_plan's launch.  strips: strips per sample
+// (0: the engine's choice for this batch).  res, when given, is added behind the activation.  y's device buffer starts as NaN.
+static int test_conv_dw_impl(int device, int n, const int* board_sizes, int max_board, int C, int k, int act, const float* x,
+                             const float* w, const float* bias, const float* res, int strips, float* y) {
+    typedef f16 T;
+    HIP_OK(hipSetDevice(device));
+    if (C <= 0 || strips < 0) return fail("test_conv_dw: bad argument");
+    TestArena A;
+    TestGeom tg;
+    if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
+    const int cs = round_up(C, 32);
+    const DwPlan dp = dw_plan(tg.hg, 0, n, cs, k, strips);
+    if (!dp.ok) return fail("test_conv_dw: " + dp.why);
+    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, C, cs));
+    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
+    const size_t y_bytes = (size_t)n * tg.slot * cs * sizeof(T);
+    T* dy = (T*)A.alloc(y_bytes);
+    const float* dw = A.upload(depthwise_image(w, C, k * k, cs));
+    const float* db = A.upload(padded_bias(bias, C, cs));
+    if (!dx || !dy || (res && !dres) || !dw || !db) return fail("test_conv_dw: hipMalloc failed");
+    HIP_OK(hipMemset(dy, 0xff, y_bytes));  // fp16 0xffff: a NaN
+    g_test_conv_kind = kConvDwLds;
+    DwParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.x = dx; q.res = dres; q.out = dy; q.wt = dw; q.bias = db;
+    q.g = tg.g; q.C = C; q.cs = cs; q.act = act;
+    dw_params(q, dp, 0);
+    dw_launch(dp, q, nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    g_test_dw_pad[0].clear();
+    g_test_dw_pad[1].clear();
+    if (cs > C) {  // what both kernels leave in the pad channels: depthwise_kernel into a NaN buffer of its own, same operands
+        T* dold = (T*)A.alloc(y_bytes);
+        if (!dold) return fail("test_conv_dw: hipMalloc failed");
+        HIP_OK(hipMemset(dold, 0xff, y_bytes));
+        const size_t total = (size_t)tg.hg.total * (cs / ElemTraits<T>::kPieceElems);
+        hipLaunchKernelGGL(depthwise_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, dx, dres, dold, dw, db, tg.g, C, cs, k, act);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipDeviceSynchronize());
+        if (read_dw_pad(tg, dy, C, cs, &g_test_dw_pad[0]) || read_dw_pad(tg, dold, C, cs, &g_test_dw_pad[1])) return -1;
+    }
+    return nhwc_to_nchw(tg, dy, C, cs, y);
+}
+
 template <typename T>
 static int test_se_unit_impl(int device, int n, const int* board_sizes, int max_board, int C, int se, int act, const float* x,
                              const float* res, const float* w1, const float* b1, const float* w2, const float* b2, float* y,
@@ -865,6 +923,20 @@ extern "C" int sayuri_hip_test_conv_pw(int device, int n, const int* board_sizes
                                        const float* w, const float* bias, const float* res, float* y, int pieces) {
     if (!board_sizes || !x || !w || !y || n <= 0) return fail("test_conv_pw: bad argument");
     return test_conv_pw_impl(device, n, board_sizes, max_board, cin, cout, act, x, w, bias, res, y, pieces);
+}
+
+extern "C" int sayuri_hip_test_conv_dw(int device, int use_fp16, int n, const int* board_sizes, int max_board, int channels, int k, int act,
+                                       const float* x, const float* w, const float* bias, const float* res, int strips, float* y) {
+    if (!board_sizes || !x || !w || !y || n <= 0) return fail("test_conv_dw: bad argument");
+    if (!use_fp16) return fail("test_conv_dw: conv_dw.h is an fp16 kernel: the fp32 engine keeps depthwise_kernel");
+    return test_conv_dw_impl(device, n, board_sizes, max_board, channels, k, act, x, w, bias, res, strips, y);
+}
+
+extern "C" int sayuri_hip_test_last_dw_pad(int which, unsigned short* bits, int cap) {
+    if (which < 0 || which > 1 || cap < 0 || (cap > 0 && !bits)) return fail("test_last_dw_pad: bad argument");
+    const std::vector<uint16_t>& v = sayuri::g_test_dw_pad[which];
+    std::copy(v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)cap), bits);
+    return (int)v.size();
 }
 
 extern "C" int sayuri_hip_test_last_conv_kind(void) { return sayuri::g_test_conv_kind; }

@@ -170,3 +170,34 @@ def conv_pw_layer(board_sizes, cin: int, cout: int, act: int, xs, w, bias=None, 
         outs.append(y[off:off + cout * b * b].reshape(cout, b * b))
         off += cout * b * b
     return rc, outs, lib.sayuri_hip_test_last_conv_kind()
+
+
+def conv_dw_layer(board_sizes, channels: int, k: int, act: int, xs, w, bias=None, res=None, strips: int = 0, max_board: int = 19,
+                  use_fp16: bool = True):
+    """The layer tap of the depthwise kernel on LDS (sayuri_hip_test_conv_dw, csrc/hip/conv_dw.h): one fp16 depthwise k x k layer
+    on host tensors, no context.  xs / res: per-sample [channels][b*b] arrays (res None: no residual; given, it is added behind
+    the activation), w [channels][k*k], strips per sample (0: the engine's choice).  -> (rc, per-sample [channels][b*b] outputs
+    that start as NaN, sayuri_hip_test_last_conv_kind); rc -1 is a refusal whose message sayuri_hip_last_error holds."""
+    lib = _lib.hip()
+    bsz = np.asarray(board_sizes, np.int32)
+    cat = lambda arrs: None if arrs is None else fp(np.concatenate([np.ascontiguousarray(a, np.float32).ravel() for a in arrs]))
+    one = lambda a: None if a is None else fp(np.ascontiguousarray(a, np.float32))
+    y = np.full(channels * int((bsz.astype(np.int64) ** 2).sum()), np.nan, np.float32)
+    rc = lib.sayuri_hip_test_conv_dw(0, int(use_fp16), len(bsz), ip(bsz), max_board, channels, k, act, cat(xs), one(w), one(bias),
+                                     cat(res), strips, fp(y))
+    outs, off = [], 0
+    for b in bsz:
+        outs.append(y[off:off + channels * b * b].reshape(channels, b * b))
+        off += channels * b * b
+    return rc, outs, lib.sayuri_hip_test_last_conv_kind()
+
+
+def conv_dw_pad_bits(which: int = 0):
+    """The pad channels [channels, stride) of every board pixel after this thread's last conv_dw_layer, raw fp16 bits
+    (sayuri_hip_test_last_dw_pad): which = 0 the kernel on LDS, 1 depthwise_kernel on the same operands."""
+    lib = _lib.hip()
+    n = lib.sayuri_hip_test_last_dw_pad(which, None, 0)
+    bits = np.zeros(max(n, 1), np.uint16)
+    if n < 0 or lib.sayuri_hip_test_last_dw_pad(which, bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), n) != n:
+        raise RuntimeError(lib.sayuri_hip_last_error().decode())
+    return bits[:n]
