@@ -21,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../../include/sayuri_hip.h"
@@ -197,67 +198,43 @@ int sayuri_hip_latency_state(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng-
 int sayuri_hip_last_split_ring(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_split_ring() : sayuri::g_test_split_ring; }
 // host arithmetic only: the geometry, the layer's weight rows and split_plan, as a latency context and the conv_split tap run them
 int sayuri_hip_split_ring_plan(int n, const int* board_sizes, int max_board, int cout, int strips, int ring) {
-    using namespace sayuri;
-    if (n <= 0 || !board_sizes || max_board < 2 || cout <= 0 || strips < 0) return fail("split_ring_plan: bad argument");
     HostGeom hg;
-    hg.n = n;
-    hg.bsz.assign(board_sizes, board_sizes + n);
-    hg.off.assign(n + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        if (hg.bsz[i] < 2 || hg.bsz[i] > max_board) return fail("split_ring_plan: bad board size");
-        hg.off[i + 1] = hg.off[i] + hg.bsz[i] * hg.bsz[i];
-    }
-    hg.total = hg.off[n];
+    if (cout <= 0 || strips < 0) return fail("split_ring_plan: bad argument");
+    if (host_geom(n, board_sizes, max_board, "split_ring_plan", &hg)) return -1;
     int wmt, ko_pad;
     conv_tile(round_up(cout, 32), true, &wmt, &ko_pad);
-    if (route_conv(true, 3, ko_pad, hg, BoardPlan{}, ConvOverride{}, 0, /*latency=*/true).family != kConvSplit)
+    if (!split_covers(ko_pad))
         return fail("split_ring_plan: a layer of " + std::to_string(ko_pad) + " weight rows is not whole 64-channel tiles: it keeps the default route");
     const SplitPlan sp = split_plan(hg, 0, n, ko_pad, strips, ring);
-    if (!sp.ok) return fail("split_ring_plan: " + split_refusal(sp));
+    if (!sp.ok) return fail("split_ring_plan: " + sp.why);
     return sp.stages;
 }
 int sayuri_hip_last_pw_launches(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_pw_launches() : 0; }
 // host arithmetic only: the geometry, the layer's weight rows and route_conv's plan, as a context and the conv_pw tap run them
 int sayuri_hip_pw_plan(int n, const int* board_sizes, int max_board, int cin, int cout, int pieces, int out[4]) {
-    using namespace sayuri;
-    if (n <= 0 || !board_sizes || max_board < 2 || cin <= 0 || cout <= 0 || pieces < 0 || !out) return fail("pw_plan: bad argument");
     HostGeom hg;
-    hg.n = n;
-    hg.bsz.assign(board_sizes, board_sizes + n);
-    hg.off.assign(n + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        if (hg.bsz[i] < 2 || hg.bsz[i] > max_board) return fail("pw_plan: bad board size");
-        hg.off[i + 1] = hg.off[i] + hg.bsz[i] * hg.bsz[i];
-    }
-    hg.total = hg.off[n];
+    if (cin <= 0 || cout <= 0 || pieces < 0 || !out) return fail("pw_plan: bad argument");
+    if (host_geom(n, board_sizes, max_board, "pw_plan", &hg)) return -1;
     int wmt, ko_pad;
     conv_tile(round_up(cout, 32), true, &wmt, &ko_pad);
-    if (cout % kPwKO || cin % kChunk)
+    if (!pw_covers(cin, cout, ko_pad))
         return fail("pw_plan: a layer of " + std::to_string(cin) + " -> " + std::to_string(cout) +
                     " channels is not whole 32-channel chunks into whole 64-channel tiles: it keeps the generic kernel");
     const PwAsk ask{cin, cout, round_up(cin, 32), 0, n, pieces, /*force=*/true};  // the plan itself: whether a context takes it is the speed rule's business (pw_pays)
     const ConvRoute r = route_conv(true, 1, ko_pad, hg, BoardPlan{}, ConvOverride{}, 0, false, &ask);
-    if (!r.pw.ok) return fail("pw_plan: " + pw_refusal(r.pw));
-    out[0] = r.pw.pieces; out[1] = r.pw.grid; out[2] = r.pw.e->nj; out[3] = (int)r.pw.lds;
+    if (!r.pw.ok) return fail("pw_plan: " + r.pw.why);
+    out[0] = r.pw.cut; out[1] = r.pw.grid; out[2] = r.pw.e->nj; out[3] = (int)r.pw.lds;
     return 0;
 }
 int sayuri_hip_last_dw_launches(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->last_dw_launches() : 0; }
 // host arithmetic only: the geometry and dw_plan, as a context and the conv_dw tap run them
 int sayuri_hip_dw_plan(int n, const int* board_sizes, int max_board, int channels, int k, int strips, int out[4]) {
-    using namespace sayuri;
-    if (n <= 0 || !board_sizes || max_board < 2 || channels <= 0 || strips < 0 || !out) return fail("dw_plan: bad argument");
     HostGeom hg;
-    hg.n = n;
-    hg.bsz.assign(board_sizes, board_sizes + n);
-    hg.off.assign(n + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        if (hg.bsz[i] < 2 || hg.bsz[i] > max_board) return fail("dw_plan: bad board size");
-        hg.off[i + 1] = hg.off[i] + hg.bsz[i] * hg.bsz[i];
-    }
-    hg.total = hg.off[n];
+    if (channels <= 0 || strips < 0 || !out) return fail("dw_plan: bad argument");
+    if (host_geom(n, board_sizes, max_board, "dw_plan", &hg)) return -1;
     const DwPlan dp = dw_plan(hg, 0, n, round_up(channels, 32), k, strips);
     if (!dp.ok) return fail("dw_plan: " + dp.why);
-    out[0] = dp.sp * 8; out[1] = dp.strips; out[2] = dp.grid; out[3] = (int)dp.lds;
+    out[0] = dp.sp * 8; out[1] = dp.cut; out[2] = dp.grid; out[3] = (int)dp.lds;
     return 0;
 }
 // debugging tap (not part of the ABI, not in the header): activation buffer `buf` (0..5) of ticket 0 as it stands after the last forward

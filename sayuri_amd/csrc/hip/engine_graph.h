@@ -6,6 +6,18 @@
 
 namespace sayuri {
 
+// The key of what an engine computes once per batch geometry (routes, plans, tile choices): what the entry is about (a, b, c) and
+// the sample range [n0, n0 + ns) it was computed for (0, 0: the whole batch).  Nothing is packed: no value aliases another entry.
+struct PlanKey {
+    int a = 0, b = 0, c = 0, n0 = 0, ns = 0;
+    bool operator<(const PlanKey& o) const { return std::tie(a, b, c, n0, ns) < std::tie(o.a, o.b, o.c, o.n0, o.ns); }
+};
+template <typename V, typename Make> static const V& cached(std::map<PlanKey, V>& m, const PlanKey& key, Make&& make) {
+    auto it = m.find(key);
+    if (it == m.end()) it = m.emplace(key, make()).first;
+    return it->second;
+}
+
 class EngineBase {
 public:
     virtual ~EngineBase() {}
@@ -135,10 +147,10 @@ public:
             if (b.type != SAYURI_BLOCK_RESIDUAL) return 1;  // every layer of the graph must be a board convolution or a per-sample kernel
         const ConvLayerDev& L = cv(SAYURI_L_BLOCK(0, SAYURI_S_CONV1));
         // (a network whose SE units could run inside the convolution keeps one chain: conv_se launches over the whole batch)
-        for (const auto& e : kBoardEntries)
-            if (e.fn_se && e.kot == L.ko_pad)
-                for (const auto& b : blocks_)
-                    if (b.apply_se) return 1;
+        // (board_se_entry, not pick_board_se: the answer is about the network, before any batch has a board plan whose LDS could be asked)
+        if (board_se_entry(L.ko_pad))
+            for (const auto& b : blocks_)
+                if (b.apply_se) return 1;
         const ConvRoute& r = route(L);
         if (!r.board || !board_plan_.ok) return 1;
         const int wgs = board_plan_.ntiles * r.tiles;
@@ -370,13 +382,7 @@ public:
             geom_.off[i + 1] = geom_.off[i] + geom_.bsz[i] * geom_.bsz[i];
         }
         geom_.total = geom_.off[n];
-        if (geom_.bsz != prev_bsz_) {  // tile choices and index tables depend on the geometry only
-            tile_cache_.clear();
-            route_cache_.clear();
-            split_cache_.clear();
-            dw_cache_.clear();
-            board_plan_valid_ = false;
-        }
+        if (geom_.bsz != prev_bsz_) forget_geometry();
         IoSlot& io = io_[t];
         const bool uniform = !mixed;
         // One sample per tile and one board size: the tables of a LONGER batch of the same size serve a shorter one (tile i
@@ -1002,11 +1008,16 @@ private:
 
     // the generic kernel's variant for the current batch geometry (cached: it depends on the geometry only)
     int choose_tile(int wmt, int kot_tiles, TileChoice<T>* out) {
-        auto it = tile_cache_.find(wmt * 1024 + kot_tiles);
-        if (it != tile_cache_.end()) { *out = it->second; return 0; }
-        if (!pick_tile<T>(geom_, wmt, kot_tiles, /*widest=*/false, out)) return fail("no conv tile configuration fits this batch geometry");
-        tile_cache_[wmt * 1024 + kot_tiles] = *out;
-        return 0;
+        *out = cached(tile_cache_, PlanKey{wmt, kot_tiles}, [&] {
+            TileChoice<T> tc{};  // (e stays null where none fits)
+            return pick_tile<T>(geom_, wmt, kot_tiles, /*widest=*/false, &tc), tc;
+        });
+        return out->e ? 0 : fail("no conv tile configuration fits this batch geometry");
+    }
+    // Tile choices, routes, plans and the board tiles depend on the batch geometry alone.  The one place that forgets them.
+    void forget_geometry() {
+        tile_cache_.clear(); route_cache_.clear(); split_cache_.clear(); dw_cache_.clear();
+        board_plan_valid_ = false;
     }
 
     // index tables of the current batch geometry for pixel-tile size 64*wnt (built on first use)
@@ -1062,16 +1073,11 @@ private:
     const ConvRoute& route(const ConvLayerDev& L, const Fwd* f = nullptr, bool tower_pw = false) {
         const BoardPlan& bp = plan();
         const bool pw = tower_pw && f && L.k == 1 && flags_.pw != 0 && sizeof(T) == 2;
-        const long long key = pw ? (1ll << 62) | ((long long)(L.cin & 0x3fff) << 46) | ((long long)(L.cout & 0x3fff) << 32) |
-                                       ((long long)(f->n0 & 0xffff) << 16) | (f->ns & 0xffff)
-                                 : (long long)L.k * 65536 + L.ko_pad;
-        auto it = route_cache_.find(key);
-        if (it == route_cache_.end()) {
+        const PlanKey key = pw ? PlanKey{-1, L.cin, L.cout, f->n0, f->ns} : PlanKey{L.k, L.ko_pad};  // (-1: no layer's k)
+        return cached(route_cache_, key, [&] {
             const PwAsk ask{L.cin, L.cout, L.cin_s, pw ? f->n0 : 0, pw ? f->ns : 0, flags_.pw_pieces, flags_.pw == 1};
-            it = route_cache_.emplace(key, route_conv(sizeof(T) == 2, L.k, L.ko_pad, geom_, bp, flags_.conv, flags_.board_kot, flags_.latency,
-                                                      pw ? &ask : nullptr)).first;
-        }
-        return it->second;
+            return route_conv(sizeof(T) == 2, L.k, L.ko_pad, geom_, bp, flags_.conv, flags_.board_kot, flags_.latency, pw ? &ask : nullptr);
+        });
     }
 
     // The last step of a board convolution (conv, conv_se) once its parameters are built: it joins the pending persistent run
@@ -1129,17 +1135,10 @@ private:
     // A block's last 3x3 convolution with the squeeze-and-excitation unit that follows it inside the kernel
     // (conv_board.h).  Returns 1 when the fused kernel does not apply (the caller then runs conv + se_unit), 0 / -1.
     int conv_se(Fwd& f, const ConvLayerDev& L, const FcLayerDev& sq, const FcLayerDev& ex, const T* in, T* out, const T* res, int C, int act) {
-        const bool off = !flags_.se_fused;
-        const BoardEntry* be = nullptr;
-        // the variant whose channel tile covers the whole layer, whatever the batch size: a position's result must not
-        // depend on how many others share its batch (a small batch would otherwise pick two half-width workgroups and
-        // the separate SE kernels, which round x to fp16 before pooling)
-        if (!off && route(L).board)
-            for (const auto& e : kBoardEntries)
-                if (e.fn_se && e.kot == L.ko_pad && e.lds(board_plan_.npos) <= kMaxLds) be = &e;
+        const BoardEntry* be = flags_.se_fused && route(L).board ? pick_board_se(board_plan_, L.ko_pad) : nullptr;
         if (!be || C > be->kot) return 1;
         const bool staged = sq.img16 && ex.img16;
-        if (!staged && (sq.out % 4 || sq.out > 512 || ex.out % 4 || ex.out > 2048 || 512 % (sq.out / 4) || 512 % (ex.out / 4))) return 1;
+        if (!staged && !se_l2_form_ok(sq.out, ex.out)) return 1;
         if constexpr (sizeof(T) != 2) return 1;
         // fused: a board too large to share a tile with another of its size (2 bs^2 > 384 pixel slots, i.e. bs >= 14), alone in
         // its tile; a smaller board ALWAYS goes through the separate kernels, also when it happens to sit alone in a tile
@@ -1156,9 +1155,7 @@ private:
         ConvParams& p = bp.c;
         conv_params(p, in, L.w, L.bias, res, out, dgeom(f.io), L.cin_s, L.cout_s, L.ko_pad, 9, act);
         p.npos = 0; p.num_pix_tiles = f.ntiles;
-        sp.squeeze = sq.dev(); sp.excite = ex.dev(); sp.C = C;
-        sp.w1h = staged ? sq.img16 : nullptr; sp.w2h = staged ? ex.img16 : nullptr;
-        sp.w1_bytes = sq.img_bytes; sp.w2_bytes = ex.img_bytes;
+        se_stage_params(sp, sq.dev(), ex.dev(), C, staged ? sq.img16 : nullptr, staged ? ex.img16 : nullptr, sq.img_bytes, ex.img_bytes);
 #ifdef SAYURI_EXPERIMENTS
         if (flags_.board_dbg < 0) {  // negative n: timeline of the n-th SE convolution of the forward
             if (!d_dbg_ && dev_alloc(&d_dbg_, 4 * 8 * 8)) return -1;
@@ -1217,12 +1214,11 @@ private:
     }
 
     // A 3x3 layer of a latency context as many small workgroups (conv_split.h): one launch over the forward's samples, the
-    // split chosen from the batch geometry (split_plan; cached like the routes: it depends on the geometry only).
+    // split chosen from the batch geometry and the forward's samples (split_plan; cached like the routes).
     int conv_split(Fwd& f, const char* name, const ConvLayerDev& L, const T* in, T* out, const T* res, int act) {
-        auto it = split_cache_.find(L.ko_pad);
-        if (it == split_cache_.end()) it = split_cache_.emplace(L.ko_pad, split_plan(geom_, f.n0, f.ns, L.ko_pad, flags_.latency_split, flags_.latency_ring)).first;
-        const SplitPlan& sp = it->second;
-        if (!sp.ok) return fail(std::string("latency context, layer ") + name + ": " + split_refusal(sp));
+        const SplitPlan& sp = cached(split_cache_, PlanKey{L.ko_pad, 0, 0, f.n0, f.ns},
+                                     [&] { return split_plan(geom_, f.n0, f.ns, L.ko_pad, flags_.latency_split, flags_.latency_ring); });
+        if (!sp.ok) return fail(std::string("latency context, layer ") + name + ": " + sp.why);
         last_split_ring_ = std::max(last_split_ring_, sp.stages);
         SplitParams q;
         std::memset(&q, 0, sizeof(q));
@@ -1310,10 +1306,8 @@ private:
         const double flops = 2.0 * f.px * L.cout * L.k * L.k, bytes = sizeof(T) * f.px * L.cout * (res ? 3 : 2);
         if constexpr (sizeof(T) == 2) {
             if (flags_.dw != 0) {
-                const long long key = ((long long)L.cout_s << 40) | ((long long)L.k << 32) | ((long long)(f.n0 & 0xffff) << 16) | (f.ns & 0xffff);
-                auto it = dw_cache_.find(key);
-                if (it == dw_cache_.end()) it = dw_cache_.emplace(key, dw_plan(geom_, f.n0, f.ns, L.cout_s, L.k, flags_.dw_strips)).first;
-                const DwPlan& dp = it->second;
+                const DwPlan& dp = cached(dw_cache_, PlanKey{L.cout_s, L.k, 0, f.n0, f.ns},
+                                          [&] { return dw_plan(geom_, f.n0, f.ns, L.cout_s, L.k, flags_.dw_strips); });
                 if (!dp.ok && flags_.dw_strips && !dw_refusal_said_) {  // a forced cut that is refused must not pass for a measurement of it
                     dw_refusal_said_ = true;
                     std::fprintf(stderr, "[sayuri_hip] SAYURI_DW_STRIPS=%d: %s: the layer keeps depthwise_kernel\n", flags_.dw_strips, dp.why.c_str());
@@ -1751,9 +1745,10 @@ private:
     hipEvent_t tick_ev_[2] = {nullptr, nullptr};
     HostGeom geom_;
     std::vector<int> prev_bsz_;
-    std::map<long long, ConvRoute> route_cache_;  // by (k, ko_pad) -- a tower 1x1 that may take conv_pw.h: by (cin, cout, first sample, samples) --, for the current batch geometry
-    std::map<long long, DwPlan> dw_cache_;  // by (cs, k, first sample, samples), for the current batch geometry
-    std::map<int, SplitPlan> split_cache_;  // latency context: by ko_pad, for the current batch geometry
+    // for the current batch geometry (forget_geometry); a plan for a sample range has the range in its key
+    std::map<PlanKey, ConvRoute> route_cache_;  // by (k, ko_pad) -- a tower 1x1 that may take conv_pw.h: by (-1, cin, cout) and the range
+    std::map<PlanKey, DwPlan> dw_cache_;        // by (cs, k) and the range
+    std::map<PlanKey, SplitPlan> split_cache_;  // latency context: by ko_pad and the range
     BoardPlan board_plan_;
     HeadFn head_fn_ = nullptr;
     void* head_img2_ = nullptr;  // per-pixel weights (policy planes, ownership) as an MFMA image
@@ -1765,7 +1760,7 @@ private:
     unsigned long long* d_sxdbg_ = nullptr;  // SAYURI_SX_DBG timeline of one split SE convolution
     bool dbg_is_se_ = false;
     bool board_plan_valid_ = false;
-    std::map<int, TileChoice<T>> tile_cache_;
+    std::map<PlanKey, TileChoice<T>> tile_cache_;  // by (wmt, channel tiles)
     std::map<std::string, Stat> stats_;
     // light per-launch timing of one kernel class inside time_runs()
     bool light_ = false;

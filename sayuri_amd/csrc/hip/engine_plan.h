@@ -315,6 +315,19 @@ struct HostGeom {
     }
 };
 
+// The geometry of n samples of the given board sizes (2 .. max_board each) as a plan query or a test tap receives them:
+// bsz, off, total.  0, or the refusal under the caller's name.
+static int host_geom(int n, const int* board_sizes, int max_board, const std::string& who, HostGeom* hg) {
+    if (n <= 0 || !board_sizes || max_board < 2) return fail(who + ": bad argument");
+    hg->n = n; hg->bsz.assign(board_sizes, board_sizes + n); hg->off.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        if (hg->bsz[i] < 2 || hg->bsz[i] > max_board) return fail(who + ": bad board size");
+        hg->off[i + 1] = hg->off[i] + hg->bsz[i] * hg->bsz[i];
+    }
+    hg->total = hg->off[n];
+    return 0;
+}
+
 // A kernel variant with PT-pixel tiles across samples fits this geometry: the worst tile's halo positions (*npos, what its
 // LDS is sized by) and samples.  Its cost: rounds of workgroups over the CUs times the time of a tile.
 static bool tile_fits(const HostGeom& geom, int PT, int npos_cap, int* npos) {
@@ -424,9 +437,28 @@ static const BoardEntry* pick_board(const BoardPlan& bp, int ko_pad, int* kot_ti
 enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwise = 3, kConvSplit = 4, kConvBoardSx = 5, kConvPw = 6,
                   kConvDwLds = 7 };
 
+// What the three many-small-workgroups families share (conv_split.h, conv_pw.h, conv_dw.h): a sample's pixels are cut into items --
+// strips of rows, pieces of column tiles --, an item times a channel tile (a slice) is one workgroup.  THE CUT RULE, where the
+// caller forces no cut: as many items per sample as keep the launch near one round of the chip -- round / (samples x channel
+// tiles), at least one; what a round is, and the family's own bounds, are stated at each plan.  The cut decides speed only.
+// cut: the items a sample is cut into (a small board may have fewer); items: per sample in the grid, what the sample with the most
+// has; tiles: channel tiles / slices; grid = samples x items x tiles; why: what refused a plan that is not ok.
+struct CutPlan {
+    bool ok = false;
+    int cut = 0, items = 0, tiles = 0, grid = 0;
+    size_t lds = 0;
+    std::string why;
+};
+template <typename P> static P refused(P plan, const std::string& why) { plan.why = why; return plan; }
+static int cut_for_round(int round, int ns, int tiles) { return std::max(1, round / std::max(1, ns * tiles)); }
+// "This layer is the kernel's kind": whole 64-channel tiles of weight rows (conv_split.h); whole 32-channel chunks into whole
+// 64-channel tiles (conv_pw.h).  route_conv, the plans, the taps and the plan queries ask here.
+static bool split_covers(int ko_pad) { return ko_pad > 0 && ko_pad % kSplitKO == 0; }
+static bool pw_covers(int cin, int cout, int ko_pad) { return cout % kPwKO == 0 && cin % kChunk == 0 && ko_pad % kPwKO == 0; }
+
 // The many-small-workgroups plan of a tower 1x1 layer (conv_pw.h) for the samples [n0, n0 + ns): how many pieces a sample's
 // pixels are cut into, the grid, the kernel variant and its LDS.  Host arithmetic only.
-// The rule (pieces == 0): as many pieces per sample as keep the launch near ONE round of the chip -- kPwRound / (samples x channel
+// The rule (pieces == 0): the cut rule (CutPlan) with a round of kPwRound -- kPwRound / (samples x channel
 // tiles), at least one, a piece never smaller than one column tile (pw_cols) nor wider than the widest variant -- so a lone 19x19
 // board on 128 output channels is cut into one piece per column tile and a batch of 256 gets one piece per sample.  A round is
 // counted as three workgroups per CU: the thin variants (NJ <= 3, at most 48 KiB of LDS) are co-resident three to a CU.  The
@@ -435,44 +467,38 @@ enum ConvFamily { kConvGeneric = 0, kConvGlds = 1, kConvBoard = 2, kConvDepthwis
 // of the generic kernel's forward where four pieces take 0.78 to 0.81).  It decides the speed only: the
 // results do not depend on the cut.  pieces == n forces n (SAYURI_PW_PIECES, the tap): a cut whose pieces
 // would be wider than the widest variant holds is refused, not narrowed.
-struct PwPlan {
-    bool ok = false;
-    int pieces = 0, pmax = 0, kts = 0, grid = 0, wide = 0;  // wide: the column tiles of the piece that did not fit (refusal)
-    const PwEntry* e = nullptr;
-    size_t lds = 0;
-};
+struct PwPlan : CutPlan { const PwEntry* e = nullptr; };  // cut: pieces
 constexpr int kPwRound = 3 * kNumCU;
-static int pw_auto(int ns, int kts) { return std::max(1, kPwRound / std::max(1, ns * kts)); }
-static std::string pw_refusal(const PwPlan& pp) {
-    return pp.wide ? "a piece of " + std::to_string(pp.wide) + " column tiles is wider than the kernel's " + std::to_string(kPwMaxCols) +
-                         " (SAYURI_PW_PIECES / pieces too small for this board)"
-                   : std::string("no pointwise plan for this layer or batch geometry");
-}
+static int pw_auto(int ns, int kts) { return cut_for_round(kPwRound, ns, kts); }
 static PwPlan pw_plan(const HostGeom& geom, int n0, int ns, int ko_pad, int cin_s, int pieces) {
     PwPlan pp;
+    pp.why = "no pointwise plan for this layer or batch geometry";  // every refusal but the too-wide piece
     if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || ko_pad <= 0 || ko_pad % kPwKO || cin_s <= 0 || cin_s % kChunk || pieces < 0) return pp;
-    pp.kts = ko_pad / kPwKO;
-    pp.pieces = pieces > 0 ? pieces : pw_auto(ns, pp.kts);
+    pp.tiles = ko_pad / kPwKO;
+    pp.cut = pieces > 0 ? pieces : pw_auto(ns, pp.tiles);
     int max_cols = 0;
     for (int s = n0; s < n0 + ns; ++s) {
-        const int bs = geom.bsz[s], ncol = (bs * bs + 15) / 16, cp = pw_cols(bs, pp.pieces, /*cap=*/pieces == 0);
-        if (cp > kPwMaxCols) { pp.wide = cp; return pp; }
-        pp.pmax = std::max(pp.pmax, (ncol + cp - 1) / cp);
+        const int bs = geom.bsz[s], ncol = (bs * bs + 15) / 16, cp = pw_cols(bs, pp.cut, /*cap=*/pieces == 0);
+        if (cp > kPwMaxCols)
+            return refused(pp, "a piece of " + std::to_string(cp) + " column tiles is wider than the kernel's " + std::to_string(kPwMaxCols) +
+                                   " (SAYURI_PW_PIECES / pieces too small for this board)");
+        pp.items = std::max(pp.items, (ncol + cp - 1) / cp);
         max_cols = std::max(max_cols, cp);
     }
     for (const auto& e : kPwEntries)
         if (!pp.e && 2 * e.nj >= max_cols) pp.e = &e;
     if (!pp.e) return pp;
     pp.lds = pw_lds_bytes(pp.e->nj);
-    pp.grid = ns * pp.pmax * pp.kts;
+    pp.grid = ns * pp.items * pp.tiles;
     pp.ok = pp.lds <= kMaxLds;
+    if (pp.ok) pp.why.clear();
     return pp;
 }
 // The kernel's part of a launch (conv_params fills q.c before).  (The kernel caps a piece at the widest variant as the rule does;
 // a forced cut that the cap would change was refused above.)
 static void pw_params(PwParams& q, const PwPlan& pp, int n0) {
     q.c.npos = 0; q.c.num_pix_tiles = 0;
-    q.pieces = pp.pieces; q.pmax = pp.pmax; q.kts = pp.kts; q.n0 = n0;
+    q.pieces = pp.cut; q.pmax = pp.items; q.kts = pp.tiles; q.n0 = n0;
 }
 static void pw_launch(const PwPlan& pp, const PwParams& q, hipStream_t s) {
     hipLaunchKernelGGL(pp.e->fn, dim3(pp.grid), dim3(256), pp.lds, s, q);
@@ -490,26 +516,20 @@ static bool pw_pays(int ns, int kts) { return pw_auto(ns, kts) >= 3; }
 // The plan of a depthwise k x k layer on LDS (conv_dw.h) for the samples [n0, n0 + ns): the channel slice, how many strips of
 // rows a sample is cut into, the grid, the kernel variant (one per k) and its LDS.  Host arithmetic only.
 // The slice is 64 channels where cs % 64 == 0 (a pixel's slice is one 128-byte line), 32 otherwise.
-// The rule (strips == 0), split_plan's and pw_plan's: as many strips per sample as keep the launch near ONE round of the chip --
+// The rule (strips == 0): the cut rule (CutPlan) with a round of kDwRound --
 // kDwRound / (samples x slices), at least one, never more than a board has rows -- so a lone 19x19 board is cut into one strip per
 // row and 256 boards are not cut at all (a strip re-reads its k - 1 halo rows: cutting a full batch only adds traffic).  A
 // round is counted as two workgroups per CU, what kDwMaxLds leaves room for: a supposition, not A/B-measured.  A batch of boards
 // so large that an uncut sample exceeds kDwMaxLds is cut until it fits.  strips == n forces n (SAYURI_DW_STRIPS, the tap): more
 // strips than the largest board of the range has rows, or a cut whose item exceeds kDwMaxLds, is refused, not changed (a smaller
 // board of a mixed batch has one strip per row at most: dw_rows).  The cut decides speed only.
-struct DwPlan {
-    bool ok = false;
-    int strips = 0, smax = 0, sp = 0, slices = 0, grid = 0, rows = 0;  // rows: the largest board's rows (refusal)
-    const DwEntry* e = nullptr;
-    size_t lds = 0;
-    std::string why;  // the refusal
-};
+struct DwPlan : CutPlan { int sp = 0, rows = 0; const DwEntry* e = nullptr; };  // cut: strips; tiles: slices; sp: 16-byte pieces of a pixel's slice; rows: the largest board's
 // Where a follow-up should look (DESIGN.md Kernel 1j, profiles/r13_dw_conv.json): at small batches the constant cuts too FINELY --
 // four forced strips beat the plan's eight at 16 boards (0.918 against 0.942 of the old kernel's forward) and its nineteen at 8
 // boards in a latency context (0.904 against 0.923), one strip beats nine on a lone 9x9 board (0.883 against 0.903); from 32 boards
 // on the plan's cut is the best measured.
 constexpr int kDwRound = 2 * kNumCU;
-static int dw_auto(int ns, int slices) { return std::max(1, kDwRound / std::max(1, ns * slices)); }
+static int dw_auto(int ns, int slices) { return cut_for_round(kDwRound, ns, slices); }
 static size_t dw_plan_lds(const HostGeom& geom, int n0, int ns, int k, int sp, int strips) {
     size_t lds = 0;
     for (int s = n0; s < n0 + ns; ++s) {
@@ -521,36 +541,32 @@ static size_t dw_plan_lds(const HostGeom& geom, int n0, int ns, int k, int sp, i
 }
 static DwPlan dw_plan(const HostGeom& geom, int n0, int ns, int cs, int k, int strips) {
     DwPlan dp;
-    if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || cs <= 0 || strips < 0) { dp.why = "bad argument"; return dp; }
+    if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || cs <= 0 || strips < 0) return refused(dp, "bad argument");
     for (const auto& e : kDwEntries)
         if (e.k == k) dp.e = &e;
-    if (!dp.e) { dp.why = "a depthwise layer of k = " + std::to_string(k) + " keeps depthwise_kernel (conv_dw.h has k = 3, 5, 7)"; return dp; }
-    if (cs % 32) { dp.why = "a channel stride of " + std::to_string(cs) + " is not whole 32-channel slices"; return dp; }
+    if (!dp.e) return refused(dp, "a depthwise layer of k = " + std::to_string(k) + " keeps depthwise_kernel (conv_dw.h has k = 3, 5, 7)");
+    if (cs % 32) return refused(dp, "a channel stride of " + std::to_string(cs) + " is not whole 32-channel slices");
     dp.sp = cs % 64 == 0 ? 8 : 4;
-    dp.slices = cs / (8 * dp.sp);
+    dp.tiles = cs / (8 * dp.sp);
     for (int s = n0; s < n0 + ns; ++s) dp.rows = std::max(dp.rows, geom.bsz[s]);
-    if (strips > dp.rows) {
-        dp.why = std::to_string(strips) + " strips are more than the " + std::to_string(dp.rows) + " rows of the largest board (SAYURI_DW_STRIPS / strips)";
-        return dp;
-    }
-    dp.strips = strips > 0 ? strips : std::min(dp.rows, dw_auto(ns, dp.slices));
-    dp.lds = dw_plan_lds(geom, n0, ns, k, dp.sp, dp.strips);
-    while (strips == 0 && dp.lds > kDwMaxLds && dp.strips < dp.rows) dp.lds = dw_plan_lds(geom, n0, ns, k, dp.sp, ++dp.strips);
-    if (dp.lds > kDwMaxLds) {
-        dp.why = "an item of " + std::to_string(dp.lds) + " bytes of LDS is more than the kernel's " + std::to_string(kDwMaxLds) +
-                 " (SAYURI_DW_STRIPS / strips too small for this board)";
-        return dp;
-    }
+    if (strips > dp.rows)
+        return refused(dp, std::to_string(strips) + " strips are more than the " + std::to_string(dp.rows) + " rows of the largest board (SAYURI_DW_STRIPS / strips)");
+    dp.cut = strips > 0 ? strips : std::min(dp.rows, dw_auto(ns, dp.tiles));
+    dp.lds = dw_plan_lds(geom, n0, ns, k, dp.sp, dp.cut);
+    while (strips == 0 && dp.lds > kDwMaxLds && dp.cut < dp.rows) dp.lds = dw_plan_lds(geom, n0, ns, k, dp.sp, ++dp.cut);
+    if (dp.lds > kDwMaxLds)
+        return refused(dp, "an item of " + std::to_string(dp.lds) + " bytes of LDS is more than the kernel's " + std::to_string(kDwMaxLds) +
+                               " (SAYURI_DW_STRIPS / strips too small for this board)");
     for (int s = n0; s < n0 + ns; ++s) {
-        const int bs = geom.bsz[s], rp = dw_rows(bs, dp.strips);
-        dp.smax = std::max(dp.smax, (bs + rp - 1) / rp);
+        const int bs = geom.bsz[s], rp = dw_rows(bs, dp.cut);
+        dp.items = std::max(dp.items, (bs + rp - 1) / rp);
     }
-    dp.grid = ns * dp.smax * dp.slices;
+    dp.grid = ns * dp.items * dp.tiles;
     dp.ok = true;
     return dp;
 }
 static void dw_params(DwParams& q, const DwPlan& dp, int n0) {
-    q.sp = dp.sp; q.slices = dp.slices; q.strips = dp.strips; q.smax = dp.smax; q.n0 = n0;
+    q.sp = dp.sp; q.slices = dp.tiles; q.strips = dp.cut; q.smax = dp.items; q.n0 = n0;
 }
 static void dw_launch(const DwPlan& dp, const DwParams& q, hipStream_t s) {
     hipLaunchKernelGGL(dp.e->fn, dim3(dp.grid), dim3(kDwThreads), dp.lds, s, q);
@@ -575,15 +591,15 @@ static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, 
     ConvRoute r;
     // a tower 1x1 of whole 64-channel tiles over whole 32-channel chunks: many small workgroups (conv_pw.h) where the plan fits
     // and the rule says it pays
-    if (fp16 && k == 1 && pw && pw->cout % kPwKO == 0 && pw->cin % kChunk == 0 && ko_pad % kPwKO == 0) {
+    if (fp16 && k == 1 && pw && pw_covers(pw->cin, pw->cout, ko_pad)) {
         r.pw = pw_plan(geom, pw->n0, pw->ns, ko_pad, pw->cin_s, pw->pieces);
-        if (r.pw.ok && (pw->force || pw_pays(pw->ns, r.pw.kts))) r.family = kConvPw;
+        if (r.pw.ok && (pw->force || pw_pays(pw->ns, r.pw.tiles))) r.family = kConvPw;
         return r;
     }
     if (!fp16 || k != 3) return r;
     // a latency context: many small workgroups (`split`; the plan is split_plan's) for every batch; a layer whose weight rows
     // are not whole 64-channel tiles keeps the route below
-    if (latency && ko_pad % kSplitKO == 0) { r.family = kConvSplit; return r; }
+    if (latency && split_covers(ko_pad)) { r.family = kConvSplit; return r; }
     if ((r.board = pick_board(plan, ko_pad, &r.tiles, force_kot))) r.family = kConvBoard;
     else if ((r.glds = pick_glds(geom, ko_pad, &r.tiles, ov))) r.family = kConvGlds;
     return r;
@@ -591,7 +607,7 @@ static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, 
 
 // The many-small-workgroups plan of a latency context (conv_split.h) for the samples [n0, n0 + ns) and a layer of `ko_pad`
 // weight rows: how many strips a board is cut into, the grid, the kernel variant and its LDS.
-// The split rule (strips == 0): as many strips per board as keep the launch near ONE round of the 256 CUs -- 256 / (samples x
+// The split rule (strips == 0): the cut rule (CutPlan) with a round of the 256 CUs -- 256 / (samples x
 // channel tiles), at least one, at most kSplitAutoMax and never more than a board has rows (split_rows) -- so a lone board is
 // cut finely and a batch of 64 not at all.  It decides the speed only: the results do not depend on the split.
 // The ring rule (ring == 0): the weight stages of the variant with `nj` column tiles per wave.  Like the split it decides the
@@ -599,29 +615,21 @@ static ConvRoute route_conv(bool fp16, int k, int ko_pad, const HostGeom& geom, 
 // Kernel 1h, profiles/r11_latency_ring.json): the four-stage ring is 5 to 8 % of a forward ahead at nj = 1 (one or two 19x19
 // boards, a lone small board, sixteen 9x9 boards on 256 channels) and level or up to 1.4 % behind at nj = 2 and 3, so only
 // nj = 1 takes it; the wide variants have no deeper ring.  ring == n forces n stages: where the chosen variant has no such
-// instantiation, or its LDS does not fit, the plan is not ok (bad_ring says why).
+// instantiation, or its LDS does not fit, the plan is not ok (why says so).
 constexpr int kSplitAutoMax = 19;
-struct SplitPlan {
-    bool ok = false;
-    int strips = 0, smax = 0, kts = 0, npos = 0, grid = 0, stages = 0, bad_ring = 0;
-    const SplitEntry* e = nullptr;
-    size_t lds = 0;
-};
-static int split_auto(int ns, int kts) { return std::max(1, std::min(kSplitAutoMax, kNumCU / std::max(1, ns * kts))); }
+struct SplitPlan : CutPlan { int npos = 0, stages = 0; const SplitEntry* e = nullptr; };  // cut: strips
+static int split_auto(int ns, int kts) { return std::min(kSplitAutoMax, cut_for_round(kNumCU, ns, kts)); }
 static int split_ring(int nj) { return nj == 1 ? kSplitDeepStages : kSplitStages; }
-static std::string split_refusal(const SplitPlan& sp) {
-    return sp.bad_ring ? "no split kernel with a ring of " + std::to_string(sp.bad_ring) + " weight stages fits this batch geometry (SAYURI_LATENCY_RING)"
-                       : std::string("no split fits this batch geometry");
-}
 static SplitPlan split_plan(const HostGeom& geom, int n0, int ns, int ko_pad, int strips, int ring) {
     SplitPlan sp;
-    if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || ko_pad <= 0 || ko_pad % kSplitKO) return sp;
-    sp.kts = ko_pad / kSplitKO;
-    sp.strips = strips > 0 ? strips : split_auto(ns, sp.kts);
+    sp.why = "no split fits this batch geometry";  // every refusal but the ring no variant has
+    if (ns <= 0 || n0 < 0 || n0 + ns > geom.n || !split_covers(ko_pad)) return sp;
+    sp.tiles = ko_pad / kSplitKO;
+    sp.cut = strips > 0 ? strips : split_auto(ns, sp.tiles);
     int max_pos = 0, max_cols = 0;
     for (int s = n0; s < n0 + ns; ++s) {
-        const int bs = geom.bsz[s], rp = split_rows(bs, sp.strips);
-        sp.smax = std::max(sp.smax, (bs + rp - 1) / rp);
+        const int bs = geom.bsz[s], rp = split_rows(bs, sp.cut);
+        sp.items = std::max(sp.items, (bs + rp - 1) / rp);
         max_pos = std::max(max_pos, (rp + 2) * (bs + 2));
         max_cols = std::max(max_cols, (rp * bs + 15) / 16);
     }
@@ -636,18 +644,20 @@ static SplitPlan split_plan(const HostGeom& geom, int n0, int ns, int ko_pad, in
         for (const auto& e : kSplitEntries)
             if (e.nj == sp.e->nj && e.stages == want && split_lds_bytes(sp.npos, want) <= kMaxLds) deep = &e;
         if (deep) sp.e = deep;
-        else if (ring) { sp.bad_ring = ring; return sp; }
+        else if (ring)
+            return refused(sp, "no split kernel with a ring of " + std::to_string(ring) + " weight stages fits this batch geometry (SAYURI_LATENCY_RING)");
     }
     sp.stages = sp.e->stages;
     sp.lds = split_lds_bytes(sp.npos, sp.stages);
-    sp.grid = ns * sp.smax * sp.kts;
+    sp.grid = ns * sp.items * sp.tiles;
     sp.ok = sp.lds <= kMaxLds;
+    if (sp.ok) sp.why.clear();
     return sp;
 }
 // The split kernels' part of a launch (conv_params fills q.c before): the halo bound, the split and the first sample.
 static void split_params(SplitParams& q, const SplitPlan& sp, int n0) {
     q.c.npos = sp.npos; q.c.num_pix_tiles = 0;
-    q.strips = sp.strips; q.smax = sp.smax; q.kts = sp.kts; q.n0 = n0;
+    q.strips = sp.cut; q.smax = sp.items; q.kts = sp.tiles; q.n0 = n0;
 }
 static void split_launch(const SplitPlan& sp, const SplitParams& q, hipStream_t s) {
     hipLaunchKernelGGL(sp.e->fn, dim3(sp.grid), dim3(256), sp.lds, s, q);
@@ -722,6 +732,31 @@ static int glds_params(GldsParams& gp, const GldsEntry& e, const int* tab_src, c
     gp.tab_src = tab_src; gp.tab_pix = tab_pix; gp.zeros = zeros;
     gp.c.npos = 0; gp.c.num_pix_tiles = ntiles;
     return ntiles * (gp.c.ko_pad / (e.wmt * 32));
+}
+// The convolution with the SE unit inside it (conv_board_se_kernel, the same stage in the persistent launch): the host's rule, for
+// Engine::conv_se and the taps alike.  The board entry with an SE kernel whose channel tile is the WHOLE layer, whatever the batch
+// size -- a position's result must not depend on how many others share its batch: a small batch would otherwise pick two half-width
+// workgroups and the separate SE kernels, which round x to fp16 before pooling --; pick_board_se: ... and whose LDS fits `plan`.
+static const BoardEntry* board_se_entry(int ko_pad) {
+    for (const auto& e : kBoardEntries)
+        if (e.fn_se && e.kot == ko_pad) return &e;
+    return nullptr;
+}
+static const BoardEntry* pick_board_se(const BoardPlan& plan, int ko_pad) {
+    const BoardEntry* e = plan.ok ? board_se_entry(ko_pad) : nullptr;
+    return e && e->lds(plan.npos) <= kMaxLds ? e : nullptr;
+}
+// A unit whose images are not staged in LDS (make_se_images refused it) still runs inside the kernel with its FCs read from L2
+// when the FC widths suit the kernel's loops: squeeze outputs and excite outputs in whole fours that divide 512 lanes' work.
+static bool se_l2_form_ok(int sq_out, int ex_out) {
+    if (sq_out <= 0 || ex_out <= 0 || sq_out % 4 || ex_out % 4) return false;  // (in front of the divisions)
+    return sq_out <= 512 && ex_out <= 2048 && 512 % (sq_out / 4) == 0 && 512 % (ex_out / 4) == 0;
+}
+// The stage's own fields of a launch: the two FCs, the channels, and -- both or neither -- the staged images (null: the L2 form).
+static void se_stage_params(BoardSeParams& sp, const FcDev& sq, const FcDev& ex, int C, const void* w1h, const void* w2h, int w1_bytes,
+                            int w2_bytes) {
+    sp.squeeze = sq; sp.excite = ex; sp.C = C;
+    sp.w1h = w1h; sp.w2h = w2h; sp.w1_bytes = w1_bytes; sp.w2_bytes = w2_bytes;
 }
 // The split-channel SE convolution (conv_board_sx.h): which boards it takes, its board kernel entry, its part of a launch and
 // its grid.  A board takes the form when at most kSxMaxSub samples of its size fit a tile (9x9 and larger): the kernel pools

@@ -1,8 +1,9 @@
 // engine_taps.h -- layer-level test taps of the C-ABI (sayuri_hip_test_*): one kernel family at a time on host tensors, for the
 // parity tests (tests/test_gpu_layers.py, test_gpu_smallops.py, test_gpu_input.py).  Not used by the pipe.  A tap converts the layouts on the host,
 // in and out, and launches ONE layer -- sayuri_hip_test_tower_run one RUN of layers, as one persistent launch; the device images,
-// the routing of a convolution to its kernel family, the launch parameters and the linking of a run are the engine's own code
-// (engine_plan.h), so the tests check the host code the engine runs.
+// the routing of a convolution to its kernel family, the plans, the rule and the parameters of the fused SE stage, the launch
+// parameters and the linking of a run are the engine's own code (engine_plan.h), so the tests check the host code the engine runs.
+// The taps' own: the staging of host tensors and, where a comment says so, a deliberately different choice of variant.
 #pragma once
 #include "engine_graph.h"
 
@@ -43,14 +44,7 @@ private:
 };
 
 static int make_test_geom(TestArena& A, int n, const int* board_sizes, int max_board, TestGeom* tg) {
-    tg->hg.n = n;
-    tg->hg.bsz.assign(board_sizes, board_sizes + n);
-    tg->hg.off.assign(n + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        if (tg->hg.bsz[i] < 2 || tg->hg.bsz[i] > max_board) return fail("test tap: bad board size");
-        tg->hg.off[i + 1] = tg->hg.off[i] + tg->hg.bsz[i] * tg->hg.bsz[i];
-    }
-    tg->hg.total = tg->hg.off[n];
+    if (host_geom(n, board_sizes, max_board, "test tap", &tg->hg)) return -1;
     tg->slot = max_board * max_board;
     tg->d_off = A.upload(tg->hg.off);
     tg->d_bsz = A.upload(tg->hg.bsz);
@@ -83,6 +77,35 @@ template <typename T> static int nhwc_to_nchw(const TestGeom& tg, const T* dev, 
     }
     return 0;
 }
+// The device side of a convolution tap: x [n][cx][bs*bs] behind the zero prefix, the residual (null: none) and y with `cy` channels
+// -- y starts as fp16 NaN (0xffff: what comes back finite was written) or as zero --, the layer's weight image and bias (empty:
+// the tap uploads its own).  0, or the tap's "...: hipMalloc failed".
+template <typename T> struct TapBufs {
+    const T *x = nullptr, *res = nullptr;
+    T* y = nullptr;
+    const void* w = nullptr;
+    const float* bias = nullptr;
+};
+template <typename T, typename W>
+static int stage_conv_tap(TestArena& A, const TestGeom& tg, const char* tap, const float* x, int cx, int cx_s, const float* res, int cy,
+                          int cy_s, bool y_nan, const std::vector<W>& w_img, const std::vector<float>& bias_img, TapBufs<T>* b) {
+    const size_t y_bytes = (size_t)tg.hg.n * tg.slot * cy_s * sizeof(T);
+    b->x = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, cx, cx_s));
+    b->res = res ? A.upload(nchw_to_nhwc<T>(tg, res, cy, cy_s)) : nullptr;
+    b->y = (T*)A.alloc(y_bytes);
+    if (!w_img.empty()) b->w = A.upload(w_img);
+    if (!bias_img.empty()) b->bias = A.upload(bias_img);
+    if (!b->x || (res && !b->res) || !b->y || (!w_img.empty() && !b->w) || (!bias_img.empty() && !b->bias))
+        return fail(std::string(tap) + ": hipMalloc failed");
+    if (y_nan) HIP_OK(hipMemset(b->y, 0xff, y_bytes));
+    return 0;
+}
+// ... and its end: the launch's status, the device's, y back in host NCHW.
+template <typename T> static int finish(const TestGeom& tg, const T* dy, int C, int cs, float* y) {
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    return nhwc_to_nchw(tg, dy, C, cs, y);
+}
 // The index tables of the board kernels for `plan` (board_setup_kernel), as board_params takes them.  false: out of memory.
 struct TestBoardTabs { int* src; int2* pix; int* cols; };
 static bool make_board_tabs(TestArena& A, const TestGeom& tg, const BoardPlan& plan, TestBoardTabs* t) {
@@ -107,24 +130,20 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
     if (make_test_geom(A, n, board_sizes, max_board, &tg)) return -1;
     const HostGeom& hg = tg.hg;
     const int cin_s = round_up(depthwise ? cout : cin, 32), cout_s = round_up(cout, 32);
-    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, depthwise ? cout : cin, cin_s));
-    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, cout, cout_s)) : nullptr;
-    T* dy = (T*)A.alloc((size_t)n * tg.slot * cout_s * sizeof(T));
-    if (!dx || !dy || (res && !dres)) return fail("test_conv: hipMalloc failed");
+    int wmt, ko_pad;
+    conv_tile(cout_s, sizeof(T) == 2, &wmt, &ko_pad);
+    TapBufs<T> b;
+    if (depthwise ? stage_conv_tap(A, tg, "test_conv", x, cout, cin_s, res, cout, cout_s, false, depthwise_image(w, cout, k * k, cout_s),
+                                   padded_bias(bias, cout, cout_s), &b)
+                  : stage_conv_tap(A, tg, "test_conv", x, cin, cin_s, res, cout, cout_s, false, conv_image<T>(w, cin, cout, k * k, ko_pad),
+                                   padded_bias(bias, cout, ko_pad), &b))
+        return -1;
     if (depthwise) {
         g_test_conv_kind = kConvDepthwise;
-        const float* dw = A.upload(depthwise_image(w, cout, k * k, cout_s));
-        const float* db = A.upload(padded_bias(bias, cout, cout_s));
-        if (!dw || !db) return fail("test_conv: hipMalloc failed");
         const size_t total = (size_t)hg.total * (cout_s / ElemTraits<T>::kPieceElems);
-        hipLaunchKernelGGL(depthwise_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, dx, post_residual ? dres : (const T*)nullptr,
-                           dy, dw, db, tg.g, cout, cout_s, k, act);
+        hipLaunchKernelGGL(depthwise_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, b.x, post_residual ? b.res : (const T*)nullptr,
+                           b.y, (const float*)b.w, b.bias, tg.g, cout, cout_s, k, act);
     } else {
-        int wmt, ko_pad;
-        conv_tile(cout_s, sizeof(T) == 2, &wmt, &ko_pad);
-        const T* dw = A.upload(conv_image<T>(w, cin, cout, k * k, ko_pad));
-        const float* db = A.upload(padded_bias(bias, cout, ko_pad));
-        if (!dw || !db) return fail("test_conv: hipMalloc failed");
         const ConvOverride ov = EngineFlags::from_env().conv;
         const BoardPlan plan = board_plan(hg, ov);
         const ConvRoute r = route_conv(sizeof(T) == 2, k, ko_pad, hg, plan, ov);
@@ -134,7 +153,7 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
             if (!make_board_tabs(A, tg, plan, &tabs)) return fail("test_conv: hipMalloc failed");
             BoardParams bp;
             board_params(bp, plan, tabs.src, tabs.pix, tabs.cols, true);
-            conv_params(bp.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 9, act);
+            conv_params(bp.c, b.x, b.w, b.bias, b.res, b.y, tg.g, cin_s, cout_s, ko_pad, 9, act);
             bp.c.npos = 0; bp.c.num_pix_tiles = plan.ntiles;
             hipLaunchKernelGGL(r.board->fn, dim3(plan.ntiles * r.tiles), dim3(512), r.board->lds(plan.npos), 0, bp);
         } else if (r.glds) {
@@ -144,7 +163,7 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
             if (!dz || !tsrc || !tpix) return fail("test_conv: hipMalloc failed");
             hipLaunchKernelGGL(r.glds->setup, dim3(r.tiles), dim3(256), 0, 0, tg.g, tsrc, tpix);
             GldsParams gp;
-            conv_params(gp.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 9, act);
+            conv_params(gp.c, b.x, b.w, b.bias, b.res, b.y, tg.g, cin_s, cout_s, ko_pad, 9, act);
             const int grid = glds_params(gp, *r.glds, tsrc, tpix, dz, r.tiles);
             hipLaunchKernelGGL(r.glds->fn, dim3(grid), dim3(512), r.glds->lds, 0, gp);
         } else {
@@ -152,14 +171,12 @@ static int test_conv_impl(int device, int n, const int* board_sizes, int max_boa
             TileChoice<T> tc;
             if (!pick_tile<T>(hg, wmt, ko_pad / (wmt * 32), /*widest=*/true, &tc)) return fail("test_conv: no tile configuration fits");
             ConvParams p;
-            conv_params(p, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, k * k, act);
+            conv_params(p, b.x, b.w, b.bias, b.res, b.y, tg.g, cin_s, cout_s, ko_pad, k * k, act);
             p.npos = tc.npos; p.num_pix_tiles = tc.ntiles;
             hipLaunchKernelGGL(tc.e->fn, dim3(tc.ntiles * (ko_pad / (wmt * 32))), dim3(512), tc.e->lds(tc.npos), 0, p);
         }
     }
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
-    return nhwc_to_nchw(tg, dy, cout, cout_s, y);
+    return finish(tg, b.y, cout, cout_s, y);
 }
 
 // The same fp16 3x3 layer as many small workgroups (conv_split.h, the latency context's route): the engine's image in natural
@@ -177,29 +194,24 @@ static int test_conv_split_impl(int device, int n, const int* board_sizes, int m
     const int cin_s = round_up(cin, 32), cout_s = round_up(cout, 32);
     int wmt, ko_pad;
     conv_tile(cout_s, true, &wmt, &ko_pad);
-    const ConvRoute r = route_conv(true, 3, ko_pad, tg.hg, BoardPlan{}, ConvOverride{}, 0, /*latency=*/true);
-    if (r.family != kConvSplit) return fail("test_conv_split: a layer of " + std::to_string(ko_pad) + " weight rows is not whole 64-channel tiles: it keeps the default route");
+    if (!split_covers(ko_pad)) return fail("test_conv_split: a layer of " + std::to_string(ko_pad) + " weight rows is not whole 64-channel tiles: it keeps the default route");
     if (channel_tiles && channel_tiles != ko_pad / kSplitKO)
         return fail("test_conv_split: the split kernel's channel tile is 64: this layer has " + std::to_string(ko_pad / kSplitKO) + " channel tiles");
     if (strips < 0) return fail("test_conv_split: bad strip count");
     const SplitPlan sp = split_plan(tg.hg, 0, n, ko_pad, strips, EngineFlags::from_env().latency_ring);
-    if (!sp.ok) return fail("test_conv_split: " + split_refusal(sp));
-    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, cin, cin_s));
-    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, cout, cout_s)) : nullptr;
-    T* dy = (T*)A.alloc((size_t)n * tg.slot * cout_s * sizeof(T));
-    const T* dw = A.upload(conv_image<T>(w, cin, cout, 9, ko_pad));
-    const float* db = A.upload(padded_bias(bias, cout, ko_pad));
-    if (!dx || !dy || (res && !dres) || !dw || !db) return fail("test_conv_split: hipMalloc failed");
+    if (!sp.ok) return fail("test_conv_split: " + sp.why);
+    TapBufs<T> b;
+    if (stage_conv_tap(A, tg, "test_conv_split", x, cin, cin_s, res, cout, cout_s, false, conv_image<T>(w, cin, cout, 9, ko_pad),
+                       padded_bias(bias, cout, ko_pad), &b))
+        return -1;
     g_test_conv_kind = kConvSplit;
     g_test_split_ring = sp.stages;
     SplitParams q;
     std::memset(&q, 0, sizeof(q));
-    conv_params(q.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 9, act);
+    conv_params(q.c, b.x, b.w, b.bias, b.res, b.y, tg.g, cin_s, cout_s, ko_pad, 9, act);
     split_params(q, sp, 0);
     split_launch(sp, q, nullptr);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
-    return nhwc_to_nchw(tg, dy, cout, cout_s, y);
+    return finish(tg, b.y, cout, cout_s, y);
 }
 
 // The fp16 1x1 case of test_conv_impl through conv_pw.h (the route of a tower 1x1 layer): the engine's image, route_conv's plan.
@@ -217,29 +229,23 @@ static int test_conv_pw_impl(int device, int n, const int* board_sizes, int max_
     const int cin_s = round_up(cin, 32), cout_s = round_up(cout, 32);
     int wmt, ko_pad;
     conv_tile(cout_s, true, &wmt, &ko_pad);
-    const PwAsk ask{cin, cout, cin_s, 0, n, pieces, /*force=*/true};
-    const ConvRoute r = route_conv(true, 1, ko_pad, tg.hg, BoardPlan{}, ConvOverride{}, 0, false, &ask);
-    if (cout % kPwKO || cin % kChunk)
+    if (!pw_covers(cin, cout, ko_pad))
         return fail("test_conv_pw: a layer of " + std::to_string(cin) + " -> " + std::to_string(cout) +
                     " channels is not whole 32-channel chunks into whole 64-channel tiles: it keeps the generic kernel");
-    if (!r.pw.ok) return fail("test_conv_pw: " + pw_refusal(r.pw));
-    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, cin, cin_s));
-    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, cout, cout_s)) : nullptr;
-    const size_t y_bytes = (size_t)n * tg.slot * cout_s * sizeof(T);
-    T* dy = (T*)A.alloc(y_bytes);
-    const T* dw = A.upload(conv_image<T>(w, cin, cout, 1, ko_pad));
-    const float* db = A.upload(padded_bias(bias, cout, ko_pad));
-    if (!dx || !dy || (res && !dres) || !dw || !db) return fail("test_conv_pw: hipMalloc failed");
-    HIP_OK(hipMemset(dy, 0xff, y_bytes));  // fp16 0xffff: a NaN
+    const PwAsk ask{cin, cout, cin_s, 0, n, pieces, /*force=*/true};
+    const ConvRoute r = route_conv(true, 1, ko_pad, tg.hg, BoardPlan{}, ConvOverride{}, 0, false, &ask);
+    if (!r.pw.ok) return fail("test_conv_pw: " + r.pw.why);
+    TapBufs<T> b;
+    if (stage_conv_tap(A, tg, "test_conv_pw", x, cin, cin_s, res, cout, cout_s, /*y_nan=*/true, conv_image<T>(w, cin, cout, 1, ko_pad),
+                       padded_bias(bias, cout, ko_pad), &b))
+        return -1;
     g_test_conv_kind = kConvPw;
     PwParams q;
     std::memset(&q, 0, sizeof(q));
-    conv_params(q.c, dx, dw, db, dres, dy, tg.g, cin_s, cout_s, ko_pad, 1, act);
+    conv_params(q.c, b.x, b.w, b.bias, b.res, b.y, tg.g, cin_s, cout_s, ko_pad, 1, act);
     pw_params(q, r.pw, 0);
     pw_launch(r.pw, q, nullptr);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
-    return nhwc_to_nchw(tg, dy, cout, cout_s, y);
+    return finish(tg, b.y, cout, cout_s, y);
 }
 
 // The pad channels [C, cs) of every board pixel (sample-major, pixel-major) as the last sayuri_hip_test_conv_dw call found them, raw
@@ -268,23 +274,18 @@ static int test_conv_dw_impl(int device, int n, const int* board_sizes, int max_
     const int cs = round_up(C, 32);
     const DwPlan dp = dw_plan(tg.hg, 0, n, cs, k, strips);
     if (!dp.ok) return fail("test_conv_dw: " + dp.why);
-    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, C, cs));
-    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
+    TapBufs<T> b;
+    if (stage_conv_tap(A, tg, "test_conv_dw", x, C, cs, res, C, cs, /*y_nan=*/true, depthwise_image(w, C, k * k, cs), padded_bias(bias, C, cs), &b))
+        return -1;
+    const float* dw = (const float*)b.w;
     const size_t y_bytes = (size_t)n * tg.slot * cs * sizeof(T);
-    T* dy = (T*)A.alloc(y_bytes);
-    const float* dw = A.upload(depthwise_image(w, C, k * k, cs));
-    const float* db = A.upload(padded_bias(bias, C, cs));
-    if (!dx || !dy || (res && !dres) || !dw || !db) return fail("test_conv_dw: hipMalloc failed");
-    HIP_OK(hipMemset(dy, 0xff, y_bytes));  // fp16 0xffff: a NaN
     g_test_conv_kind = kConvDwLds;
     DwParams q;
     std::memset(&q, 0, sizeof(q));
-    q.x = dx; q.res = dres; q.out = dy; q.wt = dw; q.bias = db;
+    q.x = b.x; q.res = b.res; q.out = b.y; q.wt = dw; q.bias = b.bias;
     q.g = tg.g; q.C = C; q.cs = cs; q.act = act;
     dw_params(q, dp, 0);
     dw_launch(dp, q, nullptr);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
     g_test_dw_pad[0].clear();
     g_test_dw_pad[1].clear();
     if (cs > C) {  // what both kernels leave in the pad channels: depthwise_kernel into a NaN buffer of its own, same operands
@@ -292,12 +293,12 @@ static int test_conv_dw_impl(int device, int n, const int* board_sizes, int max_
         if (!dold) return fail("test_conv_dw: hipMalloc failed");
         HIP_OK(hipMemset(dold, 0xff, y_bytes));
         const size_t total = (size_t)tg.hg.total * (cs / ElemTraits<T>::kPieceElems);
-        hipLaunchKernelGGL(depthwise_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, dx, dres, dold, dw, db, tg.g, C, cs, k, act);
+        hipLaunchKernelGGL(depthwise_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, b.x, b.res, dold, dw, b.bias, tg.g, C, cs, k, act);
         HIP_OK(hipGetLastError());
         HIP_OK(hipDeviceSynchronize());
-        if (read_dw_pad(tg, dy, C, cs, &g_test_dw_pad[0]) || read_dw_pad(tg, dold, C, cs, &g_test_dw_pad[1])) return -1;
+        if (read_dw_pad(tg, b.y, C, cs, &g_test_dw_pad[0]) || read_dw_pad(tg, dold, C, cs, &g_test_dw_pad[1])) return -1;
     }
-    return nhwc_to_nchw(tg, dy, C, cs, y);
+    return finish(tg, b.y, C, cs, y);
 }
 
 template <typename T>
@@ -409,6 +410,16 @@ static int test_head_tail_impl(int device, int n, const int* board_sizes, int ma
     return o.download(prob, pass, misc, own);
 }
 
+// An SE unit's two FCs as handed over the ABI and -- img1 != null -- its staged images on the device, as se_stage_params takes
+// them.  false: out of memory.
+static bool upload_se_stage(TestArena& A, BoardSeParams& sp, int C, int se, const float* w1, const float* b1, const float* w2, const float* b2,
+                            const std::vector<f16>* img1, const std::vector<unsigned char>* img2, int w1_bytes, int w2_bytes) {
+    const FcDev sq{A.upload(fc_transposed(w1, 3 * C, se)), A.upload(std::vector<float>(b1, b1 + se)), 3 * C, se};
+    const FcDev ex{A.upload(fc_transposed(w2, se, 2 * C)), A.upload(std::vector<float>(b2, b2 + 2 * C)), se, 2 * C};
+    se_stage_params(sp, sq, ex, C, img1 ? A.upload(*img1) : nullptr, img1 ? A.upload(*img2) : nullptr, w1_bytes, w2_bytes);
+    return sq.wt && sq.b && ex.wt && ex.b && (!img1 || (sp.w1h && sp.w2h));
+}
+
 // The convolution with the SE unit inside it (conv_board_se_kernel, or the same stage inside the persistent tower kernel
 // when via_tower != 0): C -> C 3x3 convolution + bias, then the unit's pool -> FC -> FC -> act(sigmoid(g) x + b + res).
 // Returns 1 when the fused kernel does not apply to this batch (several samples per tile, channel tile not 128 / 256).
@@ -427,28 +438,24 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     int wmt, ko_pad;
     conv_tile(cs, true, &wmt, &ko_pad);
     const BoardPlan plan = board_plan(tg.hg, ConvOverride{});
-    const BoardEntry* be = nullptr;
-    if (plan.ok)
-        for (const auto& e : kBoardEntries)
-            if (e.fn_se && e.kot == ko_pad && e.lds(plan.npos) <= kMaxLds) be = &e;
+    const BoardEntry* be = pick_board_se(plan, ko_pad);
     // (deliberately the kernel's own rule, one sample per tile -- not Engine::conv_se's, which fuses only boards too large to share a tile)
     if (!be || !plan.single || C > be->kot) return 1;
     std::vector<f16> img1;
     std::vector<unsigned char> img2;
     int w1_bytes = 0, w2_bytes = 0;
     const bool staged = make_se_images(C, se, max_board, w1, b1, w2, b2, &img1, &img2, &w1_bytes, &w2_bytes);
-    if (!staged && (se % 4 || se > 512 || (2 * C) % 4 || 512 % (se / 4) || 512 % (2 * C / 4))) return 1;
-    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, C, cs));
-    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
-    T* dy = (T*)A.alloc((size_t)n * tg.slot * cs * sizeof(T));
+    if (!staged && !se_l2_form_ok(se, 2 * C)) return 1;  // (nothing of the layer is uploaded or launched yet)
+    TapBufs<T> b;
     TestBoardTabs tabs;
-    if (!dx || (res && !dres) || !dy || !make_board_tabs(A, tg, plan, &tabs)) return fail("test_conv_se: hipMalloc failed");
+    if (stage_conv_tap(A, tg, "test_conv_se", x, C, cs, res, C, cs, false, std::vector<T>(), std::vector<float>(), &b)) return -1;
+    if (!make_board_tabs(A, tg, plan, &tabs)) return fail("test_conv_se: hipMalloc failed");
     BoardSeParams sp;
     std::memset(&sp, 0, sizeof(sp));
     BoardParams& bp = sp.b;
     board_params(bp, plan, tabs.src, tabs.pix, tabs.cols, true);
     ConvParams& p = bp.c;
-    conv_params(p, dx, nullptr, nullptr, dres, dy, tg.g, cs, cs, ko_pad, 9, act);
+    conv_params(p, b.x, nullptr, nullptr, b.res, b.y, tg.g, cs, cs, ko_pad, 9, act);
     p.num_pix_tiles = plan.ntiles;
     // through the tower a layer the generated epilogue covers takes its weights and bias in board_row_channel order, as in Engine::board_launch
     bp.row_order = via_tower && board_row_order_ok(bp, be->kot, !EngineFlags::off("SAYURI_TOWER_GEN_EPI")) ? 1 : 0;
@@ -456,13 +463,7 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     const std::vector<float> hb = padded_bias(bias, C, ko_pad);
     p.w = A.upload(bp.row_order ? board_row_order(img, ko_pad) : img);
     p.bias = A.upload(bp.row_order ? board_row_order(hb, ko_pad, 1) : hb);
-    sp.squeeze = FcDev{A.upload(fc_transposed(w1, 3 * C, se)), A.upload(std::vector<float>(b1, b1 + se)), 3 * C, se};
-    sp.excite = FcDev{A.upload(fc_transposed(w2, se, 2 * C)), A.upload(std::vector<float>(b2, b2 + 2 * C)), se, 2 * C};
-    sp.C = C;
-    sp.w1h = staged ? A.upload(img1) : nullptr;
-    sp.w2h = staged ? A.upload(img2) : nullptr;
-    sp.w1_bytes = w1_bytes; sp.w2_bytes = w2_bytes;
-    if (!p.w || !p.bias || !sp.squeeze.wt || !sp.squeeze.b || !sp.excite.wt || !sp.excite.b || (staged && (!sp.w1h || !sp.w2h)))
+    if (!p.w || !p.bias || !upload_se_stage(A, sp, C, se, w1, b1, w2, b2, staged ? &img1 : nullptr, &img2, w1_bytes, w2_bytes))
         return fail("test_conv_se: hipMalloc failed");
     hipModule_t mod = nullptr;
     g_test_se_form = sp.w1h ? 1 : 2;  // what both kernels branch on (board_se_pool / board_se_fc, the seam's image staging)
@@ -481,10 +482,9 @@ static int test_conv_se_impl(int device, int n, const int* board_sizes, int max_
     } else {
         hipLaunchKernelGGL(be->fn_se, dim3(plan.ntiles), dim3(512), be->lds(plan.npos), 0, sp);
     }
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
+    const int rc = finish(tg, b.y, C, cs, y);
     if (mod) (void)hipModuleUnload(mod);
-    return nhwc_to_nchw(tg, dy, C, cs, y);
+    return rc;
 }
 
 // A RUN of 1..8 board convolutions as ONE launch of the persistent tower kernel (conv_tower.h): layer 0 is cin0 -> C, every later
@@ -518,10 +518,7 @@ static int test_tower_run_impl(int device, int n, const int* board_sizes, int ma
     int wmt, ko_pad;
     conv_tile(C, true, &wmt, &ko_pad);
     const BoardPlan plan = board_plan(tg.hg, ConvOverride{});
-    const BoardEntry* be = nullptr;
-    if (plan.ok)
-        for (const auto& e : kBoardEntries)
-            if (e.kot == ko_pad && e.lds(plan.npos) <= kMaxLds) be = &e;
+    const BoardEntry* be = pick_board_se(plan, ko_pad);  // (both channel tiles of the tower kernel have the SE stage)
     if (!be) return 1;
     // the SE layer: the rule of sayuri_hip_test_conv_se (one sample per tile; the images staged, or FC widths the L2 form takes)
     const bool has_unit = se.layer >= 0;
@@ -531,9 +528,9 @@ static int test_tower_run_impl(int device, int n, const int* board_sizes, int ma
     bool staged = false;
     if (has_unit) {
         if (!se.w1 || !se.b1 || !se.w2 || !se.b2) return fail("test_tower_run: the SE layer's weights are missing");
-        if (!be->fn_se || !plan.single) return fail("test_tower_run: the SE stage needs one sample per tile");
+        if (!plan.single) return fail("test_tower_run: the SE stage needs one sample per tile");
         staged = make_se_images(C, se.se, max_board, se.w1, se.b1, se.w2, se.b2, &img1, &img2, &w1_bytes, &w2_bytes);
-        if (!staged && (se.se <= 0 || se.se % 4 || se.se > 512 || (2 * C) % 4 || 512 % (se.se / 4) || 512 % (2 * C / 4)))
+        if (!staged && !se_l2_form_ok(se.se, 2 * C))
             return fail("test_tower_run: no form of the SE stage takes this SE width");
     }
     const size_t act_bytes = (size_t)n * tg.slot * C * sizeof(T);
@@ -570,16 +567,8 @@ static int test_tower_run_impl(int device, int n, const int* board_sizes, int ma
         p.w = A.upload(bp.row_order ? board_row_order(img, ko_pad) : img);
         p.bias = A.upload(bp.row_order ? board_row_order(hb, ko_pad, 1) : hb);
         if (!p.w || !p.bias) return fail("test_tower_run: hipMalloc failed");
-        if (unit) {
-            sp.squeeze = FcDev{A.upload(fc_transposed(se.w1, 3 * C, se.se)), A.upload(std::vector<float>(se.b1, se.b1 + se.se)), 3 * C, se.se};
-            sp.excite = FcDev{A.upload(fc_transposed(se.w2, se.se, 2 * C)), A.upload(std::vector<float>(se.b2, se.b2 + 2 * C)), se.se, 2 * C};
-            sp.C = C;
-            sp.w1h = staged ? A.upload(img1) : nullptr;
-            sp.w2h = staged ? A.upload(img2) : nullptr;
-            sp.w1_bytes = w1_bytes; sp.w2_bytes = w2_bytes;
-            if (!sp.squeeze.wt || !sp.squeeze.b || !sp.excite.wt || !sp.excite.b || (staged && (!sp.w1h || !sp.w2h)))
-                return fail("test_tower_run: hipMalloc failed");
-        }
+        if (unit && !upload_se_stage(A, sp, C, se.se, se.w1, se.b1, se.w2, se.b2, staged ? &img1 : nullptr, &img2, w1_bytes, w2_bytes))
+            return fail("test_tower_run: hipMalloc failed");
         run.push_back(tower_element(sp, unit));
     }
     TowerLayer* dt = (TowerLayer*)A.alloc(sizeof(TowerLayer) * nlayers);
@@ -643,33 +632,28 @@ static int test_conv_sx_impl(int device, int n, const int* board_sizes, int max_
     if (!be) return 1;
     for (int i = 0; i < n; ++i)
         if (!sx_board_fused(tg.hg.bsz[i])) return 1;
-    const T* dx = A.upload_prefixed(nchw_to_nhwc<T>(tg, x, C, cs));
-    const T* dres = res ? A.upload(nchw_to_nhwc<T>(tg, res, C, cs)) : nullptr;
-    T* dy = (T*)A.alloc((size_t)n * tg.slot * cs * sizeof(T));
-    const T* dw = A.upload(conv_image<T>(w, C, C, 9, ko_pad));
-    const float* db = A.upload(padded_bias(bias, C, ko_pad));
+    TapBufs<T> b;  // y starts as fp16 NaN (0xffff): an output no workgroup wrote comes back as NaN, not as a plausible 0
+    if (stage_conv_tap(A, tg, "test_conv_sx", x, C, cs, res, C, cs, /*y_nan=*/true, conv_image<T>(w, C, C, 9, ko_pad), padded_bias(bias, C, ko_pad), &b))
+        return -1;
     const f16* d1 = A.upload(img1);
     const unsigned char* d2 = A.upload(img2);
     unsigned long long* xchg = (unsigned long long*)A.alloc(sizeof(unsigned long long) * (size_t)plan.ntiles * kts * kSxMaxSub * kSxSlots);
     TestBoardTabs tabs;
     TestHostWord err;
-    if (!dx || (res && !dres) || !dy || !dw || !db || !d1 || !d2 || !xchg || !make_board_tabs(A, tg, plan, &tabs) || !err.alloc())
+    if (!d1 || !d2 || !xchg || !make_board_tabs(A, tg, plan, &tabs) || !err.alloc())
         return fail("test_conv_sx: hipMalloc failed");
     BoardSxParams sp;
     std::memset(&sp, 0, sizeof(sp));
     board_params(sp.b, plan, tabs.src, tabs.pix, tabs.cols, true);
-    conv_params(sp.b.c, dx, dw, db, dres, dy, tg.g, cs, cs, ko_pad, 9, act);
+    conv_params(sp.b.c, b.x, b.w, b.bias, b.res, b.y, tg.g, cs, cs, ko_pad, 9, act);
     sp.b.c.npos = 0; sp.b.c.num_pix_tiles = plan.ntiles;
     sx_params(sp, d1, d2, w1_bytes, w2_bytes, max_board, se, kts, xchg, kEpoch, err.dev, /*dbg_stall=*/false);
-    // y starts as fp16 NaN (0xffff): an output no workgroup wrote comes back as NaN, not as a plausible 0
-    HIP_OK(hipMemset(dy, 0xff, (size_t)n * tg.slot * cs * sizeof(T)));
     g_test_conv_kind = kConvBoardSx;
     g_test_sx_kts = kts;
     hipLaunchKernelGGL(conv_board_sx_kernel<2>, dim3(sx_grid(plan.ntiles, kts)), dim3(512), be->lds(plan.npos), 0, sp);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
-    if (*(volatile unsigned*)err.host) return fail("test_conv_sx: a workgroup's wait for its sibling channel tiles ran out");
-    return nhwc_to_nchw(tg, dy, C, cs, y);
+    const int rc = finish(tg, b.y, C, cs, y);
+    if (rc == 0 && *(volatile unsigned*)err.host) return fail("test_conv_sx: a workgroup's wait for its sibling channel tiles ran out");
+    return rc;
 }
 
 // Both heads of a sample in one workgroup (head_board_kernel): trunk [n][C][bs*bs] -> the four output tensors.

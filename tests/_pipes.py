@@ -1,12 +1,13 @@
 """Context-level helpers that more than one GPU test module uses: a pipe created under exactly the engine switches a test asks
-for, the fuzz's pool of positions and its page-locked ticket buffers, and the whole-network parity check with its fp16 bound
+for, planes on the NN grid, a forward against the CPU oracle, interleaved device timing, the fuzz's pool of positions and its page-locked ticket buffers, and the whole-network parity check with its fp16 bound
 (test_gpu_net.py's docstring accounts for the tolerances)."""
+import ctypes
 import os
 
 import numpy as np
 
 from _oracle import PortNet
-from sayuri_amd import hipraw
+from sayuri_amd import _lib, hipraw
 from sayuri_amd import weights as W
 from sayuri_amd.engine import pack_planes
 from sayuri_amd.pipe import HipForwardPipe
@@ -20,11 +21,10 @@ SWITCHES = ("SAYURI_SE_FUSED", "SAYURI_SE_SPLIT", "SAYURI_TOWER", "SAYURI_LATENC
             "SAYURI_DEBUG_RECYCLE_INPUT")
 
 
-def make_pipe(path, env=None, latency=False, batch=MAXB, fp16=True):
-    """A pipe created under exactly `env` of the engine's switches (they are read once, at creation)."""
-    keep = {k: os.environ.get(k) for k in SWITCHES}
-    for k in SWITCHES:
-        os.environ.pop(k, None)
+def make_pipe(path, env=None, latency=False, batch=MAXB, fp16=True, switches=()):
+    """A pipe created under exactly `env` of the engine's switches (they are read once, at creation); `switches`: a feature's
+    own, set as `env` says and put back afterwards like the rest."""
+    keep = {k: os.environ.pop(k, None) for k in SWITCHES + tuple(switches)}
     os.environ.update(env or {})
     try:
         return HipForwardPipe(path, board_size=B, batch_size=batch, fp16=fp16, latency=latency)
@@ -33,6 +33,19 @@ def make_pipe(path, env=None, latency=False, batch=MAXB, fp16=True):
             os.environ.pop(k, None)
             if v is not None:
                 os.environ[k] = v
+
+
+def make_pipe_under(switches, path, env=None, **kw):
+    """make_pipe with exactly these switches of a feature set as `env` says, and put back afterwards"""
+    return make_pipe(path, env, switches=switches, **kw)
+
+
+def grid_of(planes, bsz, board=B):
+    """per-sample planes [43][bs*bs] on the NN grid of `board`: [n][43][board*board], zero outside a sample's board"""
+    gr = np.zeros((len(bsz), 43, board * board), np.float32)
+    for i, (p, bs) in enumerate(zip(planes, bsz)):
+        gr[i].reshape(43, board, board)[:, :bs, :bs] = p.reshape(43, bs, bs)
+    return gr
 
 
 class Pool:
@@ -94,6 +107,34 @@ FP16_ATOL = 4e-3  # times max(1, output scale): fp16_tol()
 
 def fp16_tol(exp):
     return FP16_ATOL * max(1.0, float(np.abs(exp).max()))
+
+
+def within_oracle(exp, outs, i, bs, what):
+    """sample i of a forward's raw outputs against the CPU oracle's (prob, pass, misc, own) of its position"""
+    e_prob, e_pass, e_misc, e_own = exp
+    tol = fp16_tol(np.concatenate([e_prob.ravel(), e_own.ravel(), e_misc.ravel()]))
+    crop = lambda a: a.reshape(B, B)[:bs, :bs].ravel()
+    for k in range(e_prob.shape[0]):
+        assert np.abs(crop(outs[0][i, k]) - e_prob[k]).max() <= tol, (what, i, bs, "prob", k)
+    assert np.abs(outs[1][i] - e_pass).max() <= tol and np.abs(outs[2][i] - e_misc).max() <= tol, (what, i, bs)
+    assert np.abs(crop(outs[3][i]) - e_own).max() <= tol, (what, i, bs, "own")
+
+
+def device_ms(pipes, gr, sizes, rounds=3, iters=100):
+    """device ms per forward (sayuri_hip_time_runs), inputs resident, the contexts interleaved: medians of `rounds` x `iters`"""
+    lib = _lib.hip()
+    bs = np.asarray(sizes, np.int32)
+    times = {k: [] for k in pipes}
+    for p in pipes.values():
+        assert lib.sayuri_hip_upload(p.ctx(0), len(sizes), _lib.fp(gr), bs.ctypes.data_as(_lib.c_int_p)) == 0
+        ms = ctypes.c_float(0)
+        assert lib.sayuri_hip_time_runs(p.ctx(0), 30, ctypes.byref(ms)) == 0   # warm-up
+    for _ in range(rounds):
+        for k, p in pipes.items():
+            ms = ctypes.c_float(0)
+            assert lib.sayuri_hip_time_runs(p.ctx(0), iters, ctypes.byref(ms)) == 0, lib.sayuri_hip_last_error()
+            times[k].append(ms.value / iters)
+    return {k: float(np.median(v)) for k, v in times.items()}
 
 
 def self_check_l2(got, exp, bs):

@@ -97,6 +97,22 @@ def test_what_the_plan_does_not_cover_is_refused_with_a_message():
     assert plan([20], 64, 7)[0] == -1 and b"board size" in lib.sayuri_hip_last_error()
 
 
+def test_every_plan_query_refuses_a_bad_geometry_under_its_own_name():
+    """The three plan queries build their geometry with one function (engine_plan.h, host_geom): no samples, a board larger than
+    max_board and a board of 1 are refused by each, and the message starts with the query's own prefix."""
+    lib, out = _lib.hip(), np.zeros(4, np.int32)
+    queries = {
+        b"split_ring_plan: ": lambda n, bsz: lib.sayuri_hip_split_ring_plan(n, _lib.ip(bsz), 19, 256, 0, 0),
+        b"pw_plan: ": lambda n, bsz: lib.sayuri_hip_pw_plan(n, _lib.ip(bsz), 19, 256, 128, 0, _lib.ip(out)),
+        b"dw_plan: ": lambda n, bsz: lib.sayuri_hip_dw_plan(n, _lib.ip(bsz), 19, 256, 7, 0, _lib.ip(out)),
+    }
+    for prefix, query in queries.items():
+        assert query(1, np.asarray([19], np.int32)) >= 0, prefix
+        for n, bsz, why in ((0, [19], b"bad argument"), (2, [19, 20], b"bad board size"), (2, [1, 19], b"bad board size")):
+            assert query(n, np.asarray(bsz, np.int32)) == -1, (prefix, n, bsz)
+            assert lib.sayuri_hip_last_error() == prefix + why, (prefix, n, bsz, lib.sayuri_hip_last_error())
+
+
 @pytest.mark.skipif(not (os.path.exists(OBJDUMP) and os.path.exists(READELF)), reason="needs the ROCm llvm tools")
 def test_depthwise_kernels_code_object(tmp_path):
     so = _build.HIP_SO

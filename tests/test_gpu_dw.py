@@ -10,19 +10,18 @@ and, independently of the old kernel, against the float64 direct convolution (te
 reference of _kref.py (equality).  The tap returns the channels below C; what the kernel stores in the pad channels [C, cs) of its
 NaN-pre-set buffer is read back bit for bit (hipraw.conv_dw_pad_bits) next to what depthwise_kernel stores there on the same operands.
 """
-import ctypes
+import functools
 import os
 
 import numpy as np
 import pytest
 
 import _cases
-import _pipes
 import _taps
 from _golden import Golden
 from _kref import assert_exact, conv_ref, exact_layer
 from _oracle import PortNet
-from _pipes import MAXB, Pinned, Pool, check, fp16_tol
+from _pipes import MAXB, Pinned, Pool, check, device_ms, fp16_tol, grid_of, make_pipe_under, within_oracle
 from _taps import KIND_DEPTHWISE
 from sayuri_amd import _lib, hipraw
 from sayuri_amd import weights as W
@@ -36,23 +35,7 @@ OUTS = ("prob", "pass", "misc", "own")
 KIND_DW_LDS = 7  # what the last-conv-kind reader says after the conv_dw tap
 
 
-def make_pipe(path, env=None, latency=False, batch=64, fp16=True):
-    """_pipes.make_pipe with this feature's two switches set exactly as `env` says, and put back afterwards"""
-    keep = {k: os.environ.pop(k, None) for k in DW_SWITCHES}
-    try:
-        return _pipes.make_pipe(path, env, latency=latency, batch=batch, fp16=fp16)
-    finally:
-        for k, v in keep.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def grid_of(planes, bsz):
-    gr = np.zeros((len(bsz), 43, B * B), np.float32)
-    for i, (p, bs) in enumerate(zip(planes, bsz)):
-        gr[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-    return gr
+make_pipe = functools.partial(make_pipe_under, DW_SWITCHES, batch=64)  # this feature's two switches exactly as `env` says
 
 
 def conv_dw(bsz, C, k, act, xs, w, bias, res=None, strips=0, max_board=_taps.MAX_BOARD, fp16=True):
@@ -212,17 +195,6 @@ def net_path(name, workdir):
     return path
 
 
-def _within_oracle(exp, outs, i, bs, what):
-    """sample i of a forward's raw outputs against the CPU oracle's (prob, pass, misc, own) of its position"""
-    e_prob, e_pass, e_misc, e_own = exp
-    tol = fp16_tol(np.concatenate([e_prob.ravel(), e_own.ravel(), e_misc.ravel()]))
-    crop = lambda a: a.reshape(B, B)[:bs, :bs].ravel()
-    for k in range(e_prob.shape[0]):
-        assert np.abs(crop(outs[0][i, k]) - e_prob[k]).max() <= tol, (what, i, bs, "prob", k)
-    assert np.abs(outs[1][i] - e_pass).max() <= tol and np.abs(outs[2][i] - e_misc).max() <= tol, (what, i, bs)
-    assert np.abs(crop(outs[3][i]) - e_own).max() <= tol, (what, i, bs, "own")
-
-
 @pytest.mark.parametrize("name", ["mixer64", "mixer256", "res64-replk"])
 def test_network_has_the_bits_of_the_old_kernel_in_both_kinds_of_context(name, tmp_weights_dir):
     """SAYURI_DW=0, the default and SAYURI_DW=1 with three forced strips give identical outputs; the first launched no conv_dw, the
@@ -248,8 +220,8 @@ def test_network_has_the_bits_of_the_old_kernel_in_both_kinds_of_context(name, t
                     assert np.array_equal(x, y), (name, latency, sizes, what, "rule", float(np.abs(x - y).max()))
                     assert np.array_equal(x, z), (name, latency, sizes, what, "forced", float(np.abs(x - z).max()))
                 for i, e in exp.items():
-                    _within_oracle(e, a, i, sizes[i], (name, latency, sizes, "SAYURI_DW=0"))
-                    _within_oracle(e, c, i, sizes[i], (name, latency, sizes, "SAYURI_DW=1"))
+                    within_oracle(e, a, i, sizes[i], (name, latency, sizes, "SAYURI_DW=0"))
+                    within_oracle(e, c, i, sizes[i], (name, latency, sizes, "SAYURI_DW=1"))
         finally:
             off.Destroy()
             rule.Destroy()
@@ -367,23 +339,6 @@ def test_the_routing_rule_has_its_boundary_where_design_md_puts_it(tmp_weights_d
             p.Destroy()
 
 
-def _device_ms(pipes, gr, sizes, rounds=3, iters=100):
-    """device ms per forward (sayuri_hip_time_runs), inputs resident, the contexts interleaved: medians of `rounds` x `iters`"""
-    lib = _lib.hip()
-    bs = np.asarray(sizes, np.int32)
-    times = {k: [] for k in pipes}
-    for p in pipes.values():
-        assert lib.sayuri_hip_upload(p.ctx(0), len(sizes), _lib.fp(gr), bs.ctypes.data_as(_lib.c_int_p)) == 0
-        ms = ctypes.c_float(0)
-        assert lib.sayuri_hip_time_runs(p.ctx(0), 30, ctypes.byref(ms)) == 0   # warm-up
-    for _ in range(rounds):
-        for k, p in pipes.items():
-            ms = ctypes.c_float(0)
-            assert lib.sayuri_hip_time_runs(p.ctx(0), iters, ctypes.byref(ms)) == 0, lib.sayuri_hip_last_error()
-            times[k].append(ms.value / iters)
-    return {k: float(np.median(v)) for k, v in times.items()}
-
-
 @pytest.mark.parametrize("n", [256, 32])
 def test_depthwise_route_is_no_slower_than_the_old_kernel(n, tmp_weights_dir, capsys):
     """Ten mixer blocks at 256 channels (feed-forward 384, 7x7), n boards of 19x19, default context.  Three contexts in one process,
@@ -398,7 +353,7 @@ def test_depthwise_route_is_no_slower_than_the_old_kernel(n, tmp_weights_dir, ca
     pipes = {"off": make_pipe(path, {"SAYURI_DW": "0"}, batch=256), "off2": make_pipe(path, {"SAYURI_DW": "0"}, batch=256),
              "on": make_pipe(path, batch=256)}
     try:
-        t = _device_ms(pipes, gr, sizes)
+        t = device_ms(pipes, gr, sizes)
         launches = _lib.hip().sayuri_hip_last_dw_launches(pipes["on"].ctx(0))
         s = abs(t["off"] - t["off2"]) / t["off"]
         with capsys.disabled():

@@ -19,7 +19,7 @@ import _taps
 from _cases import LAYER_SHAPES
 from _golden import Golden
 from _kref import conv_ref
-from _pipes import MAXB, Pinned, Pool, check, fp16_tol, wrong_samples
+from _pipes import MAXB, Pinned, Pool, check, fp16_tol, grid_of, wrong_samples
 from _taps import KIND_BOARD, KIND_SPLIT
 from golden_specs import FIXTURES
 from sayuri_amd import _lib
@@ -31,13 +31,6 @@ pytestmark = pytest.mark.gpu
 B = 19
 SEPARATE = {"SAYURI_SE_FUSED": "0", "SAYURI_SE_SPLIT": "0", "SAYURI_TOWER": "0"}
 make_pipe = functools.partial(_pipes.make_pipe, batch=64)  # the batch of this module's pipes where a test names none
-
-
-def grid_of(planes, bsz):
-    gr = np.zeros((len(bsz), 43, B * B), np.float32)
-    for i, (p, bs) in enumerate(zip(planes, bsz)):
-        gr[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-    return gr
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. layer level

@@ -15,7 +15,7 @@ import pytest
 
 from _golden import Golden
 from _oracle import PortNet
-from _pipes import FP16_ATOL, check, fp16_tol, self_check_l2
+from _pipes import FP16_ATOL, check, fp16_tol, grid_of, self_check_l2
 from golden_specs import FIXTURES
 from sayuri_amd import weights as W
 from sayuri_amd.pipe import HipForwardPipe
@@ -307,12 +307,6 @@ def test_a_position_does_not_depend_on_its_batch_mates(name, tmp_weights_dir, ca
     B = 19
     probes = {bs: W.synthetic_planes(1, bs, seed=4200 + bs)[0] for bs in (9, 13, 19)}
     rng = np.random.default_rng(77)
-
-    def grid_of(planes, bsz):
-        gr = np.zeros((len(bsz), 43, B * B), np.float32)
-        for i, (p, bs) in enumerate(zip(planes, bsz)):
-            gr[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-        return gr
 
     def sample(out, i):
         return [np.array(t[i]) for t in out]

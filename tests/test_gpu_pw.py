@@ -9,18 +9,17 @@ feature:
 The tolerance checks (float64 direct convolution, the CPU oracle) reuse conv_ref of _kref.py, fp16_tol of _pipes.py and the bound of
 test_gpu_layers.py.
 """
-import ctypes
+import functools
 import os
 
 import numpy as np
 import pytest
 
-import _pipes
 import _taps
 from _golden import Golden
 from _kref import conv_ref
 from _oracle import PortNet
-from _pipes import MAXB, Pinned, Pool, fp16_tol
+from _pipes import MAXB, Pinned, Pool, device_ms, grid_of, make_pipe_under, within_oracle
 from _taps import KIND_GENERIC
 from sayuri_amd import _lib, hipraw
 from sayuri_amd import weights as W
@@ -33,23 +32,7 @@ PW_SWITCHES = ("SAYURI_PW", "SAYURI_PW_PIECES")
 OUTS = ("prob", "pass", "misc", "own")
 
 
-def make_pipe(path, env=None, latency=False, batch=64):
-    """_pipes.make_pipe with this feature's two switches set exactly as `env` says, and put back afterwards"""
-    keep = {k: os.environ.pop(k, None) for k in PW_SWITCHES}
-    try:
-        return _pipes.make_pipe(path, env, latency=latency, batch=batch)
-    finally:
-        for k, v in keep.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def grid_of(planes, bsz):
-    gr = np.zeros((len(bsz), 43, B * B), np.float32)
-    for i, (p, bs) in enumerate(zip(planes, bsz)):
-        gr[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-    return gr
+make_pipe = functools.partial(make_pipe_under, PW_SWITCHES, batch=64)  # this feature's two switches exactly as `env` says
 
 
 KIND_PW = 6  # what the last-conv-kind reader says after the pointwise tap
@@ -162,17 +145,6 @@ def net_path(name, workdir, nblocks=None):
     return path
 
 
-def _within_oracle(exp, outs, i, bs, what):
-    """sample i of a forward's raw outputs against the CPU oracle's (prob, pass, misc, own) of its position"""
-    e_prob, e_pass, e_misc, e_own = exp
-    tol = fp16_tol(np.concatenate([e_prob.ravel(), e_own.ravel(), e_misc.ravel()]))
-    crop = lambda a: a.reshape(B, B)[:bs, :bs].ravel()
-    for k in range(e_prob.shape[0]):
-        assert np.abs(crop(outs[0][i, k]) - e_prob[k]).max() <= tol, (what, i, bs, "prob", k)
-    assert np.abs(outs[1][i] - e_pass).max() <= tol and np.abs(outs[2][i] - e_misc).max() <= tol, (what, i, bs)
-    assert np.abs(crop(outs[3][i]) - e_own).max() <= tol, (what, i, bs, "own")
-
-
 @pytest.mark.parametrize("name", list(NETS))
 def test_network_has_the_bits_of_the_generic_kernel_in_both_kinds_of_context(name, tmp_weights_dir):
     """Two blocks (the second with SE) of every block kind with tower 1x1 layers, at the widths these networks have.  SAYURI_PW=0
@@ -196,7 +168,7 @@ def test_network_has_the_bits_of_the_generic_kernel_in_both_kinds_of_context(nam
                 for x, y, what in zip(a, b, OUTS):
                     assert np.array_equal(x, y), (name, latency, sizes, what, float(np.abs(x - y).max()))
                 for i, e in exp.items():
-                    _within_oracle(e, b, i, sizes[i], (name, latency, sizes))
+                    within_oracle(e, b, i, sizes[i], (name, latency, sizes))
         finally:
             off.Destroy()
             on.Destroy()
@@ -309,23 +281,6 @@ def test_the_routing_rule_has_its_boundary_where_design_md_puts_it(tmp_weights_d
         everywhere.Destroy()
 
 
-def _device_ms(pipes, gr, sizes, rounds=3, iters=100):
-    """device ms per forward (sayuri_hip_time_runs), inputs resident, the contexts interleaved: medians of `rounds` x `iters`"""
-    lib = _lib.hip()
-    bs = np.asarray(sizes, np.int32)
-    times = {k: [] for k in pipes}
-    for p in pipes.values():
-        assert lib.sayuri_hip_upload(p.ctx(0), len(sizes), _lib.fp(gr), bs.ctypes.data_as(_lib.c_int_p)) == 0
-        ms = ctypes.c_float(0)
-        assert lib.sayuri_hip_time_runs(p.ctx(0), 30, ctypes.byref(ms)) == 0   # warm-up
-    for _ in range(rounds):
-        for k, p in pipes.items():
-            ms = ctypes.c_float(0)
-            assert lib.sayuri_hip_time_runs(p.ctx(0), iters, ctypes.byref(ms)) == 0, lib.sayuri_hip_last_error()
-            times[k].append(ms.value / iters)
-    return {k: float(np.median(v)) for k, v in times.items()}
-
-
 SPEED_CASES = [("latency-1x19", True, [19]), ("default-64x19", False, [19] * 64)]
 
 
@@ -341,7 +296,7 @@ def test_pointwise_route_is_no_slower_than_the_generic_kernel(label, latency, si
     pipes = {"off": make_pipe(path, {"SAYURI_PW": "0"}, latency=latency), "off2": make_pipe(path, {"SAYURI_PW": "0"}, latency=latency),
              "on": make_pipe(path, latency=latency)}
     try:
-        t = _device_ms(pipes, gr, sizes)
+        t = device_ms(pipes, gr, sizes)
         launches = _lib.hip().sayuri_hip_last_pw_launches(pipes["on"].ctx(0))
         s = abs(t["off"] - t["off2"]) / t["off"]
         with capsys.disabled():

@@ -22,7 +22,7 @@ import _taps
 from _cases import SE_LAYERS, SE_SEED, SE_UNIT_BATCHES, se_inputs, se_unit_x
 from _golden import Golden
 from _kref import se_apply_f64, se_gate_f64, se_pool_f64, se_unit_f64
-from _pipes import check, fp16_tol
+from _pipes import check, fp16_tol, grid_of
 from sayuri_amd import _lib
 from sayuri_amd import weights as W
 from sayuri_amd.pipe import Weights, hip_forward_raw
@@ -45,13 +45,6 @@ def make_pipe(monkeypatch, path, se_one=None, env=None, **kw):
         return _pipes.make_pipe(path, env, **{"batch": 64, **kw})
     finally:
         monkeypatch.delenv("SAYURI_SE_ONE", raising=False)
-
-
-def grid_of(planes, bsz):
-    gr = np.zeros((len(bsz), 43, B * B), np.float32)
-    for i, (p, bs) in enumerate(zip(planes, bsz)):
-        gr[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-    return gr
 
 
 def forward(pipe, sizes, seed):

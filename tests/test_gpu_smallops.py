@@ -144,6 +144,27 @@ def test_conv_with_se_unit_inside(act, via_tower):
                          via_tower).rc == 1
 
 
+@pytest.mark.parametrize("via_tower", [0, 1], ids=["per-layer kernel", "tower kernel"])
+def test_conv_se_tap_says_that_an_se_width_of_zero_does_not_apply(via_tower):
+    """se_size = 0 has no form of the SE stage (se_l2_form_ok's guard stands in front of the divisions by se / 4): the tap
+    returns 1 in front of any upload of the layer or launch, reports form 0, and a normal call afterwards (se = 32) gives
+    the bits of the same call before it."""
+    rng = np.random.default_rng(77)
+    C, se, bsz = 128, 32, [19]
+    xs = [rng.standard_normal((C, 361)).astype(np.float32)]
+    w = (rng.standard_normal((C, C, 3, 3)) / np.sqrt(9 * C)).astype(np.float32)
+    bias = (rng.standard_normal(C) * 0.1).astype(np.float32)
+    fc = ((rng.standard_normal((se, 3 * C)) / np.sqrt(3 * C)).astype(np.float32), (rng.standard_normal(se) * 0.1).astype(np.float32),
+          (rng.standard_normal((2 * C, se)) / np.sqrt(se)).astype(np.float32), (rng.standard_normal(2 * C) * 0.1).astype(np.float32))
+    before = _taps.ok(_taps.conv_se(bsz, C, se, 5, xs, w, bias, None, fc, via_tower), via_tower)
+    assert before.form != 0
+    one = np.zeros(1, np.float32)
+    t = _taps.conv_se(bsz, C, 0, 5, xs, w, bias, None, (one,) * 4, via_tower)
+    assert t.rc == 1 and t.form == 0, (t.rc, t.form)
+    after = _taps.ok(_taps.conv_se(bsz, C, se, 5, xs, w, bias, None, fc, via_tower), via_tower)
+    assert after.form == before.form and np.array_equal(after.outs[0].view(np.uint32), before.outs[0].view(np.uint32))
+
+
 @pytest.mark.parametrize("act", range(8))
 def test_head_board_kernel(act):
     """head_board_kernel at kernel level: the two 1x1 head convolutions in float64 (on the fp16-rounded trunk), rounded to

@@ -25,36 +25,21 @@ Prints ONE JSON object.
     python tools/latency_bench.py --ring --ring-depths 8 > profiles/r11_latency_ring.json
 """
 import argparse
-import ctypes
 import json
 import os
-import socket
-import subprocess
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from sayuri_amd import _lib, hipraw  # noqa: E402
-from sayuri_amd import weights as W  # noqa: E402
-from sayuri_amd.engine import pack_planes  # noqa: E402
-from sayuri_amd.pipe import HipForwardPipe  # noqa: E402
+import _ab
+from _ab import B, W, _lib, device_ms
+from sayuri_amd import hipraw
+from sayuri_amd.engine import pack_planes
 
-B = 19
 WORDS = 37 * 12 + 8
 NETS = {"20b256": (W.spec_20b256, 22), "40b384": (W.spec_40b384, 23)}
 POINTS = [(n, 19) for n in (1, 2, 4, 8, 16, 32, 64)] + [(1, 9), (1, 13)]
 SMALL_POINTS = [(16, 9)]  # --se-one, --ring: also a batch of small boards
-
-
-def weights_path(net):
-    spec, seed = NETS[net]
-    path = f"/tmp/sayuri_bench_{net}_seed{seed}_{os.getuid()}.bin"
-    if not os.path.exists(path):
-        W.write_weights(path, spec(), seed=seed)
-    return path
 
 
 def round_trips(ctx, stage, n, iters):
@@ -63,13 +48,6 @@ def round_trips(ctx, stage, n, iters):
     for _ in range(iters):
         hipraw.wait(ctx, hipraw.submit_packed(ctx, stage, n, 37))
     return (time.perf_counter() - t0) * 1e3 / iters
-
-
-def device_ms(lib, ctx, iters):
-    ms = ctypes.c_float(0)
-    if lib.sayuri_hip_time_runs(ctx, iters, ctypes.byref(ms)):
-        raise RuntimeError(lib.sayuri_hip_last_error().decode())
-    return ms.value / iters
 
 
 def kernel_classes(lib, ctx):
@@ -84,9 +62,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["both", "default"], default="both")
     ap.add_argument("--nets", default="20b256,40b384")
-    ap.add_argument("--iters", type=int, default=200, help="timed forwards per round and context")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=30)
+    _ab.timing_args(ap)
     ap.add_argument("--split", default="", help="also time latency contexts with these forced strips per board at n = 1 (e.g. 4,7,10)")
     ap.add_argument("--se-one", action="store_true", help="two latency contexts: one launch per SE unit against SAYURI_SE_ONE=0")
     ap.add_argument("--ring", action="store_true", help="latency contexts: the ring rule against SAYURI_LATENCY_RING=3, and =3 against =3")
@@ -95,12 +71,7 @@ def main():
     if args.ring and args.se_one:
         ap.error("--ring and --se-one are two measurements")
     lib = _lib.hip()
-    try:
-        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
-    except OSError:
-        commit = ""
-    out = {"tool": "tools/latency_bench.py", "box": socket.gethostname(), "commit": commit or "unknown", "mode": args.mode,
-           "iters": args.iters, "rounds": args.rounds, "warmup": args.warmup, "statistic": "median of rounds", "nets": {}}
+    out = _ab.header("tools/latency_bench.py", args, mode=args.mode)
     kinds = [] if args.se_one or args.ring else ["default"] + (["latency"] if args.mode == "both" else [])
     if args.ring:
         out["ring"] = True
@@ -109,39 +80,24 @@ def main():
         out["se_one"] = True
         os.environ.pop("SAYURI_SE_ONE", None)  # the two arms say which form they run
     for net in args.nets.split(","):
-        path = weights_path(net)
+        path = _ab.weights_path(NETS, net)
         channels = int(net.split("b")[1])
-        pipes = {k: HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, **({"latency": True} if k == "latency" else {})) for k in kinds}
+        make = lambda env=None, latency=True: _ab.pipe_under(tuple(env or ()), path, env or {}, latency, 64)  # noqa: E731
+        pipes = {k: make(latency=k == "latency") for k in kinds}
         if args.se_one:
-            pipes["latency"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
-            os.environ["SAYURI_SE_ONE"] = "0"
-            try:
-                pipes["latency_se_three"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
-            finally:
-                del os.environ["SAYURI_SE_ONE"]
+            pipes["latency"] = make()
+            pipes["latency_se_three"] = make({"SAYURI_SE_ONE": "0"})
         if args.ring:
-            pipes["latency"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
+            pipes["latency"] = make()
             for k, depth in [("latency_ring3", 3), ("latency_ring3_again", 3)] + [(f"latency_forced_ring{d}", int(d)) for d in args.ring_depths.split(",") if d]:
-                os.environ["SAYURI_LATENCY_RING"] = str(depth)
-                try:
-                    pipes[k] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
-                finally:
-                    del os.environ["SAYURI_LATENCY_RING"]
+                pipes[k] = make({"SAYURI_LATENCY_RING": str(depth)})
         for s in (int(x) for x in args.split.split(",") if x and args.mode == "both" and not args.se_one and not args.ring):
-            os.environ["SAYURI_LATENCY_SPLIT"] = str(s)
-            try:
-                pipes[f"latency_split{s}"] = HipForwardPipe(path, board_size=B, batch_size=64, fp16=True, latency=True)
-            finally:
-                del os.environ["SAYURI_LATENCY_SPLIT"]
+            pipes[f"latency_split{s}"] = make({"SAYURI_LATENCY_SPLIT": str(s)})
         stage = hipraw.PinnedSet(64, B, WORDS)
         res = {"points": [], "tower_state": {k: lib.sayuri_hip_tower_state(p.ctx(0)) for k, p in pipes.items()}}
         try:
             for n, bs in POINTS + (SMALL_POINTS if args.se_one or args.ring else []):
-                planes = W.synthetic_planes(n, [bs] * n, seed=100 + n)
-                grid = np.zeros((n, 43, B * B), np.float32)
-                for i, p in enumerate(planes):
-                    grid[i].reshape(43, B, B)[:, :bs, :bs] = p.reshape(43, bs, bs)
-                bsz = np.full(n, bs, np.int32)
+                planes, grid, bsz = _ab.boards(n, bs)
                 stage.records[:n * WORDS] = np.stack([pack_planes(p, 37) for p in planes]).astype(np.uint32).ravel()
                 stage.bsz[:n] = bsz
                 use = {k: p for k, p in pipes.items() if n == 1 or "split" not in k}
@@ -154,8 +110,7 @@ def main():
                 for r in range(-1, args.rounds):  # round -1: the warm-up
                     for k, p in use.items():
                         ctx = p.ctx(0)
-                        if lib.sayuri_hip_upload(ctx, n, _lib.fp(grid), _lib.ip(bsz)):
-                            raise RuntimeError(lib.sayuri_hip_last_error().decode())
+                        _ab.check(lib, lib.sayuri_hip_upload(ctx, n, _lib.fp(grid), _lib.ip(bsz)))
                         it = args.warmup if r < 0 else args.iters
                         d, w = device_ms(lib, ctx, it), round_trips(ctx, stage, n, it)
                         if r >= 0:
