@@ -65,6 +65,14 @@ int sayuri_pipe_eval(void* pipe, int mode, int gpu, int n, const float* planes, 
 int sayuri_pipe_accepts_group(void* pipe);
 int sayuri_pipe_group_eval(void* pipe, int n, const float* planes, const int* board_sizes, const float* komi,
                            const int* offsets, float* out);
+/* live weight reload (HipForwardPipe::Reload): a network of the SAME architecture into the running pipe.  sayuri_pipe_reload
+ * parses the file (LoadWeightsFile) and stages, builds and commits it on the calling thread while other threads' requests are
+ * served; when it returns, a request that begins gets the new network.  -1 with the loader's or the device's message when the
+ * file or the architecture is refused: the pipe then serves the network it had.  sayuri_pipe_accepts_reload: the device library
+ * in use has the sayuri_hip_reload_* entry points; sayuri_pipe_weights_generation: 0 before the first reload, +1 each. */
+int sayuri_pipe_accepts_reload(void* pipe);
+int sayuri_pipe_reload(void* pipe, const char* weights_path);
+int sayuri_pipe_weights_generation(void* pipe);
 int sayuri_pipe_netbench(void* pipe, int threads, double seconds, int board, double* evals_per_sec, long* total);
 void sayuri_pipe_pump_times(void* pipe, double* out8, long* batches, long* evals);
 
@@ -108,6 +116,10 @@ void sayuri_engine_net_set_device_ensemble(void* net, int on);
 /* NetworkOptions::group_forward (option "group_forward", default 1): the evaluations of one round of a search with
  * playouts_in_flight > 1 as one group request of a pipe that accepts them, or one by one; same results bit for bit */
 void sayuri_engine_net_set_group_forward(void* net, int on);
+/* Network::SwapWeights: the network in `path` (same architecture) into the facade's running pipe, then a new cache epoch: from the
+ * return on the cache never serves a result of the old weights, and a request that began before the swap does not store its
+ * result.  -1 with the loader's or the pipe's message (a dummy backend, a pipe without reload, another architecture): unchanged. */
+int sayuri_engine_net_reload(void* net, const char* path);
 void sayuri_engine_net_output(void* net, void* game, int ensemble, int symmetry, float temperature, int use_cache,
                               uint64_t seed, float* out /* [2N+9] */);
 /* NULL (message in sayuri_engine_last_error) when an option is refused, e.g. playouts_in_flight outside 1..64 */
@@ -142,7 +154,7 @@ int sayuri_selfplay_run(void* raw_pipe, int weights_version, const char* options
  * (reference SaveChunk + gzip, pipe.cc:116-159,181-233): [12] = chunks on disk when the window ended ([8] counts the
  * flush of the writer's pool behind it too), [13] = CPU nanoseconds of the writer thread, [14] = the same when the
  * window ended, [15] = bytes written to disk, [16] = bytes of record text before gzip, [17] = wall nanoseconds of the
- * final flush, [18..19] = 0.  The driver all-gathers the records inside the hook (sayuri_amd/shard.py). */
+ * final flush, [18] = networks swapped in live (option live_weights=1), [19] = 0.  The driver all-gathers the records inside the hook (sayuri_amd/shard.py). */
 typedef int (*sayuri_selfplay_stats_fn)(const uint64_t* stats10, double elapsed, int local_halt, void* user);
 int sayuri_selfplay_run_ex(void* raw_pipe, int weights_version, const char* options, const char* name_suffix, double seconds,
                            int move_cap, sayuri_selfplay_stats_fn on_stats, void* user, double interval_seconds,

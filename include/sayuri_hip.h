@@ -113,6 +113,38 @@ sayuri_hip_ctx* sayuri_hip_create_ex(int device, const sayuri_hip_netdesc* desc,
  * biases [K].  `n` must equal the element count implied by the netdesc. */
 int sayuri_hip_load_tensor(sayuri_hip_ctx* ctx, int layer_id, int kind, const float* host, size_t n);
 
+/* LIVE WEIGHT RELOAD: a new network of the SAME architecture into a context that keeps serving forwards (the reference
+ * rebuilds its graph: CudaForwardPipe::Construct with weights, cuda_forward_pipe.cc:44-119).  Everything a forward reads that
+ * is derived from the weights is one WEIGHT SET with device buffers of its own; a reload builds a second set beside the live
+ * one and swaps them between two forwards.  No forward sees a mixture; a context that is never reloaded does what it always did.
+ *   sayuri_hip_reload_begin    opens a reload.  -1 with a message that names the difference, the context unchanged, when
+ *                              `desc` differs from the context's in anything that shapes buffers or kernels (block count,
+ *                              types and widths, SE placement and widths, head type and widths, input / output channels,
+ *                              activation, version as far as it selects the encoder); when a reload is already open; while
+ *                              the context is inside sayuri_hip_time_runs / sayuri_hip_profile_run.
+ *   sayuri_hip_load_tensor     while a reload is open: fills the STAGED set, same layer ids and kinds.  (Outside a reload it
+ *                              stays refused after the first forward.)
+ *   sayuri_hip_reload_prepare  the heavy step: checks that every tensor is there, builds all images, uploads them into NEW
+ *                              device buffers (the live set is never written in place).  On failure -1, the staged set is
+ *                              freed, the reload is closed and the context is unchanged.
+ *   sayuri_hip_reload_commit   the light step, a pointer flip: forwards enqueued after it returns use the new set, forwards
+ *                              enqueued before it finish on the old one.  Returns the new generation (>= 1); -1 without a
+ *                              prepared reload.  The old set's memory is given back once every forward enqueued before the
+ *                              commit has finished ON THE DEVICE (events behind them on the tickets' streams; nobody needs to
+ *                              have waited for those tickets): submit, wait and device_bytes look, and
+ *                              sayuri_hip_device_bytes is then what it was before the reload.
+ *   sayuri_hip_reload_abort    drops an open reload, prepared or not.
+ *   sayuri_hip_weights_generation   0 for a context that was never reloaded, +1 per commit.
+ * Threads: begin / load_tensor / prepare may run on one thread while another calls submit / wait / query on the same context:
+ * they touch the staged set only (prepare's uploads slow the forwards beside it, nothing more).  commit is serialised with
+ * submit by the context itself: any thread may call it.  The fp32 engine, latency contexts and contexts that run chains or
+ * ensemble batches take reloads the same way. */
+int sayuri_hip_reload_begin(sayuri_hip_ctx* ctx, const sayuri_hip_netdesc* desc);
+int sayuri_hip_reload_prepare(sayuri_hip_ctx* ctx);
+int sayuri_hip_reload_commit(sayuri_hip_ctx* ctx);
+int sayuri_hip_reload_abort(sayuri_hip_ctx* ctx);
+int sayuri_hip_weights_generation(const sayuri_hip_ctx* ctx);
+
 /* One batch through the net: replaces NNGraph::BatchForward (cuda_forward_pipe.cc:684-1018)
  * up to, not including, FillOutputs.
  *   planes      [n][input_channels][board*board]  each sample already re-padded top-left into

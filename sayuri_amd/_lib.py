@@ -48,6 +48,11 @@ HIP_ABI = {
     "sayuri_hip_create": (_V, [_I, _V, _I, _I, _I]),
     "sayuri_hip_create_ex": (_V, [_I, _V, _I, _I, _I, _U]),
     "sayuri_hip_load_tensor": (_I, [_V, _I, _I, _F, _Z]),
+    "sayuri_hip_reload_begin": (_I, [_V, _V]),
+    "sayuri_hip_reload_prepare": (_I, [_V]),
+    "sayuri_hip_reload_commit": (_I, [_V]),
+    "sayuri_hip_reload_abort": (_I, [_V]),
+    "sayuri_hip_weights_generation": (_I, [_V]),
     "sayuri_hip_forward": (_I, [_V, _I, _F, _IP] + _OUT),
     "sayuri_hip_upload": (_I, [_V, _I, _F, _IP]),
     "sayuri_hip_run": (_I, [_V]),
@@ -174,6 +179,9 @@ def host() -> ctypes.CDLL:
         lib.sayuri_pipe_reconstruct.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         lib.sayuri_pipe_eval.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p,
                                          c_int_p, c_float_p, c_int_p, c_float_p]
+        lib.sayuri_pipe_accepts_reload.argtypes = [ctypes.c_void_p]
+        lib.sayuri_pipe_reload.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        lib.sayuri_pipe_weights_generation.argtypes = [ctypes.c_void_p]
         lib.sayuri_pipe_accepts_group.argtypes = [ctypes.c_void_p]
         lib.sayuri_pipe_group_eval.argtypes = [ctypes.c_void_p, ctypes.c_int, c_float_p, c_int_p, c_float_p, c_int_p, c_float_p]
         lib.sayuri_pipe_pump_times.restype = None

@@ -10,6 +10,7 @@
 #include "engine_options.h"
 #include "search.h"
 #include "selfplay.h"
+#include "weights_model.h"
 
 using namespace sayuri_engine;
 using sayuri_go::kNoVertex;
@@ -141,6 +142,21 @@ void sayuri_engine_net_output(void* n, void* game, int ensemble, int symmetry, f
     s[8] = r.score_error;
 }
 
+// Network::SwapWeights with the network in `path`: -1 with the loader's or the pipe's message, the facade unchanged
+int sayuri_engine_net_reload(void* n, const char* path) {
+    try {
+        if (!n || !path) throw std::runtime_error("sayuri_engine_net_reload: null argument");
+        auto w = std::make_shared<sayuri_host::DNNWeights>();
+        std::string err;
+        if (!sayuri_host::LoadWeightsFile(path, w.get(), &err)) throw std::runtime_error(err);
+        static_cast<Network*>(n)->SwapWeights(std::move(w));
+        return 0;
+    } catch (const std::exception& e) {
+        g_engine_err = e.what();
+        return -1;
+    }
+}
+
 // NetworkOptions::group_forward after construction (the option "group_forward=0/1" sets it at construction)
 void sayuri_engine_net_set_group_forward(void* n, int on) { static_cast<Network*>(n)->SetGroupForward(on != 0); }
 
@@ -196,7 +212,7 @@ void PackStats(const SelfplayStats& st, std::uint64_t* v) {  // the 20 slots of 
                                          st.cache_lookups, st.cache_hits, st.records, st.chunks_saved, 0,
                                          st.finished_moves, st.prerolled_moves,
                                          st.chunks_saved_window, st.writer_cpu_ns, st.writer_cpu_ns_window, st.bytes_written,
-                                         st.text_bytes, st.flush_ns, 0, 0};
+                                         st.text_bytes, st.flush_ns, st.weight_swaps, 0};
     std::memcpy(v, a, sizeof(a));
 }
 struct StatsHook {

@@ -102,6 +102,10 @@ void EngineOptions::Parse(const std::string& text) {
         else if (k == "target_directory") selfplay.target_directory = v;
         else if (k == "weights_dir") selfplay.weights_dir = v;
         else if (k == "weights_file") selfplay.weights_file = v;
+        else if (k == "live_weights") {
+            if (v != "0" && v != "1") throw std::invalid_argument("live_weights must be 0 or 1, got " + v);
+            selfplay.live_weights = v == "1";
+        }
         OPT_INT("stagger_moves", selfplay.stagger_moves);
         OPT_INT("game_threads", selfplay.game_threads);
         OPT_INT("chunk_pool_games", selfplay.chunk_pool_games);

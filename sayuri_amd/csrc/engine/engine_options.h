@@ -28,6 +28,9 @@ struct SelfplayOptions {
     // weights roll-over (reference Engine::SelectWeights / ShouldHalt, engine.cc:63-90): the loop winds down once the
     // newest file in weights_dir is no longer weights_file
     std::string weights_dir, weights_file;
+    // extension: 1 = a newer file of the SAME architecture is loaded into the running pipe (NetworkForwardPipe::Reload) and the
+    // games go on; the loop winds down only when the pipe refuses the file.  0 = the reference's behaviour, to the byte.
+    bool live_weights{false};
     // extension (measurement only): the first game of worker g starts after g * stagger_moves / parallel_games
     // policy-sampled moves, so that a short window sees games in every phase, as a long-running self-play does
     int stagger_moves{0};

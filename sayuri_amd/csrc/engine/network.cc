@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <random>
+#include <stdexcept>
 
 #include "encoder.h"
 
@@ -47,12 +48,21 @@ void ResultCache::Clear() {
     for (auto& s : shards_) s.generation = 0;
 }
 
-void ResultCache::Insert(std::uint64_t key, const OutputResult& value) {
+void ResultCache::NewEpoch() {
+    for (auto& s : shards_) s.mu.lock();  // (always in this order, and nobody else holds two)
+    epoch_.fetch_add(1, std::memory_order_acq_rel);
+    for (auto& e : table_) e.generation = 0;
+    for (auto& s : shards_) s.generation = 0;
+    for (auto& s : shards_) s.mu.unlock();
+}
+
+void ResultCache::Insert(std::uint64_t key, const OutputResult& value, std::uint64_t epoch) {
     if (blocks_ == 0) return;
     const size_t block = key % blocks_;
     Entry* cluster = table_.data() + block * kClusterSize;
     Shard& sh = shards_[block % kShards];
     std::lock_guard<std::mutex> lock(sh.mu);
+    if (epoch != epoch_.load(std::memory_order_acquire)) return;  // computed by weights that have been replaced since
     size_t victim = 0;
     std::uint64_t oldest = cluster[0].generation;
     for (size_t i = 1; i < kClusterSize; ++i) {
@@ -92,6 +102,13 @@ void Network::Initialize(std::shared_ptr<NetworkForwardPipe> pipe, int weights_v
     if (!Valid()) opt_.no_cache = false; // network.cc:84-88: the cache has no effect on the dummy pipe
     SetCacheSize(opt_.cache_memory_mib);
     ResetNumQueries();
+}
+
+void Network::SwapWeights(std::shared_ptr<sayuri_host::DNNWeights> weights) {
+    if (!Valid()) throw std::runtime_error("SwapWeights: the network has no forward pipe (dummy backend)");
+    if (!pipe_->AcceptsReload()) throw std::runtime_error("SwapWeights: the forward pipe does not take a weight reload");
+    pipe_->Reload(std::move(weights));  // throws when refused: nothing has changed then
+    cache_.NewEpoch();
 }
 
 size_t Network::SetCacheSize(size_t mib) {
@@ -221,6 +238,7 @@ Network::Result Network::GetOutput(const GameState& state, Ensemble ensemble, Qu
     if (opt_.no_cache || ensemble == kAverage) query.read_cache = query.write_cache = false;
 
     Result result;
+    const std::uint64_t epoch = cache_.epoch();  // noted before the evaluation begins: see SwapWeights
     if (query.read_cache && ProbeCache(state, result)) {
         ActivatePolicy(result, query.temperature);
         return result;
@@ -229,7 +247,7 @@ Network::Result Network::GetOutput(const GameState& state, Ensemble ensemble, Qu
         result = GetAverage(state, query, rng);
     } else {
         result = GetOutputInternal(state, query.symmetry, query.offset, rng);
-        if (query.write_cache) cache_.Insert(state.GetHash(), result); // stored before the policy softmax
+        if (query.write_cache) cache_.Insert(state.GetHash(), result, epoch); // stored before the policy softmax
         ActivatePolicy(result, query.temperature);
     }
     return result;
@@ -246,6 +264,7 @@ bool Network::BeginOutput(const GameState& state, Ensemble ensemble, Query query
         query.symmetry = static_cast<int>(rng.Below(SymmetryTables::kCount));
     }
     if (opt_.no_cache) query.read_cache = query.write_cache = false;
+    rec->epoch = cache_.epoch();
     if (query.read_cache && ProbeCache(state, rec->result)) {
         ActivatePolicy(rec->result, query.temperature);
         return true;
@@ -290,7 +309,7 @@ void Network::FinishOutputs(PendingOutput* const* recs, int n, Rng& rng) {
         PendingOutput& r = *recs[i];
         if (Valid()) num_queries_.fetch_add(1, std::memory_order_relaxed);
         TransformResult(r.result, r.symmetry);
-        if (r.query.write_cache) cache_.Insert(r.hash, r.result); // stored before the policy softmax
+        if (r.query.write_cache) cache_.Insert(r.hash, r.result, r.epoch); // stored before the policy softmax
         ActivatePolicy(r.result, r.query.temperature);
         r.input.reset();
     }

@@ -56,9 +56,14 @@ public:
     static constexpr size_t kClusterSize = 8;
     static constexpr size_t kEntrySize = 24 + sizeof(OutputResult); // what the reference charges per entry
     void SetCapacity(size_t entries);
-    void Insert(std::uint64_t key, const OutputResult& value);
+    // `epoch`: the cache's epoch when the request that computed `value` began; a value of an earlier epoch is not stored
+    void Insert(std::uint64_t key, const OutputResult& value, std::uint64_t epoch);
     bool Lookup(std::uint64_t key, OutputResult& value);
     void Clear();
+    // The weights behind the cache have changed: forget every entry and start a new epoch, against concurrent Insert / Lookup
+    // (Clear is for a quiet cache).  Whatever was computed by a request that began before this call is never stored afterwards.
+    void NewEpoch();
+    std::uint64_t epoch() const { return epoch_.load(std::memory_order_acquire); }
     size_t Capacity() const { return table_.size(); }
     size_t hits() const { return hits_.load(std::memory_order_relaxed); }
     size_t lookups() const { return lookups_.load(std::memory_order_relaxed); }
@@ -78,6 +83,7 @@ private:
     size_t blocks_{0};
     Shard shards_[kShards];
     std::atomic<size_t> hits_{0}, lookups_{0};
+    std::atomic<std::uint64_t> epoch_{0};
 };
 
 struct NetworkOptions {
@@ -112,6 +118,7 @@ public:
         Query query;
         int symmetry{0};
         std::uint64_t hash{0};
+        std::uint64_t epoch{0};              // the cache's epoch when the request began (SwapWeights)
         sayuri_host::PackedPlanes planes;   // the compact route (the pipe takes packed planes) ...
         std::unique_ptr<InputData> input;   // ... or the 43 fp32 planes
     };
@@ -120,6 +127,12 @@ public:
     int GetVertexWithPolicy(const GameState& state, float temperature, bool allow_pass, Rng& rng); // :431-468
     size_t SetCacheSize(size_t mib); // network.cc:102-122
     void ClearCache() { cache_.Clear(); }
+    // A new network of the same architecture into the running pipe (NetworkForwardPipe::Reload), then a new cache epoch: from
+    // the moment this returns the cache never serves a result computed by the old weights -- a request that began before it and
+    // finishes after it returns its result to its caller and does not store it.  Throws when the pipe refuses (a dummy backend,
+    // a pipe without reload, another architecture): the facade then serves the old network as before.
+    void SwapWeights(std::shared_ptr<sayuri_host::DNNWeights> weights);
+    std::uint64_t weights_epoch() const { return cache_.epoch(); }
     void ResetNumQueries(size_t q = 0) { num_queries_.store(q, std::memory_order_relaxed); }
     size_t GetNumQueries() const { return num_queries_.load(std::memory_order_relaxed); }
     PolicyBufferOffset GetDefaultPolicyOffset() const { return opt_.default_policy_offset; }

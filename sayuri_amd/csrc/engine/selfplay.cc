@@ -1,6 +1,7 @@
 #include "selfplay.h"
 
 #include "fiber.h"
+#include "weights_model.h"
 
 #include <dirent.h>
 #include <sys/stat.h>
@@ -236,9 +237,19 @@ void SelfplayEngine::PlayPolicyMoves(int g, int count) {
     }
 }
 
+std::string SelfplayEngine::weights_file() const {
+    std::lock_guard<std::mutex> lock(weights_mu_);
+    return opt_.selfplay.weights_file;
+}
+void SelfplayEngine::SetWeightsFile(const std::string& path) {
+    std::lock_guard<std::mutex> lock(weights_mu_);
+    opt_.selfplay.weights_file = path;
+}
+
 std::string SelfplayEngine::SelectWeights() const {
-    if (!opt_.selfplay.weights_file.empty() && opt_.selfplay.weights_dir.empty()) return opt_.selfplay.weights_file;
-    std::string best = opt_.selfplay.weights_file;
+    const std::string current = weights_file();
+    if (!current.empty() && opt_.selfplay.weights_dir.empty()) return current;
+    std::string best = current;
     if (opt_.selfplay.weights_dir.empty()) return best;
     DIR* d = opendir(opt_.selfplay.weights_dir.c_str());
     if (!d) return best;
@@ -260,12 +271,12 @@ std::string SelfplayEngine::SelectWeights() const {
 
 bool SelfplayEngine::ShouldHalt() const {
     if (opt_.selfplay.weights_dir.empty()) return false;
-    const std::string newest = SelectWeights();
-    if (newest == opt_.selfplay.weights_file) return false;
+    const std::string newest = SelectWeights(), current = weights_file();
+    if (newest == current) return false;
     // two spellings of one file (trailing slash in weights_dir, relative vs absolute path, a symlink) are not a newer
     // network: compare the files, not the strings
     struct stat a, b;
-    if (stat(newest.c_str(), &a) == 0 && stat(opt_.selfplay.weights_file.c_str(), &b) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino)
+    if (stat(newest.c_str(), &a) == 0 && stat(current.c_str(), &b) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino)
         return false;
     return true;
 }
@@ -358,7 +369,82 @@ SelfplayPipe::SelfplayPipe(std::shared_ptr<NetworkForwardPipe> pipe, int weights
         MakeDir(vdata_dir_);
         MakeDir(sgf_dir_);
         MakeDir(queries_dir_);
+        if (opt_.selfplay.live_weights) {
+            MakeDir(target + "/weights_log");
+            weights_log_ = target + "/weights_log/" + hash_ + ".txt";
+            LogWeights(opt_.selfplay.weights_file);
+        }
     }
+}
+
+SelfplayPipe::FileMark SelfplayPipe::MarkOf(const std::string& path) {
+    FileMark m;
+    m.path = path;
+    struct stat st {};
+    if (stat(path.c_str(), &st) == 0) {
+        m.size = static_cast<long long>(st.st_size);
+        m.mtime_s = static_cast<long long>(st.st_mtim.tv_sec);
+        m.mtime_ns = static_cast<long long>(st.st_mtim.tv_nsec);
+    }
+    return m;
+}
+
+void SelfplayPipe::LogWeights(const std::string& path) {
+    if (weights_log_.empty()) return;
+    std::lock_guard<std::mutex> lock(swap_mu_);
+    std::ofstream f(weights_log_, std::ios_base::app);
+    if (!f.is_open()) return;
+    const size_t slash = path.find_last_of('/');
+    f << played_games_.load() << ' ' << static_cast<long long>(std::time(nullptr)) << ' '
+      << (slash == std::string::npos ? path : path.substr(slash + 1)) << std::endl;
+}
+
+bool SelfplayPipe::HandleNewerWeights() {
+    if (!opt_.selfplay.live_weights || swap_refused_.load()) return false;
+    if (swap_running_.load(std::memory_order_acquire)) return true;  // the games go on while the swap thread works
+    Network& net = engine_.network();
+    if (!net.Valid() || !net.pipe()->AcceptsReload()) {
+        // a dummy backend, or a pipe / device library without reload: the reference's way, and the restarted process picks the file up
+        swap_refused_.store(true);
+        std::fprintf(stderr, "[selfplay] live_weights: the forward pipe does not take a weight reload: winding down for a restart\n");
+        return false;
+    }
+    const std::string newest = engine_.SelectWeights();
+    {
+        std::lock_guard<std::mutex> lock(swap_mu_);
+        if (MarkOf(newest) == bad_file_) return true;  // did not parse, said so once, unchanged since: not a reason to wind down
+    }
+    if (!engine_.ShouldHalt()) return true;  // (a swap finished between the caller's look and this one)
+    if (swap_thread_.joinable()) swap_thread_.join();  // the previous swap's thread has finished (swap_running_ is false)
+    swap_running_.store(true, std::memory_order_release);
+    swap_thread_ = std::thread([this, newest] { SwapThread(newest); });
+    return true;
+}
+
+void SelfplayPipe::SwapThread(std::string path) {
+    pthread_setname_np(pthread_self(), "sayuri-weights");
+    const FileMark mark = MarkOf(path);  // as it is BEFORE the parse: a writer that appends meanwhile changes it
+    auto weights = std::make_shared<sayuri_host::DNNWeights>();
+    std::string err;
+    if (!sayuri_host::LoadWeightsFile(path, weights.get(), &err)) {
+        // e.g. a file still being written: reported once, looked at again when its size or mtime have changed
+        std::fprintf(stderr, "[selfplay] live_weights: %s does not parse (%s): skipped until it changes\n", path.c_str(), err.c_str());
+        std::lock_guard<std::mutex> lock(swap_mu_);
+        bad_file_ = mark;
+    } else {
+        try {
+            engine_.network().SwapWeights(std::move(weights));
+            engine_.SetWeightsFile(path);  // ShouldHalt() is false again
+            weight_swaps_.fetch_add(1);
+            LogWeights(path);
+        } catch (const std::exception& e) {
+            // parsed, but the pipe refuses it (another architecture): worker 0's next look finds swap_refused_ and takes the
+            // reference's wind-down, exactly as without the option; the restart takes the new network
+            std::fprintf(stderr, "[selfplay] live_weights: %s is refused (%s): winding down for a restart\n", path.c_str(), e.what());
+            swap_refused_.store(true);
+        }
+    }
+    swap_running_.store(false, std::memory_order_release);
 }
 
 bool SelfplayPipe::WriteGzip(const std::string& name, const std::string& text) {
@@ -601,7 +687,7 @@ SelfplayStats SelfplayPipe::Run(double seconds) {
             bool first_game = true, halting = false;
             while (!stop_.load(std::memory_order_relaxed) && accumulation_games_.fetch_add(1) < max_games_.load(std::memory_order_relaxed)) {
                 if (g == 0 && !halting) {  // pipe.cc:246-258: only the main worker looks, once per game
-                    if (halt_wish_.load(std::memory_order_relaxed) || engine_.ShouldHalt()) {
+                    if (halt_wish_.load(std::memory_order_relaxed) || (engine_.ShouldHalt() && !HandleNewerWeights())) {
                         halt_wish_.store(true, std::memory_order_relaxed);
                         if (!stats_cb_) WindDown();  // alone: act at once; with an exchange hook the verdict comes from there
                         halting = !stats_cb_;
@@ -684,6 +770,7 @@ SelfplayStats SelfplayPipe::Run(double seconds) {
         st.prerolled_moves = prerolled_moves_.load();
         st.chunks_saved_window = chunks_.load();
         st.writer_cpu_ns_window = writer_cpu_ns_.load();
+        st.weight_swaps = weight_swaps_.load();
         st.elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     };
     SelfplayStats st;
@@ -714,6 +801,7 @@ SelfplayStats SelfplayPipe::Run(double seconds) {
         if (seconds > 0 || stop_.load()) stop_.store(true);
     }
     for (auto& w : workers) w.join();
+    if (swap_thread_.joinable()) swap_thread_.join();
     if (std::getenv("SAYURI_MEMSTAT")) {  // where the resident set of a long run is (stderr, once, after the workers have ended)
         std::size_t slabs = 0, live = 0, biggest = 0;
         for (int g = 0; g < games; ++g) {

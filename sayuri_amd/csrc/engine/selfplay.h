@@ -34,6 +34,7 @@ struct SelfplayStats {
     std::uint64_t text_bytes{0};       // the records' text before gzip
     std::uint64_t flush_ns{0};         // wall time from the workers' end until the writer has emptied its pool
     double elapsed{0};
+    std::uint64_t weight_swaps{0};     // networks swapped into the running pipe (option live_weights=1)
 };
 
 class SelfplayEngine { // engine.h:12-69
@@ -43,6 +44,9 @@ public:
     void PlayPolicyMoves(int g, int count);                        // extension: `count` policy-sampled moves, no search, no records
     std::string SelectWeights() const;                             // engine.cc:63-86
     bool ShouldHalt() const;                                       // engine.cc:88-90
+    // live_weights: the file the engine runs on, which a swap replaces while worker 0 looks at it (ShouldHalt)
+    std::string weights_file() const;
+    void SetWeightsFile(const std::string& path);
     bool Step(int g);                                              // one self-play move; false once the game is over
     void Selfplay(int g);                                          // engine.cc:234-241
     void GatherTrainingData(std::vector<TrainingData>& chunk, int g);
@@ -73,6 +77,7 @@ private:
     Slot& At(int g);
 
     EngineOptions opt_;
+    mutable std::mutex weights_mu_;  // opt_.selfplay.weights_file
     Network network_;
     std::vector<std::unique_ptr<Slot>> slots_;
     std::vector<BoardQuery> board_queries_;
@@ -87,6 +92,7 @@ class SelfplayPipe {
 public:
     SelfplayPipe(std::shared_ptr<NetworkForwardPipe> pipe, int weights_version, const EngineOptions& opt,
                  const std::string& name_suffix = "");
+    ~SelfplayPipe() { if (swap_thread_.joinable()) swap_thread_.join(); }
     // Plays until `num_games` games are complete, or (seconds > 0) until the clock runs out: games still in
     // progress are then abandoned and not written.
     SelfplayStats Run(double seconds = 0);
@@ -97,6 +103,7 @@ public:
     using StatsCallback = int (*)(const SelfplayStats* stats, int local_halt, void* user);
     void SetStatsCallback(StatsCallback cb, void* user, double interval) { stats_cb_ = cb; stats_user_ = user; stats_interval_ = interval; }
     int max_games() const { return max_games_.load(); }
+    std::uint64_t weight_swaps() const { return weight_swaps_.load(); }
     const std::string& filename_hash() const { return hash_; }
     SelfplayEngine& engine() { return engine_; }
 
@@ -124,6 +131,25 @@ private:
     std::atomic<int> max_games_{0};
     std::atomic<bool> halt_wish_{false};     // set by worker 0 (ShouldHalt) or by the stats callback's verdict
     void WindDown();                         // pipe.cc:248-254
+    // ---- option live_weights=1: a newer file goes into the running pipe instead of ending the run
+    // Worker 0 found a newer file (ShouldHalt).  true: it is taken care of without a halt -- a swap is under way on the swap
+    // thread, has just been started, or the file is one that did not parse and has not changed since; false: the pipe cannot
+    // take it (or the option is off): the reference's wind-down.
+    bool HandleNewerWeights();
+    void SwapThread(std::string path);       // parse (never on a game's fiber), Network::SwapWeights, weights_log
+    void LogWeights(const std::string& path);  // weights_log/<hash>.txt: games_finished unix_time file_name
+    struct FileMark {  // a file as last looked at: it is looked at again when size or mtime have changed
+        std::string path;
+        long long size{-1}, mtime_s{0}, mtime_ns{0};
+        bool operator==(const FileMark& o) const { return path == o.path && size == o.size && mtime_s == o.mtime_s && mtime_ns == o.mtime_ns; }
+    };
+    static FileMark MarkOf(const std::string& path);
+    std::thread swap_thread_;
+    std::atomic<bool> swap_running_{false}, swap_refused_{false};
+    std::mutex swap_mu_;                     // bad_file_, the weights log
+    FileMark bad_file_;                      // the last file that failed to parse (reported once)
+    std::atomic<std::uint64_t> weight_swaps_{0};
+    std::string weights_log_;                // path of this run's log; empty without a target directory or with live_weights=0
     StatsCallback stats_cb_{nullptr};
     void* stats_user_{nullptr};
     double stats_interval_{2.0};

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -104,6 +105,15 @@ int sayuri_hip_load_tensor(sayuri_hip_ctx* ctx, int layer_id, int kind, const fl
     if (!ctx || !host) return fail("load_tensor: null argument");
     return ctx->eng->load_tensor(layer_id, kind, host, n);
 }
+
+int sayuri_hip_reload_begin(sayuri_hip_ctx* ctx, const sayuri_hip_netdesc* desc) {
+    if (!ctx || !desc) return fail("reload_begin: null argument");
+    return ctx->eng->reload_begin(*desc);
+}
+int sayuri_hip_reload_prepare(sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->reload_prepare() : fail("reload_prepare: null ctx"); }
+int sayuri_hip_reload_commit(sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->reload_commit() : fail("reload_commit: null ctx"); }
+int sayuri_hip_reload_abort(sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->reload_abort() : fail("reload_abort: null ctx"); }
+int sayuri_hip_weights_generation(const sayuri_hip_ctx* ctx) { return ctx ? ctx->eng->weights_generation() : -1; }
 
 int sayuri_hip_upload(sayuri_hip_ctx* ctx, int n, const float* planes, const int* board_sizes) {
     if (!ctx || !planes) return fail("upload: null argument");

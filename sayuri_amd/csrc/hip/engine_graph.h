@@ -45,6 +45,12 @@ public:
     virtual int tower_state() const = 0;  // 1: the persistent tower kernel is loaded, 0: one launch per layer (fallback)
     virtual int latency_state() const = 0;  // 1: a latency context (conv_split.h), 0: the default engine
     virtual int debug_read(int buf, void* host, size_t bytes) = 0;  // debugging tap: activation buffer `buf` of ticket 0
+    // live weight reload (sayuri_hip_reload_*): a second weight set is staged beside the live one and swapped in between two forwards
+    virtual int reload_begin(const sayuri_hip_netdesc& d) = 0;
+    virtual int reload_prepare() = 0;
+    virtual int reload_commit() = 0;
+    virtual int reload_abort() = 0;
+    virtual int weights_generation() const = 0;
 };
 
 template <typename T> class Engine : public EngineBase {
@@ -55,6 +61,7 @@ public:
         : flags_(flags), device_(device), desc_(d), max_batch_(max_batch), board_(board) {
         blocks_.assign(d.blocks, d.blocks + d.residual_blocks);
         desc_.blocks = blocks_.data();
+        live_ = std::make_unique<WeightSet>();
     }
     ~Engine() override { release(); }
 
@@ -91,7 +98,7 @@ public:
         // (a layer is 450 workgroups, two rounds of the CUs, and the other ticket's launches fill the second; 200 batches
         // bit-identical to the solo result, profiles/r05_config5_pump_streams.json, tools/gpu/concurrent_ctx_dbg.py).  Without the code object
         // (SAYURI_TOWER=0, or a build whose seam was rejected) the older three-stream arrangement stays.
-        if (describe_layers()) return -1;
+        if (describe_layers(*live_)) return -1;
         // A latency context has no persistent launch to keep small copies waiting, and a round trip of one position is what it
         // is for: a stream per ticket too, no event between streams.
         inorder_ = tower_fn_[0] != nullptr || flags_.latency;
@@ -101,7 +108,7 @@ public:
     // every 3x3 convolution of the residual tower has 128 or 256 (padded) output channels and there is at least one
     bool tower_covers_net() const {
         int n3 = 0;
-        for (const auto& kv : convs_) {
+        for (const auto& kv : live_->convs) {
             const ConvLayerDev& L = kv.second;
             if (L.k != 3 || L.depthwise || kv.first == SAYURI_L_INPUT_CONV) continue;
             const int cs = round_up(L.cout, 32);
@@ -141,7 +148,7 @@ public:
         // ONE channel stride, and the packed input keeps a buffer of its own (forward_graph), so the chains' rows are disjoint
         // bytes in every buffer.  (The first version recycled the packed input's buffer, whose rows have another stride: a chain
         // that ran ahead overwrote a later chain's input -- a few dozen samples per batch off in two runs of three.)
-        if (sizeof(T) != 2 || flags_.chains == 1 || profiling_ || light_ || !head_img_ || !flags_.heads_fused) return 1;
+        if (sizeof(T) != 2 || flags_.chains == 1 || profiling_ || light_ || !live_->head_img || !flags_.heads_fused) return 1;
         if (desc_.policy_head_type != 0 || tower_covers_net()) return 1;
         for (const auto& b : blocks_)
             if (b.type != SAYURI_BLOCK_RESIDUAL) return 1;  // every layer of the graph must be a board convolution or a per-sample kernel
@@ -162,9 +169,14 @@ public:
 
     // -------------------------------------------------------------- weights
     int load_tensor(int layer, int kind, const float* host, size_t n) override {
-        if (finalized_) return fail("load_tensor after the first forward");
-        auto ci = convs_.find(layer);
-        if (ci != convs_.end()) {
+        std::lock_guard<std::mutex> rl(reload_mu_);
+        if (staged_ && staged_->built) return fail("load_tensor: the open reload is prepared already (commit or abort it)");
+        if (!staged_ && finalized_) return fail("load_tensor after the first forward");
+        WeightSet& ws = staged_ ? *staged_ : *live_;  // an open reload takes the tensors: the live set is never written in place
+        auto& convs = ws.convs;
+        auto& fcs = ws.fcs;
+        auto ci = convs.find(layer);
+        if (ci != convs.end()) {
             ConvLayerDev& L = ci->second;
             const size_t expect = kind == SAYURI_T_WEIGHTS
                                       ? (size_t)(L.depthwise ? 1 : L.cin) * L.cout * L.k * L.k
@@ -173,8 +185,8 @@ public:
             (kind == SAYURI_T_WEIGHTS ? L.hw : L.hb).assign(host, host + n);
             return 0;
         }
-        auto fi = fcs_.find(layer);
-        if (fi != fcs_.end()) {
+        auto fi = fcs.find(layer);
+        if (fi != fcs.end()) {
             FcLayerDev& L = fi->second;
             const size_t expect = kind == SAYURI_T_WEIGHTS ? (size_t)L.in * L.out : (size_t)L.out;
             if (n != expect) return fail("fc tensor size mismatch for layer " + std::to_string(layer));
@@ -189,6 +201,8 @@ public:
     int submit(int n, const float* planes, const int* board_sizes, float* prob, float* pass, float* misc, float* own,
                int* ticket, const unsigned* packed = nullptr, int binary = 0, const SymmReq* sy = nullptr) override {
         if (sy && check_symm(n, packed, *sy)) return -1;  // (before the ticket is taken: a refused call launches nothing)
+        if (n_retired_.load(std::memory_order_relaxed)) retire_poll();  // (before mu_ is taken: the frees happen outside it)
+        std::lock_guard<std::mutex> lk(mu_);  // (a reload's commit happens between two submits, never inside one)
         // The planes of batch k+1 cross PCIe while batch k computes, and the results of batch k while batch k+1 computes; each
         // of the two tickets owns its own device input / geometry / output buffers (and, by default, its own stream: below).
         const int t = next_ticket_;
@@ -268,6 +282,7 @@ public:
         if (ticket < 0 || ticket > 1 || !tick_ev_[ticket]) return fail("wait: bad ticket");
         HIP_OK(hipSetDevice(device_));
         HIP_OK(hipEventSynchronize(tick_ev_[ticket]));
+        if (n_retired_.load(std::memory_order_relaxed)) retire_poll();  // a replaced weight set whose last forwards have finished is given back
         if (sx_check(ticket)) return -1;
         if (flags_.fwdstat && fs_pending_[ticket]) {
             float ms = 0.f;
@@ -296,6 +311,7 @@ public:
     int upload(int n, const float* planes, const int* board_sizes, const unsigned* packed = nullptr, int binary = 0,
                const SymmReq* sy = nullptr) override {
         if (sy && check_symm(n, packed, *sy)) return -1;
+        std::lock_guard<std::mutex> lk(mu_);
         HIP_OK(hipSetDevice(device_));
         if (finalize()) return -1;
         HIP_OK(hipStreamSynchronize(h2d_stream_));
@@ -464,6 +480,7 @@ public:
     }
 
     int run() override {
+        std::lock_guard<std::mutex> lk(mu_);
         if (!have_batch_) return fail("run before upload");
         HIP_OK(hipSetDevice(device_));
         return forward(0);
@@ -490,8 +507,10 @@ public:
     }
 
     int time_runs(int iters, float* ms) override {
+        std::lock_guard<std::mutex> lk(mu_);
         if (!have_batch_) return fail("time_runs before upload");
         HIP_OK(hipSetDevice(device_));
+        const Measuring m{measuring_};
         pool_used_ = 0;
         group_counts_.clear();
         group_open_ = false;
@@ -542,8 +561,10 @@ public:
     }
 
     int profile_run(sayuri_hip_kernel_stat* rows, int cap) override {
+        std::lock_guard<std::mutex> lk(mu_);
         if (!have_batch_) return fail("profile_run before upload");
         HIP_OK(hipSetDevice(device_));
+        const Measuring m{measuring_};
         stats_.clear();
         profiling_ = true;
         const int rc = forward(0);
@@ -598,7 +619,89 @@ public:
         return i;
     }
 
-    size_t device_bytes() const override { return dev_bytes_; }
+    // workspaces + the live weight set + a staged one + replaced ones whose last forwards have not finished yet
+    size_t device_bytes() const override {
+        Engine* self = const_cast<Engine*>(this);
+        if (n_retired_.load(std::memory_order_relaxed)) (void)self->retire_poll();
+        // (the staged set's count is a member of its own: a caller that watches the bytes does not wait for a prepare in progress)
+        size_t b = staged_bytes_.load(std::memory_order_relaxed);
+        std::lock_guard<std::mutex> lk(self->mu_);
+        b += work_.bytes + live_->pool.bytes;
+        for (const Retired& r : retired_) b += r.set->pool.bytes;
+        return b;
+    }
+
+    // -------------------------------------------------------------- live weight reload
+    // A reload stages a second WeightSet (begin, load_tensor), builds its images into device buffers of its own (prepare) and
+    // swaps the one pointer the launch code reads the weights through (commit).  begin / load_tensor / prepare touch the staged
+    // set only (reload_mu_); commit takes mu_, which submit() and every other call that enqueues a forward hold: it falls
+    // between two forwards.  The replaced set is freed once an event recorded behind everything enqueued before the commit, on
+    // each ticket's compute stream, has fired (retire_poll: looked at by submit, wait and device_bytes, freed outside mu_).
+    int reload_begin(const sayuri_hip_netdesc& d) override {
+        std::lock_guard<std::mutex> rl(reload_mu_);
+        if (staged_) return fail("reload_begin: a reload is already open on this context (commit or abort it first)");
+        if (measuring_.load(std::memory_order_acquire)) return fail("reload_begin: the context is profiling or timing");
+        const std::string diff = desc_difference(d);
+        if (!diff.empty()) return fail("reload_begin: the network differs from the context's: " + diff + " (a context is reloaded with the same architecture only)");
+        auto ws = std::make_unique<WeightSet>();
+        if (describe_layers(*ws)) return -1;
+        staged_ = std::move(ws);
+        return 0;
+    }
+    int reload_prepare() override {
+        std::lock_guard<std::mutex> rl(reload_mu_);
+        if (!staged_) return fail("reload_prepare: no reload is open");
+        if (staged_->built) return fail("reload_prepare: the open reload is prepared already");
+        if (hipSetDevice(device_) != hipSuccess) { drop_staged(); return fail("reload_prepare: hipSetDevice failed"); }
+        int rc = build_set(*staged_);
+        staged_bytes_.store(staged_->pool.bytes, std::memory_order_relaxed);
+        if (!rc) {
+            // What the workspaces were sized by must not move (same description: it cannot; checked, not assumed).  The live set is
+            // the forwards' (mu_): the very first forward may be building it right now.
+            std::lock_guard<std::mutex> lk(mu_);
+            if (live_->built && (staged_->sx_kts != live_->sx_kts || (staged_->head_img != nullptr) != (live_->head_img != nullptr)))
+                rc = fail("reload_prepare: the new weights take another kernel form than the context's workspaces were built for");
+        }
+        if (rc) {
+            const std::string why = g_err;
+            drop_staged();
+            return fail("reload_prepare: " + why);
+        }
+        return 0;
+    }
+    int reload_commit() override {
+        std::lock_guard<std::mutex> rl(reload_mu_);
+        if (!staged_) return fail("reload_commit: no reload is open");
+        if (!staged_->built) return fail("reload_commit: the open reload is not prepared (reload_prepare first)");
+        std::lock_guard<std::mutex> lk(mu_);
+        HIP_OK(hipSetDevice(device_));
+        Retired r;
+        for (int t = 0; t < 2; ++t) {
+            if (t == 1 && compute_[1] == compute_[0]) break;
+            hipError_t e = hipEventCreateWithFlags(&r.done[t], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventRecord(r.done[t], compute_[t]);
+            if (e != hipSuccess) {
+                for (hipEvent_t& ev : r.done) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+                return fail(std::string("reload_commit: ") + hipGetErrorString(e));
+            }
+        }
+        r.set = std::move(live_);
+        live_ = std::move(staged_);
+        staged_bytes_.store(0, std::memory_order_relaxed);
+        retired_.push_back(std::move(r));
+        n_retired_.store((int)retired_.size(), std::memory_order_relaxed);
+        // Nothing else holds a weight address: routes, plans and index tables are keyed by the batch geometry and hold none, and
+        // a tower slot's table is compared bytewise with what the device holds before every launch (tower_flush).
+        return generation_.fetch_add(1, std::memory_order_acq_rel) + 1;
+    }
+    int reload_abort() override {
+        std::lock_guard<std::mutex> rl(reload_mu_);
+        if (!staged_) return fail("reload_abort: no reload is open");
+        (void)hipSetDevice(device_);
+        drop_staged();
+        return 0;
+    }
+    int weights_generation() const override { return generation_.load(std::memory_order_acquire); }
     int last_chains() const override { return last_chains_; }
     int last_split_ring() const override { return last_split_ring_; }
     int last_pw_launches() const override { return last_pw_launches_; }
@@ -616,23 +719,118 @@ public:
 
 private:
     // -------------------------------------------------------------- construction helpers
-    void add_conv(int id, int cin, int cout, int k, bool depthwise = false) {
-        ConvLayerDev L;
-        L.cin = cin; L.cout = cout; L.k = k; L.depthwise = depthwise;
-        convs_[id] = L;
+    // Device allocations with one owner and one byte count: the context's workspaces, or one weight set.
+    struct DevPool {
+        std::vector<void*> allocs;
+        size_t bytes = 0;
+    };
+    // A WEIGHT SET: everything a forward reads that is derived from the weights -- the layers with their device images, the SE
+    // images inside them, the head images -- in device allocations of its own.  The launch code reaches it through live_ alone.
+    struct WeightSet {
+        std::map<int, ConvLayerDev> convs;
+        std::map<int, FcLayerDev> fcs;
+        HeadFn head_fn = nullptr;
+        void* head_img2 = nullptr;  // per-pixel weights (policy planes, ownership) as an MFMA image
+        void* head_img = nullptr;   // stacked head-convolution image (head_board.h); null = separate head kernels
+        float* head_bias = nullptr;
+        int head_pt = 0, head_vt = 0;
+        int sx_kts = 0;             // channel tiles per layer of the split SE images (0: the set has none)
+        bool built = false;         // the images are on the device (build_set)
+        DevPool pool;
+    };
+    // a replaced set and the events behind the last forwards that may read it, one per compute stream
+    struct Retired {
+        std::unique_ptr<WeightSet> set;
+        hipEvent_t done[2] = {nullptr, nullptr};
+    };
+    struct Measuring {  // time_runs / profile_run in progress: no reload is opened meanwhile
+        std::atomic<bool>& flag;
+        explicit Measuring(std::atomic<bool>& f) : flag(f) { flag.store(true, std::memory_order_release); }
+        ~Measuring() { flag.store(false, std::memory_order_release); }
+    };
+    void free_pool(DevPool& p) {
+        for (void* q : p.allocs) (void)hipFree(q);
+        p.allocs.clear();
+        p.bytes = 0;
     }
-    void add_fc(int id, int in, int out) {
-        FcLayerDev L;
-        L.in = in; L.out = out;
-        fcs_[id] = L;
+    void drop_staged() {  // reload_mu_ held
+        if (staged_) free_pool(staged_->pool);
+        staged_.reset();
+        staged_bytes_.store(0, std::memory_order_relaxed);
+    }
+    // Frees every replaced set whose events have all fired; a set whose forwards still run stays for the next look.  Called
+    // WITHOUT mu_: the finished sets are taken off the list under it, and freed outside it -- hipFree synchronises the device, once
+    // per allocation of the set, and a submit on another thread must not wait behind that for the mutex.
+    int retire_poll() {
+        std::vector<Retired> gone;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            for (size_t i = 0; i < retired_.size();) {
+                bool done = true;
+                for (hipEvent_t e : retired_[i].done)
+                    if (e && hipEventQuery(e) != hipSuccess) done = false;
+                if (!done) { (void)hipGetLastError(); ++i; continue; }
+                gone.push_back(std::move(retired_[i]));
+                retired_.erase(retired_.begin() + (long)i);
+            }
+            n_retired_.store((int)retired_.size(), std::memory_order_relaxed);
+        }
+        if (!gone.empty()) (void)hipSetDevice(device_);
+        for (Retired& r : gone) {
+            free_pool(r.set->pool);
+            for (hipEvent_t e : r.done)
+                if (e) (void)hipEventDestroy(e);
+        }
+        return 0;
+    }
+    // What of a description shapes buffers or kernels, against the context's own: "" when nothing differs.
+    std::string desc_difference(const sayuri_hip_netdesc& d) const {
+        const sayuri_hip_netdesc& c = desc_;
+        auto ne = [](const char* what, int have, int got) { return std::string(what) + " " + std::to_string(got) + " (the context has " + std::to_string(have) + ")"; };
+        if (d.residual_blocks != c.residual_blocks) return ne("residual_blocks", c.residual_blocks, d.residual_blocks);
+        if (d.residual_channels != c.residual_channels) return ne("residual_channels", c.residual_channels, d.residual_channels);
+        if (d.input_channels != c.input_channels) return ne("input_channels", c.input_channels, d.input_channels);
+        if ((d.version <= 2) != (c.version <= 2)) return ne("version (encoder)", c.version, d.version);
+        if (d.policy_head_type != c.policy_head_type) return ne("policy_head_type", c.policy_head_type, d.policy_head_type);
+        if (d.policy_head_channels != c.policy_head_channels) return ne("policy_head_channels", c.policy_head_channels, d.policy_head_channels);
+        if (d.value_head_channels != c.value_head_channels) return ne("value_head_channels", c.value_head_channels, d.value_head_channels);
+        if (d.policy_dw_filter != c.policy_dw_filter) return ne("policy_dw_filter", c.policy_dw_filter, d.policy_dw_filter);
+        if (d.probabilities_channels != c.probabilities_channels) return ne("probabilities_channels", c.probabilities_channels, d.probabilities_channels);
+        if (d.pass_probability_outputs != c.pass_probability_outputs) return ne("pass_probability_outputs", c.pass_probability_outputs, d.pass_probability_outputs);
+        if (d.ownership_channels != c.ownership_channels) return ne("ownership_channels", c.ownership_channels, d.ownership_channels);
+        if (d.value_misc_outputs != c.value_misc_outputs) return ne("value_misc_outputs", c.value_misc_outputs, d.value_misc_outputs);
+        if (d.default_act != c.default_act) return ne("default_act", c.default_act, d.default_act);
+        if (!d.blocks) return "no block descriptions";
+        for (int b = 0; b < c.residual_blocks; ++b) {
+            const sayuri_hip_blockdesc &x = d.blocks[b], &y = blocks_[b];
+            const std::string at = "block " + std::to_string(b) + ": ";
+            if (x.type != y.type) return at + ne("type", y.type, x.type);
+            if ((x.apply_se != 0) != (y.apply_se != 0)) return at + ne("apply_se", y.apply_se, x.apply_se);
+            if (y.apply_se && x.se_size != y.se_size) return at + ne("se_size", y.se_size, x.se_size);
+            if (x.bottleneck_channels != y.bottleneck_channels) return at + ne("bottleneck_channels", y.bottleneck_channels, x.bottleneck_channels);
+            if (x.feedforward_channels != y.feedforward_channels) return at + ne("feedforward_channels", y.feedforward_channels, x.feedforward_channels);
+            if (x.dw_filter != y.dw_filter) return at + ne("dw_filter", y.dw_filter, x.dw_filter);
+        }
+        return "";
     }
 
-    int describe_layers() {
+    // the layers of the context's description, without tensors, into `ws`
+    int describe_layers(WeightSet& ws) {
+        auto add_conv = [&ws](int id, int cin, int cout, int k, bool depthwise = false) {
+            ConvLayerDev L;
+            L.cin = cin; L.cout = cout; L.k = k; L.depthwise = depthwise;
+            ws.convs[id] = L;
+        };
+        auto add_fc = [&ws](int id, int in, int out) {
+            FcLayerDev L;
+            L.in = in; L.out = out;
+            ws.fcs[id] = L;
+        };
         const auto& d = desc_;
         const int C = d.residual_channels;
         if (C <= 0 || d.input_channels <= 0) return fail("bad net description");
         add_conv(SAYURI_L_INPUT_CONV, d.input_channels, C, 3);
-        cs_max_ = std::max(round_up(C, 32), round_up(d.input_channels, 32));
+        int cs_max = std::max(round_up(C, 32), round_up(d.input_channels, 32));  // (a member for the context's own set only)
         for (int b = 0; b < d.residual_blocks; ++b) {
             const auto& bd = blocks_[b];
             const int I = bd.bottleneck_channels, F = bd.feedforward_channels;
@@ -652,14 +850,14 @@ private:
                     add_conv(SAYURI_L_BLOCK(b, SAYURI_S_CONV4), I, I, 3);
                 }
                 add_conv(SAYURI_L_BLOCK(b, SAYURI_S_POST_BTL), I, C, 1);
-                cs_max_ = std::max(cs_max_, round_up(I, 32));
+                cs_max = std::max(cs_max, round_up(I, 32));
                 break;
             case SAYURI_BLOCK_MIXER:
                 if (F <= 0 || bd.dw_filter <= 0) return fail("mixer block without ffn channels / dw filter");
                 add_conv(SAYURI_L_BLOCK(b, SAYURI_S_DW_CONV), C, C, bd.dw_filter, true);
                 add_conv(SAYURI_L_BLOCK(b, SAYURI_S_CONV1), C, F, 1);
                 add_conv(SAYURI_L_BLOCK(b, SAYURI_S_CONV2), F, C, 1);
-                cs_max_ = std::max(cs_max_, round_up(F, 32));
+                cs_max = std::max(cs_max, round_up(F, 32));
                 break;
             default:
                 return fail("unknown block type");
@@ -687,11 +885,14 @@ private:
         add_fc(SAYURI_L_V_INTER_FC, 3 * Cv, 3 * Cv);
         add_conv(SAYURI_L_V_OWNERSHIP, Cv, 1, 1);
         add_fc(SAYURI_L_V_MISC, 3 * Cv, d.value_misc_outputs);
-        cs_max_ = std::max(cs_max_, std::max(round_up(Cp, 32), round_up(Cv, 32)));
+        cs_max = std::max(cs_max, std::max(round_up(Cp, 32), round_up(Cv, 32)));
+        if (&ws == live_.get()) cs_max_ = cs_max;
         return 0;
     }
 
-    template <typename U> int dev_alloc(U** p, size_t count) {
+    template <typename U> int dev_alloc(U** p, size_t count) { return dev_alloc(work_, p, count); }
+    template <typename U> int dev_upload(U** p, const std::vector<U>& h) { return dev_upload(work_, p, h); }
+    template <typename U> int dev_alloc(DevPool& pool, U** p, size_t count) {
         void* q = nullptr;
         const size_t bytes = std::max<size_t>(count * sizeof(U), 256);
         HIP_OK(hipMalloc(&q, bytes));
@@ -700,13 +901,13 @@ private:
         // a staging slot lost the tail of its records to the fill of the buffer allocated for them one call earlier).
         HIP_OK(hipMemset(q, 0, bytes));
         HIP_OK(hipStreamSynchronize(nullptr));
-        allocs_.push_back(q);
-        dev_bytes_ += bytes;
+        pool.allocs.push_back(q);
+        pool.bytes += bytes;
         *p = (U*)q;
         return 0;
     }
-    template <typename U> int dev_upload(U** p, const std::vector<U>& h) {
-        if (dev_alloc(p, h.size())) return -1;
+    template <typename U> int dev_upload(DevPool& pool, U** p, const std::vector<U>& h) {
+        if (dev_alloc(pool, p, h.size())) return -1;
         HIP_OK(hipMemcpy(*p, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice));
         return 0;
     }
@@ -714,41 +915,44 @@ private:
     static bool is_tiny_head_conv(int id) { return id == SAYURI_L_PROB_CONV || id == SAYURI_L_V_OWNERSHIP; }
 
     // Stacked [policy | value] head-convolution image for head_board_kernel (fp16 engine, normal policy head).
-    int build_head_image() {
+    int build_head_image(WeightSet& ws) {
         const sayuri_hip_netdesc& d = desc_;
         if (sizeof(T) != 2 || d.policy_head_type != 0) return 0;
-        const ConvLayerDev& P = convs_.at(SAYURI_L_P_HD_CONV);
-        const ConvLayerDev& V = convs_.at(SAYURI_L_V_HD_CONV);
-        const ConvLayerDev& PW = convs_.at(SAYURI_L_PROB_CONV);
-        const ConvLayerDev& OW = convs_.at(SAYURI_L_V_OWNERSHIP);
+        const ConvLayerDev& P = ws.convs.at(SAYURI_L_P_HD_CONV);
+        const ConvLayerDev& V = ws.convs.at(SAYURI_L_V_HD_CONV);
+        const ConvLayerDev& PW = ws.convs.at(SAYURI_L_PROB_CONV);
+        const ConvLayerDev& OW = ws.convs.at(SAYURI_L_V_OWNERSHIP);
         if (P.hw.empty() || V.hw.empty() || P.hb.empty() || V.hb.empty() || PW.hw.empty() || OW.hw.empty()) return 0;
         HeadImages hi;
-        head_fn_ = make_head_images(P.cin, P.cout, V.cout, d.probabilities_channels, board_, P.hw.data(), P.hb.data(), V.hw.data(),
-                                    V.hb.data(), PW.hw.data(), OW.hw.data(), &hi);
-        if (!head_fn_) return 0;
+        ws.head_fn = make_head_images(P.cin, P.cout, V.cout, d.probabilities_channels, board_, P.hw.data(), P.hb.data(), V.hw.data(),
+                                      V.hb.data(), PW.hw.data(), OW.hw.data(), &hi);
+        if (!ws.head_fn) return 0;
         f16 *w = nullptr, *w2 = nullptr;
-        if (dev_upload(&w2, hi.img2) || dev_upload(&w, hi.img) || dev_upload(&head_bias_, hi.bias)) return -1;
-        head_img2_ = w2;
-        head_img_ = w;
-        head_pt_ = hi.PT;
-        head_vt_ = hi.VT;
+        if (dev_upload(ws.pool, &w2, hi.img2) || dev_upload(ws.pool, &w, hi.img) || dev_upload(ws.pool, &ws.head_bias, hi.bias)) return -1;
+        ws.head_img2 = w2;
+        ws.head_img = w;
+        ws.head_pt = hi.PT;
+        ws.head_vt = hi.VT;
         return 0;
     }
 
-    int finalize() {
-        if (finalized_) return 0;
-        if (build_head_image()) return -1;
-        for (auto& kv : convs_) {
+    // Loaded tensors -> the device images of a weight set, in the set's own allocations.  The reusable half of what the first
+    // forward does: finalize() builds the live set with it, reload_prepare() a staged one beside the running forwards (the
+    // uploads go through the null stream into buffers nothing reads yet: they order against nothing, and need not).
+    int build_set(WeightSet& ws) {
+        DevPool& pool = ws.pool;
+        if (build_head_image(ws)) return -1;
+        for (auto& kv : ws.convs) {
             ConvLayerDev& L = kv.second;
             if (L.hw.empty() || L.hb.empty()) return fail("missing tensors for conv layer " + std::to_string(kv.first));
             L.cin_s = round_up(L.cin, 32);
             L.cout_s = round_up(L.cout, 32);
             if (is_tiny_head_conv(kv.first)) {  // consumed by head_tail_kernel in fp32
-                if (dev_upload(&L.w32, L.hw) || dev_upload(&L.bias, L.hb)) return -1;
+                if (dev_upload(pool, &L.w32, L.hw) || dev_upload(pool, &L.bias, L.hb)) return -1;
             } else if (L.depthwise) {
                 float* w = nullptr;
-                if (dev_upload(&w, depthwise_image(L.hw.data(), L.cout, L.k * L.k, L.cout_s)) ||
-                    dev_upload(&L.bias, padded_bias(L.hb.data(), L.cout, L.cout_s)))
+                if (dev_upload(pool, &w, depthwise_image(L.hw.data(), L.cout, L.k * L.k, L.cout_s)) ||
+                    dev_upload(pool, &L.bias, padded_bias(L.hb.data(), L.cout, L.cout_s)))
                     return -1;
                 L.w = w;
             } else {
@@ -756,25 +960,35 @@ private:
                 const std::vector<T> img = conv_image<T>(L.hw.data(), L.cin, L.cout, L.k * L.k, L.ko_pad);
                 const std::vector<float> b = padded_bias(L.hb.data(), L.cout, L.ko_pad);
                 T* w = nullptr;
-                if (dev_upload(&w, img) || dev_upload(&L.bias, b)) return -1;
+                if (dev_upload(pool, &w, img) || dev_upload(pool, &L.bias, b)) return -1;
                 L.w = w;
                 if (sizeof(T) == 2 && L.k == 3 && L.ko_pad % 128 == 0 && !flags_.latency) {  // (conv_split.h reads the natural order)
                     T* wb = nullptr;
-                    if (dev_upload(&wb, board_row_order(img, L.ko_pad)) || dev_upload(&L.bias_board, board_row_order(b, L.ko_pad, 1))) return -1;
+                    if (dev_upload(pool, &wb, board_row_order(img, L.ko_pad)) || dev_upload(pool, &L.bias_board, board_row_order(b, L.ko_pad, 1))) return -1;
                     L.w_board = wb;
                 }
             }
             std::vector<float>().swap(L.hw);
             std::vector<float>().swap(L.hb);
         }
-        if (build_se_images()) return -1;
-        for (auto& kv : fcs_) {
+        if (build_se_images(ws)) return -1;
+        for (auto& kv : ws.fcs) {
             FcLayerDev& L = kv.second;
             if (L.hw.empty() || L.hb.empty()) return fail("missing tensors for fc layer " + std::to_string(kv.first));
-            if (dev_upload(&L.wt, fc_transposed(L.hw.data(), L.in, L.out)) || dev_upload(&L.b, L.hb)) return -1;
+            if (dev_upload(pool, &L.wt, fc_transposed(L.hw.data(), L.in, L.out)) || dev_upload(pool, &L.b, L.hb)) return -1;
             std::vector<float>().swap(L.hw);
             std::vector<float>().swap(L.hb);
         }
+        ws.built = true;
+        return 0;
+    }
+
+    // The once-only half: the live set (unless a reload committed before the first forward has brought one that is built), then
+    // workspaces, pinned rings and tables.
+    int finalize() {
+        if (finalized_) return 0;
+        if (!live_->built && build_set(*live_)) return -1;
+        sx_kts_ = live_->sx_kts;
         // workspaces
         slot_pix_ = board_ * board_;
         const size_t act_elems = (size_t)max_batch_ * slot_pix_ * cs_max_;
@@ -821,13 +1035,15 @@ private:
     // weights once per board size 2..board with the scaled-mean third of the pooled vector folded into the mean third
     // (reference GlobalPooling<false>, se_unit.cc:9-40: pool = (mean, mean * (B-14)/10, max)), the excite weights with
     // both bias vectors behind them.  Units whose images do not fit the LDS keep reading fp32 weights from L2.
-    int build_se_images() {
+    int build_se_images(WeightSet& ws) {
         if (sizeof(T) != 2) return 0;
+        auto& fcs = ws.fcs;
+        DevPool& pool = ws.pool;
         const int C = desc_.residual_channels;
         for (int b = 0; b < desc_.residual_blocks; ++b) {
             if (!blocks_[b].apply_se) continue;
-            FcLayerDev& sq = fcs_.at(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE));
-            FcLayerDev& ex = fcs_.at(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE));
+            FcLayerDev& sq = fcs.at(SAYURI_L_BLOCK(b, SAYURI_S_SQUEEZE));
+            FcLayerDev& ex = fcs.at(SAYURI_L_BLOCK(b, SAYURI_S_EXCITE));
             const int se = sq.out;
             if (sq.hw.empty() || ex.hw.empty() || sq.hb.empty() || ex.hb.empty()) continue;  // finalize() reports it
             if (sq.in != 3 * C || ex.in != se || ex.out != 2 * C) continue;
@@ -841,16 +1057,16 @@ private:
                     make_sx_images(C, se, kts, board_, sq.hw.data(), sq.hb.data(), ex.hw.data(), ex.hb.data(), &img1, &img2, &w1_bytes, &w2_bytes)) {
                     f16* d1 = nullptr;
                     unsigned char* d2 = nullptr;
-                    if (dev_upload(&d1, img1) || dev_upload(&d2, img2)) return -1;
+                    if (dev_upload(pool, &d1, img1) || dev_upload(pool, &d2, img2)) return -1;
                     sq.sx_img = d1; sq.sx_bytes = w1_bytes;
                     ex.sx_img = d2; ex.sx_bytes = w2_bytes;
-                    sx_kts_ = kts;
+                    ws.sx_kts = kts;
                 }
                 continue;
             }
             f16* d1 = nullptr;
             unsigned char* d2 = nullptr;
-            if (dev_upload(&d1, img1) || dev_upload(&d2, img2)) return -1;
+            if (dev_upload(pool, &d1, img1) || dev_upload(pool, &d2, img2)) return -1;
             sq.img16 = d1; sq.img_bytes = w1_bytes;
             ex.img16 = d2; ex.img_bytes = w2_bytes;
         }
@@ -859,8 +1075,17 @@ private:
 
     void release() {
         (void)hipSetDevice(device_);
-        for (void* p : allocs_) (void)hipFree(p);
-        allocs_.clear();
+        free_pool(work_);
+        if (live_) free_pool(live_->pool);
+        if (staged_) free_pool(staged_->pool);
+        staged_.reset();
+        for (Retired& r : retired_) {
+            free_pool(r.set->pool);
+            for (hipEvent_t e : r.done)
+                if (e) (void)hipEventDestroy(e);
+        }
+        retired_.clear();
+        n_retired_.store(0, std::memory_order_relaxed);
         ident_.clear();
         if (h_geom_) (void)hipHostFree(h_geom_);
         h_geom_ = nullptr;
@@ -1413,8 +1638,9 @@ private:
         return 0;
     }
 
-    const ConvLayerDev& cv(int id) const { return convs_.at(id); }
-    const FcLayerDev& fc(int id) const { return fcs_.at(id); }
+    // the live weight set's layers: the one way the launch code reaches a weight
+    const ConvLayerDev& cv(int id) const { return live_->convs.at(id); }
+    const FcLayerDev& fc(int id) const { return live_->fcs.at(id); }
 
     // -------------------------------------------------------------- the graph
     // One forward of ticket t's batch: as ONE chain of launches on the ticket's compute stream, or -- chains_for_batch() -- as
@@ -1586,7 +1812,7 @@ private:
         const HeadWeights hw{fc(SAYURI_L_P_INTER_FC).dev(), fc(SAYURI_L_PASS_FC).dev(), fc(SAYURI_L_V_INTER_FC).dev(), fc(SAYURI_L_V_MISC).dev(),
                              pw.w32, pw.bias, ow.w32, ow.bias};
         const HeadParams h = head_params(hw, Cp, Cv, d.probabilities_channels, act, board_, f.io.prob, f.pass, f.misc, f.io.own, f.io.g_perm);
-        if (head_img_ && flags_.heads_fused) {
+        if (live_->head_img && flags_.heads_fused) {
             // both heads of a sample in one workgroup: trunk -> LDS -> stacked 1x1 convolution on the matrix cores -> pooling,
             // FCs and the per-pixel planes (head_board.h)
             HeadBoardParams hp;
@@ -1597,9 +1823,9 @@ private:
                 hp.dbg = d_hdbg_;
             }
 #endif
-            hp.trunk = buf[x]; hp.w = head_img_; hp.w2 = head_img2_; hp.bias = head_bias_; hp.g = g; hp.cs = csC; hp.PT = head_pt_; hp.VT = head_vt_; hp.h = h;
+            hp.trunk = buf[x]; hp.w = live_->head_img; hp.w2 = live_->head_img2; hp.bias = live_->head_bias; hp.g = g; hp.cs = csC; hp.PT = live_->head_pt; hp.VT = live_->head_vt; hp.h = h;
             hp.n0 = f.n0;
-            const auto fn = head_fn_;
+            const auto fn = live_->head_fn;
             const int ns = f.ns;
             return timed(f, "heads_fused", 2.0 * f.px * C * (Cp + Cv), f.px * csC * 2, [&] {
                 hipLaunchKernelGGL(fn, dim3(ns), dim3(512), kMaxLds, f.stream, hp);
@@ -1725,8 +1951,14 @@ private:
     std::vector<sayuri_hip_blockdesc> blocks_;
     int max_batch_, board_;
     int cs_max_ = 32, slot_pix_ = 0;
-    std::map<int, ConvLayerDev> convs_;
-    std::map<int, FcLayerDev> fcs_;
+    std::unique_ptr<WeightSet> live_;    // what forwards read (mu_)
+    std::unique_ptr<WeightSet> staged_;  // an open reload's set (reload_mu_)
+    std::vector<Retired> retired_;       // replaced sets whose last forwards may still run (mu_)
+    std::atomic<int> n_retired_{0}, generation_{0};
+    std::atomic<size_t> staged_bytes_{0};  // device bytes of the staged set (updated when a prepare ends, a reload closes)
+    std::atomic<bool> measuring_{false};
+    std::mutex mu_;         // everything that enqueues a forward, and a reload's commit
+    std::mutex reload_mu_;  // the staged set; taken before mu_ where both are
     bool finalized_ = false, have_batch_ = false, profiling_ = false;
     hipStream_t h2d_stream_ = nullptr, d2h_stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
@@ -1734,8 +1966,7 @@ private:
     IoSlot io_[2];
     hipStream_t compute_[2] = {nullptr, nullptr};  // each ticket's forwards (init())
     bool inorder_ = false;  // a ticket's copies on the ticket's compute stream (init(), submit())
-    std::vector<void*> allocs_;
-    size_t dev_bytes_ = 0;
+    DevPool work_;  // workspaces, tables, i/o buffers: everything that is not a weight
     std::vector<int> perm_;  // device sample -> caller's slot (enqueue_inputs)
     float* d_zeros_ = nullptr;
     int* h_symm_ = nullptr;  // pinned 2-slot ring: [slot][src(max_batch) | symm(max_batch)] (allocated with the first SymmReq batch)
@@ -1750,11 +1981,6 @@ private:
     std::map<PlanKey, DwPlan> dw_cache_;        // by (cs, k) and the range
     std::map<PlanKey, SplitPlan> split_cache_;  // latency context: by ko_pad and the range
     BoardPlan board_plan_;
-    HeadFn head_fn_ = nullptr;
-    void* head_img2_ = nullptr;  // per-pixel weights (policy planes, ownership) as an MFMA image
-    void* head_img_ = nullptr;   // stacked head-convolution image (head_board.h); null = separate head kernels
-    float* head_bias_ = nullptr;
-    int head_pt_ = 0, head_vt_ = 0;
     unsigned long long* d_hdbg_ = nullptr;  // SAYURI_HEADS_DBG timeline of head_board_kernel
     unsigned long long* d_dbg_ = nullptr;  // SAYURI_BOARD_DBG timeline of one tower convolution
     unsigned long long* d_sxdbg_ = nullptr;  // SAYURI_SX_DBG timeline of one split SE convolution

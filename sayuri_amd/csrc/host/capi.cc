@@ -168,6 +168,28 @@ int sayuri_packed_symmetry(const std::uint32_t* record, int binary, int bs, int 
     b.Store(out);
     return 0;
 }
+// Live weight reload (HipForwardPipe::Reload): the file is parsed on the calling thread, then staged, built and committed beside
+// the running batches.  -1 with the loader's or the device's message; the pipe then serves the network it had.  (The handle keeps
+// the DNNWeights it was created from for the shapes its taps read, which a reload cannot change; the version is the pipe's.)
+int sayuri_pipe_accepts_reload(void* hp) { return static_cast<PipeHandle*>(hp)->pipe->AcceptsReload() ? 1 : 0; }
+int sayuri_pipe_reload(void* hp, const char* weights_path) {
+    auto* h = static_cast<PipeHandle*>(hp);
+    if (!h || !weights_path) return -1;
+    try {
+        auto w = std::make_shared<DNNWeights>();
+        std::string err;
+        if (!LoadWeightsFile(weights_path, w.get(), &err)) {
+            g_err = err;
+            return -1;
+        }
+        h->pipe->Reload(std::move(w));
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+int sayuri_pipe_weights_generation(void* hp) { return static_cast<PipeHandle*>(hp)->pipe->WeightsGeneration(); }
 int sayuri_pipe_num_workers(void* hp) { return static_cast<PipeHandle*>(hp)->pipe->GetNumWorkers(); }
 void* sayuri_pipe_ctx(void* hp, int gpu) { return static_cast<PipeHandle*>(hp)->pipe->ctx(gpu); }
 int sayuri_pipe_reconstruct(void* hp, int board, int batch) {
@@ -207,7 +229,7 @@ extern "C" void* sayuri_pipe_raw(void* hp) {
 }
 extern "C" int sayuri_pipe_weights_version(void* hp) {
     auto* h = static_cast<PipeHandle*>(hp);
-    return h && h->weights ? h->weights->version : -1;
+    return h && h->pipe ? h->pipe->WeightsVersion() : -1;  // (the network in use: a reload may have brought another version)
 }
 
 extern "C" int sayuri_pipe_eval(void* hp, int mode, int gpu, int n, const float* planes, const int* board_sizes,

@@ -88,8 +88,35 @@ CreateExFn FindCreateEx() { return reinterpret_cast<CreateExFn>(FindInDeviceLibr
 typedef int (*SubmitSymmFn)(sayuri_hip_ctx*, int, const unsigned*, int, int, const int*, const int*, const int*, float*, float*, float*,
                             float*, int*);
 
-sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bool fp16, unsigned hip_flags) {
-    std::vector<sayuri_hip_blockdesc> blocks(w.residual_blocks);
+// The live-reload entry points of the device library in use, looked up like create_ex: a library without them (an older build, the
+// plain stand-in of the host tests) serves everything else, and the pipe says AcceptsReload() == false.
+struct ReloadFns {
+    int (*begin)(sayuri_hip_ctx*, const sayuri_hip_netdesc*) = nullptr;
+    int (*prepare)(sayuri_hip_ctx*) = nullptr;
+    int (*commit)(sayuri_hip_ctx*) = nullptr;
+    int (*abort)(sayuri_hip_ctx*) = nullptr;
+    int (*generation)(const sayuri_hip_ctx*) = nullptr;
+    bool all() const { return begin && prepare && commit && abort && generation; }
+};
+ReloadFns FindReload() {
+    ReloadFns f;
+    f.begin = reinterpret_cast<decltype(f.begin)>(FindInDeviceLibrary("sayuri_hip_reload_begin"));
+    f.prepare = reinterpret_cast<decltype(f.prepare)>(FindInDeviceLibrary("sayuri_hip_reload_prepare"));
+    f.commit = reinterpret_cast<decltype(f.commit)>(FindInDeviceLibrary("sayuri_hip_reload_commit"));
+    f.abort = reinterpret_cast<decltype(f.abort)>(FindInDeviceLibrary("sayuri_hip_reload_abort"));
+    f.generation = reinterpret_cast<decltype(f.generation)>(FindInDeviceLibrary("sayuri_hip_weights_generation"));
+    return f;
+}
+
+// The architecture of a DNNWeights as the device library takes it.
+struct NetDesc {
+    std::vector<sayuri_hip_blockdesc> blocks;
+    sayuri_hip_netdesc d{};
+};
+void DescribeNet(DNNWeights& w, NetDesc* nd) {
+    std::vector<sayuri_hip_blockdesc>& blocks = nd->blocks;
+    sayuri_hip_netdesc& d = nd->d;
+    blocks.assign(w.residual_blocks, sayuri_hip_blockdesc{});
     for (int i = 0; i < w.residual_blocks; ++i) {
         BlockBasic& b = *w.tower[i];
         blocks[i].type = BlockTypeCode(b);
@@ -99,7 +126,7 @@ sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bo
         blocks[i].feedforward_channels = b.feedforward_channels;
         blocks[i].dw_filter = b.IsMixerBlock() ? b.dw_conv.GetFilter() : 0;
     }
-    sayuri_hip_netdesc d{};
+    d = sayuri_hip_netdesc{};
     d.version = w.version;
     d.input_channels = w.input_channels;
     d.residual_channels = w.residual_channels;
@@ -114,6 +141,53 @@ sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bo
     d.policy_head_type = w.policy_head_type == PolicyHeadType::kRepLK ? 1 : 0;
     d.policy_dw_filter = d.policy_head_type ? w.p_dw_conv.GetFilter() : 0;
     d.blocks = blocks.data();
+}
+
+// Every tensor of the network into the context: a new one's own set, or the staged set of an open reload.  Throws on a refusal.
+void LoadTensors(sayuri_hip_ctx* ctx, DNNWeights& w) {
+    LoadConv(ctx, SAYURI_L_INPUT_CONV, w.input_conv);
+    for (int i = 0; i < w.residual_blocks; ++i) {
+        BlockBasic& b = *w.tower[i];
+        if (b.IsResidualBlock()) {
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV1), b.conv1);
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV2), b.conv2);
+        } else if (b.IsBottleneckBlock() || b.IsNestedBottleneckBlock()) {
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_PRE_BTL), b.pre_btl_conv);
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV1), b.conv1);
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV2), b.conv2);
+            if (b.IsNestedBottleneckBlock()) {
+                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV3), b.conv3);
+                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV4), b.conv4);
+            }
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_POST_BTL), b.post_btl_conv);
+        } else {
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_DW_CONV), b.dw_conv);
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV1), b.conv1);
+            LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV2), b.conv2);
+        }
+        if (b.apply_se) {
+            LoadFc(ctx, SAYURI_L_BLOCK(i, SAYURI_S_SQUEEZE), b.squeeze);
+            LoadFc(ctx, SAYURI_L_BLOCK(i, SAYURI_S_EXCITE), b.excite);
+        }
+    }
+    LoadConv(ctx, SAYURI_L_P_HD_CONV, w.p_hd_conv);
+    if (w.policy_head_type == PolicyHeadType::kRepLK) {
+        LoadConv(ctx, SAYURI_L_P_DW_CONV, w.p_dw_conv);
+        LoadConv(ctx, SAYURI_L_P_PT_CONV, w.p_pt_conv);
+    }
+    LoadFc(ctx, SAYURI_L_P_INTER_FC, w.p_inter_fc);
+    LoadConv(ctx, SAYURI_L_PROB_CONV, w.prob_conv);
+    LoadFc(ctx, SAYURI_L_PASS_FC, w.pass_fc);
+    LoadConv(ctx, SAYURI_L_V_HD_CONV, w.v_hd_conv);
+    LoadFc(ctx, SAYURI_L_V_INTER_FC, w.v_inter_fc);
+    LoadConv(ctx, SAYURI_L_V_OWNERSHIP, w.v_ownership);
+    LoadFc(ctx, SAYURI_L_V_MISC, w.v_misc);
+}
+
+sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bool fp16, unsigned hip_flags) {
+    NetDesc nd;
+    DescribeNet(w, &nd);
+    const sayuri_hip_netdesc& d = nd.d;
 
     sayuri_hip_ctx* ctx = nullptr;
     if (hip_flags) {
@@ -128,43 +202,7 @@ sayuri_hip_ctx* BuildCtx(int device, DNNWeights& w, int max_batch, int board, bo
         if (!ctx) ThrowHip("sayuri_hip_create");
     }
     try {
-        LoadConv(ctx, SAYURI_L_INPUT_CONV, w.input_conv);
-        for (int i = 0; i < w.residual_blocks; ++i) {
-            BlockBasic& b = *w.tower[i];
-            if (b.IsResidualBlock()) {
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV1), b.conv1);
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV2), b.conv2);
-            } else if (b.IsBottleneckBlock() || b.IsNestedBottleneckBlock()) {
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_PRE_BTL), b.pre_btl_conv);
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV1), b.conv1);
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV2), b.conv2);
-                if (b.IsNestedBottleneckBlock()) {
-                    LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV3), b.conv3);
-                    LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV4), b.conv4);
-                }
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_POST_BTL), b.post_btl_conv);
-            } else {
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_DW_CONV), b.dw_conv);
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV1), b.conv1);
-                LoadConv(ctx, SAYURI_L_BLOCK(i, SAYURI_S_CONV2), b.conv2);
-            }
-            if (b.apply_se) {
-                LoadFc(ctx, SAYURI_L_BLOCK(i, SAYURI_S_SQUEEZE), b.squeeze);
-                LoadFc(ctx, SAYURI_L_BLOCK(i, SAYURI_S_EXCITE), b.excite);
-            }
-        }
-        LoadConv(ctx, SAYURI_L_P_HD_CONV, w.p_hd_conv);
-        if (d.policy_head_type) {
-            LoadConv(ctx, SAYURI_L_P_DW_CONV, w.p_dw_conv);
-            LoadConv(ctx, SAYURI_L_P_PT_CONV, w.p_pt_conv);
-        }
-        LoadFc(ctx, SAYURI_L_P_INTER_FC, w.p_inter_fc);
-        LoadConv(ctx, SAYURI_L_PROB_CONV, w.prob_conv);
-        LoadFc(ctx, SAYURI_L_PASS_FC, w.pass_fc);
-        LoadConv(ctx, SAYURI_L_V_HD_CONV, w.v_hd_conv);
-        LoadFc(ctx, SAYURI_L_V_INTER_FC, w.v_inter_fc);
-        LoadConv(ctx, SAYURI_L_V_OWNERSHIP, w.v_ownership);
-        LoadFc(ctx, SAYURI_L_V_MISC, w.v_misc);
+        LoadTensors(ctx, w);
     } catch (...) {
         sayuri_hip_destroy(ctx);
         throw;
@@ -190,7 +228,7 @@ HipForwardPipe::~HipForwardPipe() {
     }
 }
 
-bool HipForwardPipe::Valid() const { return weights_ != nullptr; }
+bool HipForwardPipe::Valid() const { return valid_.load(std::memory_order_acquire); }
 
 sayuri_hip_ctx* HipForwardPipe::ctx(int gpu) const {
     return gpu >= 0 && gpu < static_cast<int>(graphs_.size()) ? graphs_[gpu]->ctx : nullptr;
@@ -204,6 +242,7 @@ void HipForwardPipe::Initialize(std::shared_ptr<DNNWeights> weights) {
 void HipForwardPipe::Construct(ForwardPipeOption option, std::shared_ptr<DNNWeights> weights) {
     // cuda_forward_pipe.cc:44-119: rebuild only when the board changes or the batch grows.
     if (weights) weights_ = weights;
+    valid_.store(weights_ != nullptr, std::memory_order_release);
     if (weights_ == nullptr) return;  // Network falls back to its dummy backend
     int board = option.IsValidBoardSize() ? option.board_size : board_size_;
     int batch = option.IsValidBatchSize() ? option.batch_size : max_batch_;
@@ -230,6 +269,9 @@ void HipForwardPipe::BuildGraphs() {
 
     const size_t B2 = static_cast<size_t>(board_size_) * board_size_;
     DNNWeights& w = *weights_;
+    shape_ = NetShape{w.version, w.input_channels, w.probabilities_channels, w.pass_probability_outputs, w.value_misc_outputs};
+    weights_version_.store(w.version, std::memory_order_release);
+    accepts_reload_ = FindReload().all();
     // Ensemble requests: the contexts and the output / fp32 staging take the 7 extra samples of each of the E requests a batch
     // can expand; with E = 0 (or a device library without the entry point) every size below is what it was.
     submit_symm_ = cfg_.ensemble_slots > 0 ? FindInDeviceLibrary("sayuri_hip_submit_packed_symm") : nullptr;
@@ -315,12 +357,58 @@ void HipForwardPipe::DestroyGraphs() {
 
 void HipForwardPipe::Release() { DestroyGraphs(); }
 
+// For each graph: begin -> tensors -> prepare on the caller's thread, beside the pump's batches (the device library lets these
+// three run next to submit / wait), then the commits.  Nothing is committed before every graph is prepared: a refusal leaves all
+// of them on the old network.
+void HipForwardPipe::Reload(std::shared_ptr<DNNWeights> weights) {
+    if (!weights) throw std::runtime_error("HipForwardPipe::Reload: no weights");
+    std::lock_guard<std::mutex> one(reload_mu_);  // one reload at a time; Construct / Release are the owner's, as ever
+    if (graphs_.empty()) throw std::runtime_error("HipForwardPipe::Reload: the pipe is not constructed");
+    const ReloadFns fn = FindReload();
+    if (!fn.all()) throw std::runtime_error("HipForwardPipe::Reload: the device library has no live-reload entry points (sayuri_hip_reload_*)");
+    NetDesc nd;
+    DescribeNet(*weights, &nd);
+    size_t opened = 0;
+    try {
+        for (auto& g : graphs_) {
+            if (fn.begin(g->ctx, &nd.d)) ThrowHip("sayuri_hip_reload_begin");
+            ++opened;
+            LoadTensors(g->ctx, *weights);
+            if (fn.prepare(g->ctx)) {  // (a failed prepare has closed its reload itself)
+                --opened;
+                ThrowHip("sayuri_hip_reload_prepare");
+            }
+        }
+    } catch (...) {
+        for (size_t i = 0; i < opened; ++i) (void)fn.abort(graphs_[i]->ctx);
+        throw;
+    }
+    // the light step: a pointer flip per graph, serialised with the pump's submit by the context itself
+    for (size_t i = 0; i < graphs_.size(); ++i)
+        if (fn.commit(graphs_[i]->ctx) < 0) {
+            // (cannot happen after a successful prepare short of a device error; graphs before i serve the new network already)
+            const std::string why = sayuri_hip_last_error();
+            for (size_t k = i; k < graphs_.size(); ++k) (void)fn.abort(graphs_[k]->ctx);
+            throw std::runtime_error("sayuri_hip_reload_commit: " + why);
+        }
+    weights_version_.store(weights->version, std::memory_order_release);
+    weights_ = std::move(weights);
+}
+
+int HipForwardPipe::WeightsGeneration() const {
+    const ReloadFns fn = FindReload();
+    if (!fn.generation || graphs_.empty()) return 0;
+    int g = fn.generation(graphs_[0]->ctx);
+    for (auto& gr : graphs_) g = std::min(g, fn.generation(gr->ctx));
+    return g;
+}
+
 void HipForwardPipe::Destroy() { DestroyGraphs(); }
 
 // Copy one request into staging slot `slot`, re-padding a smaller board top-left into the NN
 // grid (what SendQueryAndWait does with a temporary InputData, batch_forward_pipe.cc:15-33).
 void HipForwardPipe::StageInput(Staging* st, int slot, const InputData& in, bool already_padded) {
-    const int B = board_size_, bs = in.board_size, C = weights_->input_channels;
+    const int B = board_size_, bs = in.board_size, C = shape_.input_channels;
     if (bs < 2 || bs > B) throw std::runtime_error("InputData board size does not fit the NN board");
     float* dst = st->planes + static_cast<size_t>(slot) * C * B * B;
     st->bsz[slot] = bs;
@@ -335,7 +423,7 @@ void HipForwardPipe::StageInput(Staging* st, int slot, const InputData& in, bool
                         sizeof(float) * bs);
 }
 
-int HipForwardPipe::BinaryPlanes() const { return PackedPlanes::BinaryPlanes(weights_->input_channels); }
+int HipForwardPipe::BinaryPlanes() const { return PackedPlanes::BinaryPlanes(shape_.input_channels); }
 
 // The packed flavour: the record goes into the pinned packed buffer as it is -- the bits are in the sample's own cell
 // order, the device kernel knows the sample's board size, nothing is re-padded.
@@ -349,7 +437,7 @@ void HipForwardPipe::StagePacked(Staging* st, int slot, const PackedPlanes& in) 
 // A packed slot of a batch that also holds fp32 requests: expand it into the fp32 staging (NN grid), pump thread.  An ensemble
 // slot's symmetries 1..7 go to their device samples the same way, each cell taken through PackedPlanes::SymmetryIndex.
 void HipForwardPipe::ExpandPacked(Staging* st, int slot, int dst_slot, int symmetry) {
-    const int B = board_size_, bs = st->bsz[slot], C = weights_->input_channels, nbin = BinaryPlanes();
+    const int B = board_size_, bs = st->bsz[slot], C = shape_.input_channels, nbin = BinaryPlanes();
     const std::uint32_t* rec = st->packed + static_cast<size_t>(slot) * PackedPlanes::RecordWords(nbin);
     float* dst = st->planes + static_cast<size_t>(dst_slot) * C * B * B;
     std::memset(dst, 0, sizeof(float) * C * B * B);
@@ -369,7 +457,7 @@ void HipForwardPipe::ExpandPacked(Staging* st, int slot, int dst_slot, int symme
 // pass[0] for every offset, cuda_forward_pipe.cc:1074, is a known discrepancy) fused with the
 // un-padding of SendQueryAndWait (batch_forward_pipe.cc:48-68).
 void HipForwardPipe::FillOutput(const Staging* g, int slot, const Echo& in, bool unpad, OutputResult* out) const {
-    DNNWeights& w = *weights_;
+    const NetShape& w = shape_;  // (not weights_: Reload replaces that pointer while callers fill their outputs)
     const int B = board_size_, B2 = B * B, bs = in.board_size;
     const bool v1 = w.version <= 2;  // Encoder::GetEncoderVersion, encoder.h:64-77
     int offset = v1 ? 0 : static_cast<int>(in.offset);
@@ -864,7 +952,7 @@ std::vector<OutputResult> HipForwardPipe::BatchForward(int gpu, const std::vecto
     if (n == 0) return outs;
     Graph* g = graphs_[gpu].get();
     // pageable scratch staging of its own: the pinned sets belong to the queue path
-    DNNWeights& w = *weights_;
+    const NetShape& w = shape_;
     const size_t B2 = static_cast<size_t>(board_size_) * board_size_;
     Staging s;
     std::vector<float> planes(static_cast<size_t>(n) * w.input_channels * B2), prob(static_cast<size_t>(n) * w.probabilities_channels * B2),

@@ -108,6 +108,19 @@ public:
     bool AcceptsGroup() const SAYURI_EXT_OVERRIDE { return true; }
     void ForwardGroup(const PackedPlanes* in, int n, OutputResult* out) SAYURI_EXT_OVERRIDE;
 
+    // A new network of the same architecture into the running pipe (pipe_api.h).  Each device context stages and builds the new
+    // weight set on the CALLER's thread while the pump keeps sending batches, then all contexts commit; batches submitted before
+    // a context's commit finish on the old set.  Throws with the device's message when a step is refused -- nothing was committed
+    // then, the pipe serves the old network.  AcceptsReload() is false on a device library without sayuri_hip_reload_*.
+    // Construct(option, weights) keeps its meaning: it rebuilds the graphs.
+    bool AcceptsReload() const SAYURI_EXT_OVERRIDE { return accepts_reload_; }
+    void Reload(std::shared_ptr<DNNWeights> weights) SAYURI_EXT_OVERRIDE;
+    // With several GPUs the graphs commit one after the other (microseconds apart) while requests keep being routed round robin:
+    // until Reload has returned, one caller may get the new network from one graph and then the old one from the next.  "Old
+    // answers, then new ones" holds per graph, and for every request that begins after Reload has returned.
+    int WeightsGeneration() const;  // commits every graph has seen: 0 = never reloaded
+    int WeightsVersion() const { return weights_version_.load(std::memory_order_acquire); }  // DNNWeights::version of the network in use
+
     // batch_forward_pipe.h:27-28.  `inputs` are already re-padded into the NN grid.
     std::vector<OutputResult> BatchForward(int gpu, const std::vector<InputData>& inputs);
 
@@ -245,6 +258,13 @@ private:
     void ExpandPacked(Staging* s, int slot, int dst_slot, int symmetry);
     void FillOutput(const Staging* s, int slot, const Echo& in, bool unpad, OutputResult* out) const;
 
+    // what the callers' own code reads of the network (staging, outputs): fixed by the architecture, so a reload does not move it
+    struct NetShape { int version, input_channels, probabilities_channels, pass_probability_outputs, value_misc_outputs; };
+    NetShape shape_{};
+    bool accepts_reload_{false};
+    std::atomic<int> weights_version_{-1};
+    std::atomic<bool> valid_{false};  // weights_ != nullptr, for callers that ask while Reload replaces the pointer
+    std::mutex reload_mu_;
     HipPipeConfig cfg_;
     int board_size_{0};
     int max_batch_{0};

@@ -108,6 +108,13 @@ public:
     // for other callers' requests before it sends them.
     virtual bool AcceptsGroup() const { return false; }
     virtual void ForwardGroup(const PackedPlanes*, int, OutputResult*) { throw std::runtime_error("this pipe does not take group requests"); }
+    // Extension: a new network of the SAME architecture into the running pipe.  Reload returns when every device graph has
+    // taken it: a request that begins afterwards gets the new network, one in flight is finished by the network it was sent to,
+    // no request fails because of a reload.  It throws when the weights are refused (another architecture, a device library
+    // without the entry points): the pipe then keeps serving the old network.  A pipe over several devices may switch them one
+    // after the other: while Reload runs, consecutive requests of one caller may be answered by the new and then the old network.
+    virtual bool AcceptsReload() const { return false; }
+    virtual void Reload(std::shared_ptr<DNNWeights>) { throw std::runtime_error("this pipe does not take a weight reload"); }
     std::string GetName() const;
     int GetVersion() const;
     std::shared_ptr<DNNWeights> weights_{nullptr};

@@ -188,6 +188,22 @@ class HipForwardPipe:
             raise RuntimeError(_lib.host().sayuri_host_last_error().decode())
         return [np.concatenate([out[i, :int(bsz[i]) ** 2], out[i, 361:361 + int(bsz[i]) ** 2], out[i, 722:]]) for i in range(n)]
 
+    def AcceptsReload(self) -> bool:
+        """False on a device library without the live-reload entry points (sayuri_hip_reload_*)."""
+        return bool(_lib.host().sayuri_pipe_accepts_reload(self._h))
+
+    def Reload(self, weights_path: str):
+        """A new network of the SAME architecture into the running pipe (HipForwardPipe::Reload): parsed, staged and built on
+        this thread while other threads' requests keep being served, then swapped in between two batches.  Returns when every
+        GPU's context has it: a request that begins afterwards gets the new network.  Raises with the loader's or the device's
+        message when the file or the architecture is refused; the pipe then serves the network it had."""
+        if _lib.host().sayuri_pipe_reload(self._h, weights_path.encode()):
+            raise RuntimeError(f"HipForwardPipe.Reload: {_lib.host().sayuri_host_last_error().decode()}")
+
+    def weights_generation(self) -> int:
+        """0 for a pipe that was never reloaded, +1 per reload."""
+        return int(_lib.host().sayuri_pipe_weights_generation(self._h))
+
     def AcceptsEnsemble(self) -> bool:
         return bool(_lib.host().sayuri_pipe_accepts_ensemble(self._h))
 

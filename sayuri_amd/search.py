@@ -38,6 +38,7 @@ def lib() -> ctypes.CDLL:
         h.sayuri_engine_net_output.argtypes = [vp, vp, ci, ci, cf, ci, u64, vp]
         h.sayuri_engine_net_set_device_ensemble.argtypes = [vp, ci]
         h.sayuri_engine_net_set_group_forward.argtypes = [vp, ci]
+        h.sayuri_engine_net_reload.argtypes = [vp, ctypes.c_char_p]
         h.sayuri_engine_search_flight_stats.argtypes = [vp, vp]
         h.sayuri_engine_search_round_seconds.argtypes = [vp, vp]
         h.sayuri_engine_search_new.restype = vp
@@ -110,6 +111,13 @@ class Network:
         """NetworkOptions::group_forward (also the option `group_forward`): the leaves of one round of a search with
         playouts_in_flight > 1 as one ForwardGroup of the pipe, or one by one.  The results are the same, bit for bit."""
         lib().sayuri_engine_net_set_group_forward(self._h, int(on))
+
+    def reload(self, weights_path: str):
+        """Network::SwapWeights: the network in `weights_path` (same architecture) into the facade's running pipe; from the
+        return on the position cache serves no result of the old weights.  Raises with the loader's or the pipe's message when
+        the file or the architecture is refused, or the backend is not a pipe that reloads: the facade is unchanged then."""
+        if lib().sayuri_engine_net_reload(self._h, weights_path.encode()):
+            raise RuntimeError(f"Network.reload: {lib().sayuri_engine_last_error().decode()}")
 
     def output(self, game: Game, ensemble: int = 0, symmetry: int = 0, temperature: float = 1.0, use_cache: bool = False,
                seed: int = 0) -> np.ndarray:
@@ -214,6 +222,7 @@ def selfplay(pipe=None, options: dict | None = None, seconds: float = 0.0, move_
             snap = {k: int(st[i]) for i, k in enumerate(STAT_NAMES)}
             snap["finished_moves"], snap["prerolled_moves"] = int(st[10]), int(st[11])
             snap["chunks_saved_window"], snap["writer_cpu_seconds"] = int(st[12]), st[14] / 1e9
+            snap["weight_swaps"] = int(st[18])
             snap["elapsed"] = float(elapsed)
             return 1 if on_stats(snap, bool(local_halt)) else 0
         except BaseException as e:  # an exception must not unwind through the C frames
@@ -236,6 +245,7 @@ def selfplay(pipe=None, options: dict | None = None, seconds: float = 0.0, move_
     out["chunks_saved_window"] = int(stats[12])
     out["writer_cpu_seconds"], out["writer_cpu_seconds_window"] = stats[13] / 1e9, stats[14] / 1e9
     out["bytes_written"], out["text_bytes"], out["writer_flush_seconds"] = int(stats[15]), int(stats[16]), stats[17] / 1e9
+    out["weight_swaps"] = int(stats[18])  # networks swapped in live (option live_weights=1)
     out["elapsed"] = el.value
     return out
 
