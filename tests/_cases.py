@@ -762,3 +762,88 @@ def planes_of_records(records, binary, cbsz, cin, board):
         out[j, :binary, :bs, :bs] = record_bits(records[j], binary, np.arange(bs * bs)).reshape(binary, bs, bs)
         out[j, binary:, :bs, :bs] = records[j][binary * 12:binary * 12 + cin - binary].view(np.float32)[:, None, None]
     return out.reshape(len(cbsz), cin, board * board)
+
+
+# ====================================================================================================================
+# The activation sweep (test_gpu_act_sweep.py, test_act_sweep_reference_cpu.py): an identity convolution -- a channel permutation in
+# the centre tap, bias 0 -- delivers any chosen value exactly to an epilogue, so one layer puts every finite fp16 value through it.
+SWEEP_SEED = 1905
+F16_FINITE = np.concatenate([np.arange(0x0000, 0x7C00, dtype=np.uint16), np.arange(0x8000, 0xFC00, dtype=np.uint16)])   # 63 488 patterns
+# every activation's edges: 0, HardSwish's +-3, Mish's guard at 20, +-11.09 where fp16 exp overflows, the ends of the range
+SWEEP_EDGES = (0.0, -0.0, 3.0, -3.0, 20.0, 11.09, -11.09, 65504.0, -65504.0)
+# fp32 engine: points next to the edges that are no fp16 values, and +-87.3 / +-88.8 / +-104 where fp32 exp under- and overflows
+F32_POINTS = np.array([np.nextafter(np.float32(v), np.float32(d)) for v in (0.0, 3.0, -3.0, 20.0) for d in (-np.inf, np.inf)] +
+                      [87.3, -87.3, 88.8, -88.8, 104.0, -104.0], np.float32)
+SWEEP_MODES = ("none", "sweep", "small")   # no residual; another permutation of the same sweep; a small residual (|z| < 32 off the grid)
+
+
+def sweep_edge_bits():
+    """the fp16 patterns of SWEEP_EDGES and of their fp16 neighbours on both sides (where finite)"""
+    b = np.array(SWEEP_EDGES, np.float16).view(np.uint16).astype(np.int64)
+    bits = np.concatenate([b, b + 1, b - 1])
+    bits = bits[((bits & 0x7FFF) < 0x7C00) & (bits >= 0)]
+    return np.unique(bits.astype(np.uint16))
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_values(n, seed, normals_only=False, f32_points=False):
+    """n >= 63 488 (+ the fp32 points) pre-activations as float32: every finite fp16 value once (normals_only: the 61 442 zeros
+    and normals), the fp32 points once where asked, the remaining slots repeats of the edges and their neighbours, shuffled with
+    a fixed seed.  Read-only."""
+    pool = F16_FINITE
+    if normals_only:
+        pool = pool[((pool & 0x7FFF) >= 0x0400) | ((pool & 0x7FFF) == 0)]
+    vals = pool.view(np.float16).astype(np.float32)
+    if f32_points:
+        vals = np.concatenate([vals, F32_POINTS])
+    assert n >= len(vals), (n, len(vals))
+    edges = sweep_edge_bits()
+    if normals_only:
+        edges = edges[((edges & 0x7FFF) >= 0x0400) | ((edges & 0x7FFF) == 0)]
+    edges = edges.view(np.float16).astype(np.float32)
+    fill = np.resize(np.concatenate([edges, F32_POINTS]) if f32_points else edges, n - len(vals))
+    out = np.concatenate([vals, fill])
+    out = out[np.random.default_rng([SWEEP_SEED, seed, n]).permutation(n)]
+    out.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_small(n, seed):
+    """n fp16 values spread over (-16, 16), as float32: the small residual"""
+    out = np.random.default_rng([SWEEP_SEED, seed, n, 3]).uniform(-16.0, 16.0, n).astype(np.float16).astype(np.float32)
+    out.setflags(write=False)
+    return out
+
+
+def sweep_planes(v, bsz, C):
+    """a flat draw cut into per-sample [C][b*b] planes (views)"""
+    outs, off = [], 0
+    for b in bsz:
+        outs.append(v[off:off + C * b * b].reshape(C, b * b))
+        off += C * b * b
+    assert off == len(v)
+    return outs
+
+
+def sweep_inputs(bsz, C, mode, seed=0, normals_only=False, f32_points=False):
+    """(xs, res | None) of one sweep case over the boards bsz with C channels; mode one of SWEEP_MODES"""
+    n = C * sum(b * b for b in bsz)
+    xs = sweep_planes(sweep_values(n, seed, normals_only, f32_points), bsz, C)
+    if mode == "none":
+        return xs, None
+    return xs, sweep_planes(sweep_values(n, seed + 1000, normals_only, f32_points) if mode == "sweep" else sweep_small(n, seed), bsz, C)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_perm(C, seed, identity=False):
+    """the channel permutation pi of a case (identity: a depthwise tap has no other)"""
+    return np.arange(C) if identity else np.random.default_rng([SWEEP_SEED, seed, C, 7]).permutation(C)
+
+
+def perm_weights(pi, k, depthwise=False):
+    """w[c][pi(c)][centre] = 1, everything else 0 (depthwise: w[c][0][centre] = 1) -> [C][C | 1][k][k] float32"""
+    C = len(pi)
+    w = np.zeros((C, 1 if depthwise else C, k, k), np.float32)
+    w[np.arange(C), 0 if depthwise else pi, k // 2, k // 2] = 1.0
+    return w

@@ -1,5 +1,6 @@
 """The numpy references of the kernel parity tests, each once: float64 restatements of what the CPU oracle computes (the
-activations, the direct convolution, the SE unit, the head tail) and the exact-arithmetic reference of test_gpu_exact.py.  No
+activations, the direct convolution, the SE unit, the head tail), the exact-arithmetic reference of test_gpu_exact.py and the
+reference, bound and predicate of the activation sweep (test_gpu_act_sweep.py).  No
 GPU, no device library: the test_*_reference_cpu.py modules pin these functions to the oracle and to each other.
 
 conv_ref is the general layer (any k, depthwise, residual in front of or behind the activation) written as the oracle writes
@@ -326,3 +327,146 @@ def pack_image_ref(fp16, bsz, max_board, cin, sentinel, planes=None, records=Non
                     rows[pend - 1] = sentinel
         img[i * B2:i * B2 + bs * bs] = rows
     return img
+
+
+# ---- the activation sweep (test_gpu_act_sweep.py states the principle; test_act_sweep_reference_cpu.py pins what follows)
+ACT_NAMES = ("identity", "relu", "elu", "selu", "gelu", "mish", "swish", "hardswish")
+ACT_K = 8.0          # fp32 evaluation: K * 2^-24 * max(1, |z|, |ref|); derived in the GPU module's docstring, never from a GPU run
+F16_OVERFLOW = 65520.0   # the tie between 65504 and the next binade: an fp16 store gives inf from here on
+SELU_SCALE, SELU_ALPHA = 1.05070098, 1.67326324
+
+
+def act_f64(z, act):
+    """The eight activations in float64, in forms that stay finite and accurate over |z| <= 1.4e5 (act_np's Mish and Swish
+    overflow exp past 709 and lose the tails)."""
+    z = np.asarray(z, np.float64)
+    neg = np.minimum(z, 0.0)
+    if act == 0:
+        return z
+    if act == 1:
+        return np.maximum(z, 0.0)
+    if act == 2:
+        return np.where(z > 0, z, np.expm1(neg))
+    if act == 3:
+        return np.where(z > 0, SELU_SCALE * z, SELU_SCALE * SELU_ALPHA * np.expm1(neg))
+    if act == 4:   # tanh form; tanh saturates to +-1 without overflow
+        return 0.5 * z * (1.0 + np.tanh(0.7978845608028654 * (z + 0.044715 * z * z * z)))
+    if act == 5:   # z * tanh(softplus(z)); softplus(z) = z past 30 (log1p(exp(-30)) = 9e-14 of 30), log1p(exp(z)) below
+        return z * np.tanh(np.where(z > 30.0, z, np.log1p(np.exp(np.minimum(z, 30.0)))))
+    if act == 6:   # two-sided: z / (1 + e^-z) for z >= 0, z e^z / (1 + e^z) below
+        e = np.exp(-np.abs(z))
+        return np.where(z >= 0, z / (1.0 + e), z * e / (1.0 + e))
+    if act == 7:
+        return np.where(z >= 3, z, np.where(z <= -3, 0.0, z * (z + 3.0) / 6.0))
+    raise ValueError(act)
+
+
+def ulp16(v):
+    """the spacing of fp16 at v: 2^(e - 10) with e the exponent of |v| held to [-14, 15] -- 2^-24 below 2^-14, 32 from 32768 on"""
+    a = np.abs(np.asarray(v, np.float64))
+    _, ex = np.frexp(a)
+    return np.ldexp(1.0, np.clip(np.where(a == 0, -14, ex - 1), -14, 15) - 10)
+
+
+def act_bound(ref, z, store16=True, K=ACT_K):
+    """|got - ref| <= ulp16(ref) / 2 (the one round-to-nearest fp16 store; dropped for an fp32 store) + K 2^-24 max(1, |z|, |ref|)"""
+    ref, z = np.asarray(ref, np.float64), np.asarray(z, np.float64)
+    b = K * 2.0 ** -24 * np.maximum(1.0, np.maximum(np.abs(z), np.abs(ref)))
+    return b + 0.5 * ulp16(ref) if store16 else b
+
+
+def act_sweep_bad(got, z, act, store16=True, post_res=None, K=ACT_K):
+    """The predicate of the activation sweep on flat arrays.  z: the exact float64 argument of the activation (x + res);
+    post_res: a residual added BEHIND the activation (the depthwise order), so ref = act(z) + post_res.
+    identity / ReLU: got == store(ref) value for value (-0 equals +0, inf equals inf where store(ref) overflows, NaN nothing).
+    the other six: no NaN; finite got within act_bound of ref; +-inf (of ref's sign) only if |ref| + bound >= 65520, and
+    required if |ref| - bound >= 65520 (fp16 store; an fp32 store never overflows on these data).
+    -> (bad mask, |got - ref| / bound where both are finite, else 0)"""
+    got, z = np.asarray(got, np.float64).ravel(), np.asarray(z, np.float64).ravel()
+    ref = act_f64(z, act)
+    if post_res is not None:
+        ref = ref + np.asarray(post_res, np.float64).ravel()
+    assert got.shape == ref.shape and np.isfinite(ref).all()
+    if act in (0, 1):
+        with np.errstate(over="ignore"):
+            exp = ref.astype(np.float16 if store16 else np.float32).astype(np.float64)
+        return got != exp, np.zeros(got.shape)
+    bound = act_bound(ref, z, store16, K)
+    lim = F16_OVERFLOW if store16 else np.inf
+    fin = np.isfinite(got)
+    with np.errstate(invalid="ignore"):
+        err = np.where(fin, np.abs(got - ref), 0.0)
+    bad = np.isnan(got)
+    bad |= np.isinf(got) & ((np.abs(ref) + bound < lim) | (np.sign(got) != np.sign(ref)))
+    bad |= fin & (np.abs(ref) - bound >= lim)
+    bad |= fin & (err > bound)
+    return bad, err / bound
+
+
+def act_units_used(got, z, act, store16=True, post_res=None):
+    """how much of K the finite outputs use: the largest (|got - ref| - the store's half ulp) / (2^-24 max(1, |z|, |ref|)); a record, no
+    input to the bound"""
+    got, z = np.asarray(got, np.float64).ravel(), np.asarray(z, np.float64).ravel()
+    ref = act_f64(z, act) + (0.0 if post_res is None else np.asarray(post_res, np.float64).ravel())
+    fin = np.isfinite(got)
+    with np.errstate(invalid="ignore"):
+        over = np.where(fin, np.abs(got - ref), 0.0) - (0.5 * ulp16(ref) if store16 else 0.0)
+    return float(np.max(np.where(fin, over, 0.0) / act_bound(ref, z, False, 1.0), initial=0.0))
+
+
+ACT_DEFECTS = ("hswish_edge_2.5", "hswish_times_0.1667", "selu_alpha_1.67", "selu_scale_1.0507", "gelu_coef_0.0455", "gelu_erf",
+               "mish_guard_2", "swish_no_log2e", "elu_no_log2e")
+
+
+def act_f32_emu(x, act, defect=None):
+    """common.h's activate() restated in numpy float32, operation for operation (fast_exp = exp2(x * log2e), __expf = numpy's
+    float32 exp -- its error is the larger of the two ways to state it: exp2(x * log2e) gives ELU 1.21 and SELU 2.62 in the K
+    table --, rcp = 1 / t, fma through float64); numpy's exp2 and division are correctly rounded where v_exp_f32 / v_rcp_f32 are
+    good to 1 ulp.
+    defect: one of ACT_DEFECTS, the value a kernel with that mistake would form.  -> float32, before the store"""
+    assert defect is None or defect in ACT_DEFECTS, defect
+    f = np.float32
+    x = np.asarray(x, f)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore", divide="ignore"):
+        fast_exp = lambda v, log2e=f(1.4426950408889634): np.exp2(v * log2e)
+        fma = lambda a, b, c: (a.astype(np.float64) * np.asarray(b, np.float64) + c).astype(f)
+        if act == 0:
+            return x
+        if act == 1:
+            return np.where(x > 0, x, f(0))
+        if act in (2, 3):
+            e = np.exp2(x) if defect == "elu_no_log2e" else np.exp(x)   # __expf
+            if act == 2:
+                return np.where(x > 0, x, e - f(1))
+            scale = f(1.0507) if defect == "selu_scale_1.0507" else f(1.05070098)
+            alpha = f(1.67) if defect == "selu_alpha_1.67" else f(1.67326324)
+            return np.where(x > 0, scale * x, (scale * alpha) * (e - f(1)))
+        if act == 4:
+            if defect == "gelu_erf":
+                import math
+                return (0.5 * x.astype(np.float64) * (1.0 + np.vectorize(math.erf)(x.astype(np.float64) / math.sqrt(2.0)))).astype(f)
+            c = f(0.0455) if defect == "gelu_coef_0.0455" else f(0.044715)
+            u = f(0.7978845608028654) * (x + c * x * x * x)
+            t = f(1) - f(2) / (fast_exp(f(2) * u) + f(1))
+            return f(0.5) * x * (f(1) + t)
+        if act == 5:
+            e = fast_exp(x)
+            r = f(1) / fma(e, e + f(2), 2.0)
+            return np.where(x > (2 if defect == "mish_guard_2" else 20), x, x * fma(np.full(x.shape, -2, f), r, 1.0))
+        if act == 6:
+            return x / (f(1) + (np.exp2(-x) if defect == "swish_no_log2e" else fast_exp(-x)))
+        if act == 7:
+            mid = x * (x + f(3)) * f(0.1667) if defect == "hswish_times_0.1667" else x * (x + f(3)) / f(6)
+            return np.where(x >= (2.5 if defect == "hswish_edge_2.5" else 3), x, np.where(x <= -3, f(0), mid))
+    raise ValueError(act)
+
+
+def f16_store_toward_zero(a):
+    """float32 -> fp16 by truncation over the whole range (subnormals and overflow to the largest finite value included), as
+    float32: the planted store defect of the activation sweep"""
+    a = np.asarray(a, np.float32)
+    with np.errstate(over="ignore"):
+        n = a.astype(np.float16)
+    bits = n.view(np.uint16)
+    away = np.abs(n.astype(np.float64)) > np.abs(a.astype(np.float64))   # rounded away from zero (inf included): one step back
+    return np.where(away, bits - np.uint16(1), bits).astype(np.uint16).view(np.float16).astype(np.float32)

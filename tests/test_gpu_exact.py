@@ -9,7 +9,8 @@ order, in any MFMA, with any split of the channels -- is a multiple of 2^-q belo
 accumulator holds the exact sum S.  The kernels' contract (fp16 operands, fp32 accumulate, bias and residual added in fp32, ONE
 round-to-nearest-even fp16 store) then leaves exactly one result, float16(act(S)) for act = identity / ReLU, which is what
 np.float64(S).astype(np.float16) gives.  exact_layer computes it and asserts the regime itself (A * 2^q < 2^24, |S| < 65504), so
-a case outside it cannot run.  Values are compared with ==, so that -0 equals +0.
+a case outside it cannot run.  Values are compared with ==, so that -0 equals +0.  The other six activations are no exact
+functions: test_gpu_act_sweep.py puts every finite fp16 value through each kernel's epilogue for all eight.
 
 Two draws.  unit: x in [-2, 2], w in {-1, 0, 1}, bias in [-8, 8], residual in [-16, 16] -- every output is itself an fp16 value,
 nothing rounds: the tier for "every product of every tap, channel and pixel lands in the right place".  wide: x in [-16, 16], w
